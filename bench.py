@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — stereo frames/s of the MI355X-native HRIR spatializer on BASELINE.json's workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 starts the N ranks itself (one process per GPU through `python -m torch.distributed.run`, before
 anything in this process touches the GPU); launched under torchrun (WORLD_SIZE set) it is one of the ranks:
@@ -16,7 +16,9 @@ already resident in HBM.  Default workload = the configuration BASELINE.json's m
 through a parseHeSuViFormat text map) is measured in the same run and reported as `"secondary"` inside the one JSON line.
 `--workload cfg1|cfg2|cfg2-14ch|cfg4|cfg5|cfg3-14ch` benches the other BASELINE configurations on request.  After the timed
 region (untimed, in the CPU-baseline leg) two streams' head and tail of the last step are compared with the float64 oracle:
-`parity_spot_err` (primary and secondary); above 1e-5 the exit code is 3.
+`parity_spot_err` (primary and secondary); above 1e-5 the exit code is 3.  `--dump-outputs DIR` writes what the last timed step
+of the headline workload returned (its stereo output, a seeded sample of streams when it exceeds 64 MB) to DIR/*.npy, so that two
+builds run with the same arguments (hence the same seeded inputs) can be compared output for output.
 
 Streams are independent, so N GPUs = N ranks each owning its own batch (weak scaling, no data-path collective); RCCL
 carries only the final {frames (sum), elapsed (max)} aggregate.  One JSON line on rank 0.
@@ -210,6 +212,46 @@ def oracle_spot_check(x_dev, y_dev, tracks, lt, rt, calls: int, streams=(0, -1),
     return worst
 
 
+# ---------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_BUDGET_BYTES = 60 << 20      # all arrays of one dump together (64 MB is the bound; npy headers and the id files fit in the rest)
+DUMP_SEED = 0xD0E5                # the stream sample of a leg larger than its share of the budget
+
+
+def dump_outputs(out_dir: str, name: str, legs, global_ids, rank: int, world: int) -> list:
+    """--dump-outputs: what the timed path handed its caller in the LAST timed step, so that two builds can be compared output for
+    output (the inputs are seeded, so the same arguments give the same inputs).  Per leg the stereo output y[streams, frames, 2] as the
+    kernels wrote it (float32) goes to <out_dir>/<name>[_rank<r>]_y[_lane<l>_<rate>Hz].npy, and the global ids of the streams in it
+    (float64) to the same name with _stream_ids.  A leg larger than its share of the budget keeps a fixed, seeded set of whole
+    streams (always the first and the last); a single stream larger than the share keeps its first frames.  Returns the paths."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (world * len(legs))
+    stem = name + (f"_rank{rank}" if world > 1 else "")
+    written = []
+    for g in legs:
+        n, F = g["n"], g["F"]
+        k, frames = min(n, share // (8 * F)), F
+        if k == 0:
+            k, frames = 1, share // 8
+        if k == n:
+            local = np.arange(n)
+        elif k == 1:
+            local = np.array([0])
+        else:
+            rest = np.random.default_rng(DUMP_SEED).choice(np.arange(1, n - 1), size=k - 2, replace=False)
+            local = np.sort(np.concatenate([[0, n - 1], rest]))
+        idx = torch.as_tensor(local, dtype=torch.int64, device=g["y"].device)
+        y = g["y"].index_select(0, idx)[:, :frames].cpu().numpy()
+        ids = np.array([global_ids[g["first"] + int(i)] for i in local], dtype=np.float64)
+        tag = stem + "_y" + (f"_lane{g['lane']}_{g['rate']}Hz" if len(legs) > 1 else "")
+        for suffix, a in (("", y), ("_stream_ids", ids)):
+            path = os.path.join(out_dir, tag + suffix + ".npy")
+            np.save(path, a)
+            written.append(path)
+    return written
+
+
 # ---------------------------------------------------------------------------------------------- one workload
 def flops_per_frame(C: int, path: dict) -> float:
     """Algorithmic flops of the transforms THIS implementation runs per output frame (for the FP32-vector roof)."""
@@ -244,7 +286,8 @@ def measured_ceilings(ctx) -> dict:
             "source": "aw_context_bandwidth_probe on this box, this process, before the timed region"}
 
 
-def run_workload(name: str, args, ctx, world: int, rank: int, backend: str, with_cpu: bool, with_check: bool = None, measured: dict = None, eq_mode: str = None):
+def run_workload(name: str, args, ctx, world: int, rank: int, backend: str, with_cpu: bool, with_check: bool = None, measured: dict = None, eq_mode: str = None,
+                 dump_dir: str = None):
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -366,6 +409,10 @@ def run_workload(name: str, args, ctx, world: int, rank: int, backend: str, with
     elapsed = time.perf_counter() - t0
     step_ms = ev0.elapsed_time(ev1) / steps
     frames_step = sum(g["n"] * g["F"] for g in legs)
+    if dump_dir:                  # after the timed region, before anything below runs the buffers again (the EQ parity leg does)
+        paths = dump_outputs(dump_dir, name, legs, global_ids, rank, world)
+        print(f"[bench rank {rank}/{world}] --dump-outputs: {len(paths)} files, {sum(os.path.getsize(p) for p in paths)} bytes in {dump_dir}",
+              file=sys.stderr, flush=True)
 
     # RCCL over xGMI: the only collective of the run (sum of frames, max of elapsed)
     frames_total, elapsed_max, _ = aggregate_throughput(float(frames_step) * steps, elapsed,
@@ -780,9 +827,15 @@ def main() -> int:
     ap.add_argument("--no-ceiling", action="store_true", help="skip the measured read / write / copy ceiling probe (roofline.measured)")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the PCIe-inclusive secondary legs (secondary_end_to_end)")
     ap.add_argument("--no-warm-activation", action="store_true", help="skip the second, warm-context activation (config.activation_warm)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline workload's output of the last step to DIR/*.npy (a seeded sample of streams, <= 64 MB)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps is not None and args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.warmup is not None and args.warmup < 0:
+        raise SystemExit("--warmup must be >= 0")
 
     # N > 1 and not yet under a launcher: become the launcher.  Nothing above has touched the GPU (no torch.cuda call).
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -836,7 +889,7 @@ def main() -> int:
           + (" (forced one-rank process group)" if force_pg else ""), file=sys.stderr, flush=True)
     ctx = aw.Context(local_rank, stream=torch.cuda.current_stream().cuda_stream)
     measured = measured_ceilings(ctx) if rank == 0 and not args.no_ceiling else None       # before any timed region, on this box
-    result = run_workload(args.workload, args, ctx, world, rank, backend, with_cpu=not args.no_cpu_baseline, measured=measured)
+    result = run_workload(args.workload, args, ctx, world, rank, backend, with_cpu=not args.no_cpu_baseline, measured=measured, dump_dir=args.dump_outputs)
     sec = SECONDARY.get(args.workload)
     if sec and not args.no_secondary and not args.streams and not args.seconds:
         r2 = run_workload(sec, args, ctx, world, rank, backend, with_cpu=False, with_check=not args.no_cpu_baseline, measured=measured)

@@ -70,3 +70,39 @@ def test_traffic_key_survives_a_refused_profile(bench, full, tmp_path, monkeypat
     full["roofline"]["traffic_note"] = "newest profile of this shape predates the current device sources: re-profile"
     d = json.loads(bench.emit(full))
     assert d["roofline"]["traffic"] is None and "re-profile" in d["roofline"]["traffic_note"]
+
+
+def test_dump_outputs_writes_the_last_step_within_the_budget(bench, tmp_path, monkeypatch):
+    """--dump-outputs on host tensors: a leg that fits is written whole; a larger one keeps the same seeded streams every time (first
+    and last included) with their global ids; the files stay float32 / float64 and within the budget."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 5 * 1000 * 8)
+    y = torch.arange(12 * 1000 * 2, dtype=torch.float32).reshape(12, 1000, 2)
+    leg = dict(lane=0, rate=48000, n=12, F=1000, y=y, first=2)
+    ids = list(range(100, 114))
+    runs = []
+    for d in ("a", "b"):
+        paths = bench.dump_outputs(str(tmp_path / d), "cfgX", [leg], ids, 0, 1)
+        assert sorted(os.path.basename(p) for p in paths) == ["cfgX_y.npy", "cfgX_y_stream_ids.npy"]
+        assert sum(os.path.getsize(p) for p in paths) < 5 * 1000 * 8 + 1024
+        runs.append((np.load(tmp_path / d / "cfgX_y.npy"), np.load(tmp_path / d / "cfgX_y_stream_ids.npy")))
+    (ya, ia), (yb, ib) = runs
+    assert ya.dtype == np.float32 and ia.dtype == np.float64 and ya.shape == (len(ia), 1000, 2)
+    assert len(ia) == 5 and ia[0] == 102 and ia[-1] == 113 and np.array_equal(ya, yb) and np.array_equal(ia, ib)
+    assert np.array_equal(ya, y.numpy()[(ia - 102).astype(int)])
+    small = dict(leg, n=2, y=y[:2])
+    bench.dump_outputs(str(tmp_path / "c"), "cfgX", [small], ids, 1, 2)           # two ranks: half the budget each, every stream fits
+    assert np.array_equal(np.load(tmp_path / "c" / "cfgX_rank1_y.npy"), y[:2].numpy())
+    one = dict(leg, n=1, F=1000, y=y[:1])
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 300 * 8)
+    bench.dump_outputs(str(tmp_path / "d"), "cfgX", [one], ids, 0, 1)            # one stream over the budget: its first frames
+    assert np.array_equal(np.load(tmp_path / "d" / "cfgX_y.npy"), y[:1, :300].numpy())
+
+
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--warmup", "-1"]])
+def test_step_counts_out_of_range_are_refused(argv):
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run"] + argv, capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert p.returncode != 0 and "must be" in p.stderr

@@ -100,3 +100,27 @@ def test_strong_scaling_and_equalizer_modes_run_on_the_gpu():
     assert d["config"]["hrir_taps"] == 8640 + eq["response_taps"] - 1 and d["cpu_baseline"]["kind"] == "port"
     d = run("--workload", "cfg4", "--eq", "cascade", "--streams", "16", "--seconds", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-secondary")
     assert "cascade" in d["config"]["equalizer"]["mode"] and d["config"]["hrir_taps"] == 8640 and "f64" in d["dtype"]
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_the_timed_output_and_repeats(tmp_path):
+    """--dump-outputs DIR: the last timed step's stereo output of a seeded sample of streams (a leg over the budget), within 64 MB, the
+    same bits from two runs with the same arguments; --steps sets the timed steps."""
+    import numpy as np
+    argv = ["--workload", "cfg2", "--streams", "24", "--steps", "3", "--warmup", "1", "--cpu-sample-streams", "1",
+            "--no-ceiling", "--no-end-to-end", "--no-warm-activation", "--no-secondary"]
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv + ["--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["parity_spot_err"] < 1e-5
+        assert sorted(os.listdir(out)) == ["cfg2_y.npy", "cfg2_y_stream_ids.npy"]
+        assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 * 10**6
+        dumps.append((np.load(out / "cfg2_y.npy"), np.load(out / "cfg2_y_stream_ids.npy")))
+    (ya, ia), (yb, ib) = dumps
+    assert ya.dtype == np.float32 and ya.shape == (len(ia), 480000, 2) and 2 < len(ia) < 24 and ia[0] == 0 and ia[-1] == 23
+    assert np.isfinite(ya).all() and np.abs(ya).max() > 0
+    assert np.array_equal(ia, ib) and np.array_equal(ya, yb)
