@@ -11,7 +11,7 @@ _capi.load()
 
 from .api import (  # noqa: E402
     AirwaveError, Context, ConvolutionEngine, HRIR, HRIRChannelMap, HRIRError, HRIRManager, InputLayout,
-    RealtimeAudioProcessor, Resampler, Spatializer, WAVData, WAVError, WAVLoader, default_context,
+    RealtimeAudioProcessor, Resampler, SAMPLE_FORMATS, Spatializer, WAVData, WAVError, WAVLoader, default_context, sample_format_bytes,
 )
 
 from .batching import MixedRateBatch, RateBucket, bucket_by_rate, resample_tracks  # noqa: E402
@@ -30,5 +30,5 @@ __all__ = [
     "ParametricEqualizerPreparationError", "ParametricEqualizerProcessor", "ParametricEqualizerState", "EqualizerNotFoldable", "FoldedHRIR", "fold_equalizer",
     "AirwaveError", "Context", "ConvolutionEngine", "HRIR", "HRIRChannelMap", "HRIRError", "HRIRManager",
     "InputLayout", "RealtimeAudioProcessor", "Resampler", "Spatializer", "WAVData", "WAVError", "WAVLoader",
-    "default_context",
+    "default_context", "SAMPLE_FORMATS", "sample_format_bytes",
 ]

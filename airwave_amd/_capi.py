@@ -50,6 +50,10 @@ SIGNATURES = {
     "aw_spatializer_process_planar": (_I32, [_V, c_float_p, c_float_p, c_float_p, c_float_p, _I32]),
     "aw_spatializer_reserve": (_I32, [_V, _I64]),
     "aw_spatializer_reserve_host": (_I32, [_V, _I64]),
+    "aw_sample_format_bytes": (_I32, [_I32]),
+    "aw_spatializer_process_pcm": (_I32, [_V, _V, _I32, _V, _I32, _I64, _V]),
+    "aw_spatializer_process_host_pcm": (_I32, [_V, _V, _I32, _V, _I32, _I64, ctypes.POINTER(ctypes.c_uint64)]),
+    "aw_spatializer_reserve_pcm": (_I32, [_V, _I64, _I32, _I32]),
     "aw_spatializer_reset": (_I32, [_V]),
     "aw_spatializer_stream_count": (_I32, [_V]),
     "aw_spatializer_channel_count": (_I32, [_V]),

@@ -72,6 +72,41 @@ def _i32p(a: np.ndarray):
     return a.ctypes.data_as(c_int32_p)
 
 
+# aw_sample_format (include/airwave_hip.h): sample formats of the PCM entries
+SAMPLE_FORMATS = {"f32": 0, "s16": 1, "s24": 2, "s32": 3}
+_FORMAT_DTYPE = {0: np.dtype(np.float32), 1: np.dtype(np.int16), 2: np.dtype(np.uint8), 3: np.dtype(np.int32)}
+
+
+def sample_format_bytes(fmt) -> int:
+    """aw_sample_format_bytes: 4, 2, 3, 4 for f32, s16, s24, s32; 0 for an unknown format."""
+    code = SAMPLE_FORMATS.get(fmt, -1) if isinstance(fmt, str) else int(fmt)
+    return int(_capi.load().aw_sample_format_bytes(code))
+
+
+def _pcm_array(a, fmt, shape3, what: str) -> Tuple[np.ndarray, int]:
+    """Checks one PCM buffer against its format and the [S, F, C] shape it must have (s24: packed bytes, uint8 [S, F, C, 3]) and
+    returns (array, aw_sample_format).  fmt None: from the dtype (float32, int16, int32; packed s24 must be named).  Raises before
+    the library is called."""
+    if not isinstance(a, np.ndarray):
+        raise TypeError(f"{what}: a numpy array is required")
+    if fmt is None:
+        code = {np.dtype(np.float32): 0, np.dtype(np.int16): 1, np.dtype(np.int32): 3}.get(a.dtype)
+        if code is None:
+            raise TypeError(f"{what}: dtype {a.dtype} has no implied sample format (float32, int16, int32; packed s24: fmt='s24', uint8 [..., 3])")
+    else:
+        code = SAMPLE_FORMATS.get(fmt) if isinstance(fmt, str) else (int(fmt) if int(fmt) in _FORMAT_DTYPE else None)
+        if code is None:
+            raise ValueError(f"{what}: unknown sample format {fmt!r}")
+        if a.dtype != _FORMAT_DTYPE[code]:
+            raise TypeError(f"{what}: format {fmt!r} needs dtype {_FORMAT_DTYPE[code]}, got {a.dtype}")
+    want = tuple(shape3) + ((3,) if code == 2 else ())
+    if a.shape != want:
+        raise ValueError(f"{what}: shape {a.shape}, expected {want}")
+    if not a.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"{what}: must be C-contiguous")
+    return a, code
+
+
 class Context:
     """Device + stream + shared twiddle tables (FFTSetupManager analogue, FFTSetupManager.swift:41-60)."""
 
@@ -422,12 +457,43 @@ class Spatializer:
         """reserve() plus the device-side staging of the host entry (process / process_host_into)."""
         _check(self._lib.aw_spatializer_reserve_host(self._h, int(max_frames)))
 
-    def process_host_into(self, x: np.ndarray, out: np.ndarray) -> None:
-        """Host entry on caller-owned arrays (e.g. Context.pinned_empty): x [streams][frames][channels], out [streams][frames][2]."""
-        assert x.dtype == np.float32 and out.dtype == np.float32 and x.flags["C_CONTIGUOUS"] and out.flags["C_CONTIGUOUS"]
-        S, F, C = x.shape
-        assert S == self.n_streams and C == self.n_channels and out.shape == (S, F, 2)
-        _check(self._lib.aw_spatializer_process_host(self._h, _fp(x), _fp(out), F))
+    def process_host_into(self, x: np.ndarray, out: np.ndarray, in_format=None, out_format=None) -> int:
+        """Host entry on caller-owned arrays (e.g. Context.pinned_empty): x [streams][frames][channels], out [streams][frames][2].
+        float32 arrays take aw_spatializer_process_host; int16 / int32 arrays (or packed s24: uint8 [..., 3] with the format named,
+        in_format / out_format 's24') take aw_spatializer_process_host_pcm.  Returns the clipped-sample count (0 for float32 output)."""
+        if x.dtype == np.float32 and out.dtype == np.float32 and in_format in (None, "f32", 0) and out_format in (None, "f32", 0):
+            assert x.flags["C_CONTIGUOUS"] and out.flags["C_CONTIGUOUS"]
+            S, F, C = x.shape
+            assert S == self.n_streams and C == self.n_channels and out.shape == (S, F, 2)
+            _check(self._lib.aw_spatializer_process_host(self._h, _fp(x), _fp(out), F))
+            return 0
+        if not isinstance(x, np.ndarray) or x.ndim < 3:
+            raise ValueError("x: [streams][frames][channels] array required")
+        F = x.shape[1]
+        x, fi = _pcm_array(x, in_format, (self.n_streams, F, self.n_channels), "x")
+        out, fo = _pcm_array(out, out_format, (self.n_streams, F, 2), "out")
+        clipped = ctypes.c_uint64(0)
+        _check(self._lib.aw_spatializer_process_host_pcm(self._h, ctypes.c_void_p(x.ctypes.data), fi, ctypes.c_void_p(out.ctypes.data), fo, F,
+                                                         ctypes.byref(clipped)))
+        return int(clipped.value)
+
+    def process_pcm_device(self, in_ptr: int, in_format, out_ptr: int, out_format, frames: int, clipped_ptr: int = 0) -> None:
+        """aw_spatializer_process_pcm on device buffers (asynchronous on the context's stream); formats by name ('f32', 's16', 's24',
+        's32') or code.  clipped_ptr: 0, or a device uint64 the call adds its clipped-sample count to."""
+        codes = []
+        for fmt in (in_format, out_format):
+            code = SAMPLE_FORMATS.get(fmt, -1) if isinstance(fmt, str) else int(fmt)
+            if code not in _FORMAT_DTYPE:
+                raise ValueError(f"unknown sample format {fmt!r}")
+            codes.append(code)
+        _check(self._lib.aw_spatializer_process_pcm(self._h, ctypes.c_void_p(in_ptr), codes[0], ctypes.c_void_p(out_ptr), codes[1], int(frames),
+                                                    ctypes.c_void_p(clipped_ptr or None)))
+
+    def reserve_pcm(self, max_frames: int, in_format, out_format) -> None:
+        """reserve_host() for these sample formats: neither PCM entry allocates afterwards for calls of up to max_frames frames."""
+        fi = SAMPLE_FORMATS.get(in_format, -1) if isinstance(in_format, str) else int(in_format)
+        fo = SAMPLE_FORMATS.get(out_format, -1) if isinstance(out_format, str) else int(out_format)
+        _check(self._lib.aw_spatializer_reserve_pcm(self._h, int(max_frames), fi, fo))
 
     def reset(self) -> None:
         _check(self._lib.aw_spatializer_reset(self._h))

@@ -37,6 +37,7 @@ SOURCES = [
     "device/eq_kernels.hip",
     "device/probe_kernels.hip",
     "device/prep_kernels.hip",
+    "device/pcm_kernels.hip",
     "runtime.cpp",
     "eq_runtime.cpp",
     "host/eq.cpp",

@@ -1,0 +1,78 @@
+// pcm.hpp — element rules of the integer PCM sample formats (aw_sample_format, include/airwave_hip.h), shared by the decode / encode
+// kernels (pcm_kernels.hip), the single-stream host path (runtime.cpp) and a CPU test that compiles this header with plain g++.
+//
+// Decode is aw_wav_load's rule (host/host_api.cpp): s / 2^15, s / 2^23, s / 2^31.  Every scale is a power of two, so the product
+// with 0x1p-15f (and so on) is the same float; for s32, (float)s rounds to nearest-even exactly as (float)((double)s / 2^31) does.
+// Encode is the inverse scale, rounded to nearest with ties to even, then saturated; s32 is computed in double.  NaN encodes to 0.
+// A sample is clipped when the rounded value lies outside the integer range, or when it is NaN or +-inf.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define AWP_HD __host__ __device__ __forceinline__
+#else
+#define AWP_HD inline
+#endif
+
+namespace awp {
+
+enum Format : int { kF32 = 0, kS16 = 1, kS24 = 2, kS32 = 3 };
+
+AWP_HD int format_bytes(int f) { return f == kF32 || f == kS32 ? 4 : f == kS16 ? 2 : f == kS24 ? 3 : 0; }
+
+AWP_HD float decode_s16(int32_t s) { return (float)s * 0x1p-15f; }
+// b0..b2: the three little-endian bytes of a packed s24 sample
+AWP_HD float decode_s24(uint32_t b0, uint32_t b1, uint32_t b2) {
+    const int32_t s = (int32_t)((b0 | (b1 << 8) | (b2 << 16)) << 8) >> 8;     // sign-extend bit 23
+    return (float)s * 0x1p-23f;
+}
+AWP_HD float decode_s32(int32_t s) { return (float)s * 0x1p-31f; }
+
+// Returns the integer sample; *clip is set to 1 when the sample clipped (left untouched otherwise).
+AWP_HD int32_t encode_s16(float x, unsigned *clip) {
+    const float v = rintf(x * 32768.0f);
+    if (v >= -32768.0f && v <= 32767.0f) return (int32_t)v;
+    *clip = 1;
+    return v > 0.0f ? 32767 : v < 0.0f ? -32768 : 0;                         // (NaN: neither)
+}
+AWP_HD int32_t encode_s24(float x, unsigned *clip) {
+    const float v = rintf(x * 8388608.0f);
+    if (v >= -8388608.0f && v <= 8388607.0f) return (int32_t)v;
+    *clip = 1;
+    return v > 0.0f ? 8388607 : v < 0.0f ? -8388608 : 0;
+}
+AWP_HD int32_t encode_s32(float x, unsigned *clip) {
+    const double v = rint((double)x * 2147483648.0);
+    if (v >= -2147483648.0 && v <= 2147483647.0) return (int32_t)v;
+    *clip = 1;
+    return v > 0.0 ? 2147483647 : v < 0.0 ? (int32_t)(-2147483647 - 1) : 0;
+}
+
+// One element at byte address p (any alignment), for the host path and the kernels' unaligned heads and tails.
+AWP_HD float decode_at(int fmt, const unsigned char *p) {
+    switch (fmt) {
+        case kS16: return decode_s16((int16_t)(uint16_t)(p[0] | (p[1] << 8)));
+        case kS24: return decode_s24(p[0], p[1], p[2]);
+        case kS32: return decode_s32((int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24)));
+        default: {
+            const uint32_t u = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+            float f;
+            __builtin_memcpy(&f, &u, 4);
+            return f;
+        }
+    }
+}
+AWP_HD void encode_at(int fmt, float x, unsigned char *p, unsigned *clip) {
+    uint32_t u;
+    switch (fmt) {
+        case kS16: u = (uint32_t)encode_s16(x, clip); break;
+        case kS24: u = (uint32_t)encode_s24(x, clip); break;
+        case kS32: u = (uint32_t)encode_s32(x, clip); break;
+        default: __builtin_memcpy(&u, &x, 4); break;
+    }
+    const int n = format_bytes(fmt);
+    for (int i = 0; i < n; ++i) p[i] = (unsigned char)(u >> (8 * i));
+}
+
+}  // namespace awp

@@ -14,6 +14,8 @@
 #include <thread>
 
 #include "device/eq_kernels.hpp"
+#include "device/pcm.hpp"
+#include "device/pcm_kernels.hpp"
 #include "host/tables.hpp"
 
 // Default fused window: 8192 frames; 16384 (tile_ols2.hpp) where measurements favour it.
@@ -712,6 +714,9 @@ void aw_spatializer_destroy(aw_spatializer *sp) {
     if (sp->h_pin_out) (void)hipHostFree(sp->h_pin_out);
     if (sp->h_bounce_in) (void)hipHostFree(sp->h_bounce_in);
     if (sp->h_bounce_out) (void)hipHostFree(sp->h_bounce_out);
+    if (sp->d_pcm_in) (void)hipFree(sp->d_pcm_in);
+    if (sp->d_pcm_out) (void)hipFree(sp->d_pcm_out);
+    if (sp->d_clip) (void)hipFree(sp->d_clip);
     if (sp->k0) (void)hipEventDestroy(sp->k0);
     if (sp->k1) (void)hipEventDestroy(sp->k1);
     for (auto &pr : sp->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -734,7 +739,7 @@ int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what) {
         case 7: return sp->last_lw_R;         // long-window path: rows R of the last call's windows (N = R x 4096); 0 = the partitioned kernels ran
         case 8: return sp->last_lw_R2;        // rows of the last call's remainder window when it ran as two groups of windows (0: one group)
         case 9: return (int64_t)sp->lw_plans.size();   // long-window table sets built so far (one per window length; reserve builds those of its plan)
-        case 6: return (int64_t)(sp->ctx->pool_capacity * sizeof(awk::cf) + (sp->stage_in_cap + sp->stage_out_cap) * sizeof(float));   // grow-only device buffers, bytes (the context's scratch pool + this handle's staging)
+        case 6: return (int64_t)(sp->ctx->pool_capacity * sizeof(awk::cf) + (sp->stage_in_cap + sp->stage_out_cap) * sizeof(float) + sp->pcm_in_cap + sp->pcm_out_cap);   // grow-only device buffers, bytes (the context's scratch pool + this handle's staging)
         case 10: return sp->reserve_tables_us;    // last aw_spatializer_reserve: float64 table build on host threads, microseconds
         case 11: return sp->reserve_upload_us;    //   table upload (hipMalloc + hipMemcpy)
         case 12: return sp->reserve_scratch_us;   //   scratch pool growth (hipMalloc)
@@ -1431,9 +1436,11 @@ aw_status aw_spatializer_process(aw_spatializer *sp, const float *in, float *out
  * (aw_host_alloc_pinned, hipHostMalloc, hipHostRegister) are read and written by the DMA engines directly; pageable ones are bounced
  * through page-locked chunks by the context's copy threads (below).  aw_spatializer_reserve_host() sizes the device-side chunk buffers
  * and the bounce chunks ahead of time; without it they grow on the first call. */
-static int64_t host_chunk_streams(const aw_spatializer *sp, int64_t frames) {
+// in_bytes: bytes per input sample (4 for float32; aw_spatializer_process_host_pcm: 2 / 3 / 4).  AW_HOST_CHUNK_MB counts input bytes as
+// they cross PCIe, so a 16-bit batch moves twice the streams per chunk of a float32 one.
+static int64_t host_chunk_streams(const aw_spatializer *sp, int64_t frames, size_t in_bytes = sizeof(float)) {
     const size_t chunk_bytes = (size_t)sp->ctx->cfg.host_chunk_mb << 20;        // input bytes per staged chunk (LaunchCfg: read once per context)
-    const size_t per_stream = (size_t)frames * sp->n_channels * sizeof(float);
+    const size_t per_stream = (size_t)frames * sp->n_channels * in_bytes;
     if (sp->n_streams < 4 || per_stream * sp->n_streams < 2 * chunk_bytes) return 0;           // small batches: one piece, serial (plug-in shaped calls)
     int64_t cs = (int64_t)std::max<size_t>(1, chunk_bytes / per_stream);
     cs = std::max<int64_t>(cs, 2);
@@ -1468,64 +1475,153 @@ static aw_status host_pipeline_objects(aw_context *c) {
     return AW_OK;
 }
 
-static aw_status sp_grow_pinned(aw_spatializer *sp, float **buf, size_t *cap, size_t need);
+static aw_status sp_grow_bytes(aw_spatializer *sp, unsigned char **buf, size_t *cap, size_t need) {
+    if (*cap >= need) return AW_OK;
+    if (*buf) AW_HIP_TRY(hipFree(*buf));
+    *buf = nullptr; *cap = 0;
+    AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(buf), need));
+    sp->ctx->device_allocs += 1;
+    *cap = need;
+    return AW_OK;
+}
 
-// bounce: also the page-locked chunks that pageable caller buffers go through (aw_spatializer_reserve_host makes them; a call on pageable
-// memory that was not reserved for makes them on its first use)
-static aw_status host_stage_buffers(aw_spatializer *sp, int64_t frames, int64_t cs, bool bounce_in = false, bool bounce_out = false) {
+static aw_status sp_grow_pinned_bytes(aw_spatializer *sp, unsigned char **buf, size_t *cap, size_t need) {
+    if (*cap >= need) return AW_OK;
+    if (*buf) AW_HIP_TRY(hipHostFree(*buf));
+    *buf = nullptr; *cap = 0;
+    AW_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(buf), need, hipHostMallocDefault));
+    sp->ctx->device_allocs += 1;
+    *cap = need;
+    return AW_OK;
+}
+
+// the clipped-sample counter of the host entry (made once, with the first integer output)
+static aw_status sp_clip_counter(aw_spatializer *sp) {
+    if (sp->d_clip) return AW_OK;
+    AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sp->d_clip), sizeof(unsigned long long)));
+    sp->ctx->device_allocs += 1;
+    return AW_OK;
+}
+
+// float32 staging of every entry that stages (two chunks of streams in flight each way, or the whole batch); host: also the device PCM
+// slots of integer formats and the integer output's clip counter; bounce: the page-locked chunks that pageable caller buffers go through
+// (aw_spatializer_reserve_host / _reserve_pcm make them; a call on pageable memory that was not reserved for makes them on its first use)
+static aw_status host_stage_buffers(aw_spatializer *sp, int64_t frames, int64_t cs, bool bounce_in = false, bool bounce_out = false,
+                                    int in_fmt = AW_SAMPLE_F32, int out_fmt = AW_SAMPLE_F32, bool host = true) {
     const size_t streams = cs > 0 ? 2 * (size_t)cs : (size_t)sp->n_streams;           // two chunks in flight each way, or the whole batch
-    aw_status st = sp_grow(sp, &sp->d_stage_in, &sp->stage_in_cap, streams * frames * sp->n_channels);
-    if (st == AW_OK) st = sp_grow(sp, &sp->d_stage_out, &sp->stage_out_cap, streams * frames * 2);
-    if (st == AW_OK && cs > 0 && bounce_in) st = sp_grow_pinned(sp, &sp->h_bounce_in, &sp->bounce_in_cap, streams * frames * sp->n_channels);
-    if (st == AW_OK && cs > 0 && bounce_out) st = sp_grow_pinned(sp, &sp->h_bounce_out, &sp->bounce_out_cap, streams * frames * 2);
+    const size_t in_n = streams * frames * sp->n_channels, out_n = streams * frames * 2;   // elements
+    const size_t in_b = (size_t)awp::format_bytes(in_fmt), out_b = (size_t)awp::format_bytes(out_fmt);
+    aw_status st = sp_grow(sp, &sp->d_stage_in, &sp->stage_in_cap, in_n);
+    if (st == AW_OK) st = sp_grow(sp, &sp->d_stage_out, &sp->stage_out_cap, out_n);
+    if (st == AW_OK && host && in_fmt != AW_SAMPLE_F32) st = sp_grow_bytes(sp, &sp->d_pcm_in, &sp->pcm_in_cap, in_n * in_b);
+    if (st == AW_OK && host && out_fmt != AW_SAMPLE_F32) st = sp_grow_bytes(sp, &sp->d_pcm_out, &sp->pcm_out_cap, out_n * out_b);
+    if (st == AW_OK && host && out_fmt != AW_SAMPLE_F32) st = sp_clip_counter(sp);
+    if (st == AW_OK && host && cs > 0 && bounce_in) st = sp_grow_pinned_bytes(sp, &sp->h_bounce_in, &sp->bounce_in_cap, in_n * in_b);
+    if (st == AW_OK && host && cs > 0 && bounce_out) st = sp_grow_pinned_bytes(sp, &sp->h_bounce_out, &sp->bounce_out_cap, out_n * out_b);
+    return st;
+}
+
+static bool pcm_format_ok(aw_sample_format f) { return awp::format_bytes(f) > 0; }
+
+// the chunking of a staged call: what the formats ask for, or — inside what a reserve sized — the chunking its buffers were sized for
+// (never a reallocation on this path)
+static int64_t staged_chunk_streams(const aw_spatializer *sp, int64_t frames, size_t in_bytes) {
+    int64_t cs = host_chunk_streams(sp, frames, in_bytes);
+    if (frames <= sp->host_reserved_frames) cs = sp->host_chunk_reserved > 0 ? (cs > 0 ? std::min(cs, sp->host_chunk_reserved) : sp->host_chunk_reserved) : 0;
+    return cs;
+}
+
+static aw_status reserve_staged(aw_spatializer *sp, int64_t max_frames, aw_sample_format in_fmt, aw_sample_format out_fmt) {
+    aw_status st = aw_spatializer_reserve(sp, max_frames);
+    if (st != AW_OK) return st;
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    const int64_t cs = host_chunk_streams(sp, max_frames, (size_t)awp::format_bytes(in_fmt));
+    if (cs > 0) { st = host_pipeline_objects(sp->ctx); if (st != AW_OK) return st; }
+    st = host_stage_buffers(sp, max_frames, cs, /*bounce_in=*/true, /*bounce_out=*/true, in_fmt, out_fmt);
+    if (st == AW_OK) { sp->host_chunk_streams = cs; sp->host_chunk_reserved = cs; sp->host_reserved_frames = std::max(sp->host_reserved_frames, max_frames); }
     return st;
 }
 
 aw_status aw_spatializer_reserve_host(aw_spatializer *sp, int64_t max_frames) try {
-    aw_status st = aw_spatializer_reserve(sp, max_frames);
-    if (st != AW_OK) return st;
-    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
-    const int64_t cs = host_chunk_streams(sp, max_frames);
-    if (cs > 0) { st = host_pipeline_objects(sp->ctx); if (st != AW_OK) return st; }
-    st = host_stage_buffers(sp, max_frames, cs, /*bounce_in=*/true, /*bounce_out=*/true);
-    if (st == AW_OK) { sp->host_chunk_streams = cs; sp->host_chunk_reserved = cs; sp->host_reserved_frames = std::max(sp->host_reserved_frames, max_frames); }
-    return st;
+    return reserve_staged(sp, max_frames, AW_SAMPLE_F32, AW_SAMPLE_F32);
 } AW_NOEXCEPT_TAIL
 
-aw_status aw_spatializer_process_host(aw_spatializer *sp, const float *in, float *out, int64_t frames) try {
-    if (!sp || !in || !out) return fail(AW_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (frames <= 0) return frames == 0 ? AW_OK : fail(AW_ERR_INVALID_ARGUMENT, "frames must be >= 0");
-    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+aw_status aw_spatializer_reserve_pcm(aw_spatializer *sp, int64_t max_frames, aw_sample_format in_format, aw_sample_format out_format) try {
+    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    if (!pcm_format_ok(in_format) || !pcm_format_ok(out_format)) return fail(AW_ERR_INVALID_ARGUMENT, "unknown sample format");
+    return reserve_staged(sp, max_frames, in_format, out_format);
+} AW_NOEXCEPT_TAIL
+
+int32_t aw_sample_format_bytes(aw_sample_format f) { return awp::format_bytes(f); }
+
+// decode n samples of in_fmt at src into floats at dst / encode n floats into out_fmt, on the context's stream (profiled as stages)
+static aw_status pcm_decode(aw_spatializer *sp, int in_fmt, const void *src, float *dst, int64_t n) {
+    SpStageTimer tm(sp);
+    if (sp->profiling) tm.begin();
+    AW_HIP_TRY(awk::launch_pcm_decode(in_fmt, src, dst, n, sp->ctx->stream));
+    if (sp->profiling) tm.end("aw_pcm_decode_kernel");
+    return AW_OK;
+}
+static aw_status pcm_encode(aw_spatializer *sp, int out_fmt, const float *src, void *dst, int64_t n, unsigned long long *clipped) {
+    SpStageTimer tm(sp);
+    if (sp->profiling) tm.begin();
+    AW_HIP_TRY(awk::launch_pcm_encode(out_fmt, src, dst, n, clipped, sp->ctx->stream));
+    if (sp->profiling) tm.end("aw_pcm_encode_kernel");
+    return AW_OK;
+}
+
+// The host entry for every pair of sample formats.  float32 / float32 (aw_spatializer_process_host) moves the bytes, chunks and launches
+// it always has: the device PCM slots of float32 ARE the float staging, and neither conversion kernel runs.  Otherwise each chunk goes
+// H2D into its PCM slot -> decode into the float staging -> kernels -> encode into the PCM out slot -> D2H, the conversions on the
+// context's stream between the events that already order the slots (ev_run[slot] covers the PCM slots too).
+static aw_status host_process(aw_spatializer *sp, const void *in_v, int in_fmt, void *out_v, int out_fmt, int64_t frames, uint64_t *clipped) {
     aw_context *c = sp->ctx;
-    std::lock_guard<std::mutex> lk(c->launch_mu);
-    const size_t in_ps = (size_t)frames * sp->n_channels, out_ps = (size_t)frames * 2;          // floats per stream
+    const unsigned char *in = static_cast<const unsigned char *>(in_v);
+    unsigned char *out = static_cast<unsigned char *>(out_v);
+    const bool dec = in_fmt != AW_SAMPLE_F32, enc = out_fmt != AW_SAMPLE_F32;
+    const size_t in_b = (size_t)awp::format_bytes(in_fmt), out_b = (size_t)awp::format_bytes(out_fmt);
+    const size_t in_ps = (size_t)frames * sp->n_channels, out_ps = (size_t)frames * 2;          // samples per stream
+    const size_t in_psb = in_ps * in_b, out_psb = out_ps * out_b;                                // bytes per stream
     if (sp_zero_copy(sp, frames)) {      // one stream, a callback's worth of frames: the kernels read and write page-locked host memory themselves
-        std::memcpy(sp->h_pin_in, in, in_ps * sizeof(float));
+        if (dec) for (size_t i = 0; i < in_ps; ++i) sp->h_pin_in[i] = awp::decode_at(in_fmt, in + i * in_b);     // (the CPU converts on the way)
+        else std::memcpy(sp->h_pin_in, in, in_psb);
         const LwCallPlan lw0 = sp_begin_call(sp, frames);
         aw_status st0 = sp_run_streams(sp, lw0, 0, 1, sp->h_pin_in, sp->h_pin_out, frames);
         if (st0 != AW_OK) return st0;
         sp->hist_cur ^= 1;
         AW_HIP_TRY(hipStreamSynchronize(c->stream));
-        std::memcpy(out, sp->h_pin_out, out_ps * sizeof(float));
+        if (enc) {
+            uint64_t n_clip = 0;
+            for (size_t i = 0; i < out_ps; ++i) { unsigned k = 0; awp::encode_at(out_fmt, sp->h_pin_out[i], out + i * out_b, &k); n_clip += k; }
+            if (clipped) *clipped = n_clip;
+        } else {
+            std::memcpy(out, sp->h_pin_out, out_psb);
+        }
         sp->host_chunk_streams = 0;
         return AW_OK;
     }
-    int64_t cs = host_chunk_streams(sp, frames);
-    // a reserved spatializer keeps the chunking its buffers were sized for (never a reallocation on this path)
-    if (frames <= sp->host_reserved_frames) cs = sp->host_chunk_reserved > 0 ? (cs > 0 ? std::min(cs, sp->host_chunk_reserved) : sp->host_chunk_reserved) : 0;
+    const int64_t cs = staged_chunk_streams(sp, frames, in_b);
     const bool page_in = cs > 0 && !host_ptr_is_pinned(in), page_out = cs > 0 && !host_ptr_is_pinned(out);
-    aw_status st = host_stage_buffers(sp, frames, cs, page_in, page_out);
+    aw_status st = host_stage_buffers(sp, frames, cs, page_in, page_out, in_fmt, out_fmt);
     if (st == AW_OK && cs > 0) st = host_pipeline_objects(c);
     if (st != AW_OK) return st;
     sp->host_chunk_streams = cs;
+    unsigned char *pcm_in = dec ? sp->d_pcm_in : reinterpret_cast<unsigned char *>(sp->d_stage_in);
+    unsigned char *pcm_out = enc ? sp->d_pcm_out : reinterpret_cast<unsigned char *>(sp->d_stage_out);
+    if (enc) AW_HIP_TRY(hipMemsetAsync(sp->d_clip, 0, sizeof(unsigned long long), c->stream));
+    uint64_t n_clip = 0;
     const LwCallPlan lw = sp_begin_call(sp, frames);
     if (cs == 0) {                       // one piece: H2D -> kernels -> D2H on the context's stream
-        AW_HIP_TRY(hipMemcpyAsync(sp->d_stage_in, in, in_ps * sp->n_streams * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        AW_HIP_TRY(hipMemcpyAsync(pcm_in, in, in_psb * sp->n_streams, hipMemcpyHostToDevice, c->stream));
+        if (dec && (st = pcm_decode(sp, in_fmt, pcm_in, sp->d_stage_in, (int64_t)(in_ps * sp->n_streams))) != AW_OK) return st;
         st = sp_run_streams(sp, lw, 0, sp->n_streams, sp->d_stage_in, sp->d_stage_out, frames);
         if (st != AW_OK) return st;
         sp->hist_cur ^= 1;
-        AW_HIP_TRY(hipMemcpyAsync(out, sp->d_stage_out, out_ps * sp->n_streams * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        if (enc && (st = pcm_encode(sp, out_fmt, sp->d_stage_out, pcm_out, (int64_t)(out_ps * sp->n_streams), sp->d_clip)) != AW_OK) return st;
+        AW_HIP_TRY(hipMemcpyAsync(out, pcm_out, out_psb * sp->n_streams, hipMemcpyDeviceToHost, c->stream));
+        if (enc) AW_HIP_TRY(hipMemcpyAsync(&n_clip, sp->d_clip, sizeof(n_clip), hipMemcpyDeviceToHost, c->stream));
         AW_HIP_TRY(hipStreamSynchronize(c->stream));
+        if (clipped) *clipped = n_clip;
         return AW_OK;
     }
     // whatever the context's stream still holds (an earlier device-buffer call of this spatializer) comes first
@@ -1543,46 +1639,108 @@ aw_status aw_spatializer_process_host(aw_spatializer *sp, const float *in, float
         if (!page_out || prev_s0 < 0 || he != hipSuccess) return;
         he = hipEventSynchronize(c->ev_d2h[slot_prev]);
         if (he != hipSuccess) return;
-        float *d = out + (size_t)prev_s0 * out_ps; const float *b = sp->h_bounce_out + (size_t)slot_prev * cs * out_ps;
-        const size_t n = (size_t)prev_ns * out_ps * sizeof(float);
+        unsigned char *d = out + (size_t)prev_s0 * out_psb; const unsigned char *b = sp->h_bounce_out + (size_t)slot_prev * cs * out_psb;
+        const size_t n = (size_t)prev_ns * out_psb;
         if (c->cfg.host_out_async) c->copy_pool_out->start(d, b, n);
         else c->copy_pool->copy(d, b, n);            // AW_HOST_OUT_ASYNC=0 (A/B): round 5's form, on the driver thread
     };
     for (int64_t s0 = 0; s0 < sp->n_streams && he == hipSuccess; s0 += cs, ++k) {
         const int ns = (int)std::min<int64_t>(cs, sp->n_streams - s0), slot = k & 1;
-        float *d_in = sp->d_stage_in + (size_t)slot * cs * in_ps, *d_out = sp->d_stage_out + (size_t)slot * cs * out_ps;
-        const float *src = in + (size_t)s0 * in_ps;
+        unsigned char *d_in = pcm_in + (size_t)slot * cs * in_psb, *d_out = pcm_out + (size_t)slot * cs * out_psb;
+        float *f_in = sp->d_stage_in + (size_t)slot * cs * in_ps, *f_out = sp->d_stage_out + (size_t)slot * cs * out_ps;   // (float32: d_in / d_out)
+        const unsigned char *src = in + (size_t)s0 * in_psb;
         if (page_in) {
-            float *b = sp->h_bounce_in + (size_t)slot * cs * in_ps;
+            unsigned char *b = sp->h_bounce_in + (size_t)slot * cs * in_psb;
             if (k >= 2) he = hipEventSynchronize(c->ev_h2d[slot]);                              // chunk k-2's H2D has read this bounce slot
             if (he != hipSuccess) break;
-            c->copy_pool->copy(b, src, (size_t)ns * in_ps * sizeof(float));
+            c->copy_pool->copy(b, src, (size_t)ns * in_psb);
             src = b;
         }
         if (k >= 2) he = hipStreamWaitEvent(c->s_h2d, c->ev_run[slot], 0);                      // chunk k-2's kernels have read this device slot
-        if (he == hipSuccess) he = hipMemcpyAsync(d_in, src, (size_t)ns * in_ps * sizeof(float), hipMemcpyHostToDevice, c->s_h2d);
+        if (he == hipSuccess) he = hipMemcpyAsync(d_in, src, (size_t)ns * in_psb, hipMemcpyHostToDevice, c->s_h2d);
         if (he == hipSuccess) he = hipEventRecord(c->ev_h2d[slot], c->s_h2d);
         if (he == hipSuccess) he = hipStreamWaitEvent(c->stream, c->ev_h2d[slot], 0);
         if (he == hipSuccess && k >= 2) he = hipStreamWaitEvent(c->stream, c->ev_d2h[slot], 0); // chunk k-2's output has left this device slot
         if (he != hipSuccess) break;
-        st = sp_run_streams(sp, lw, (int)s0, ns, d_in, d_out, frames);
+        if (dec) st = pcm_decode(sp, in_fmt, d_in, f_in, (int64_t)ns * in_ps);
+        if (st == AW_OK) st = sp_run_streams(sp, lw, (int)s0, ns, f_in, f_out, frames);
+        if (st == AW_OK && enc) st = pcm_encode(sp, out_fmt, f_out, d_out, (int64_t)ns * out_ps, sp->d_clip);
         if (st != AW_OK) break;
         he = hipEventRecord(c->ev_run[slot], c->stream);
         if (he == hipSuccess) he = hipStreamWaitEvent(c->s_d2h, c->ev_run[slot], 0);
         if (page_out) c->copy_pool_out->wait();          // chunk k-2's copy-out has left this bounce slot (it had a whole chunk's time)
-        float *dst = page_out ? sp->h_bounce_out + (size_t)slot * cs * out_ps : out + (size_t)s0 * out_ps;
-        if (he == hipSuccess) he = hipMemcpyAsync(dst, d_out, (size_t)ns * out_ps * sizeof(float), hipMemcpyDeviceToHost, c->s_d2h);
+        unsigned char *dst = page_out ? sp->h_bounce_out + (size_t)slot * cs * out_psb : out + (size_t)s0 * out_psb;
+        if (he == hipSuccess) he = hipMemcpyAsync(dst, d_out, (size_t)ns * out_psb, hipMemcpyDeviceToHost, c->s_d2h);
         if (he == hipSuccess) he = hipEventRecord(c->ev_d2h[slot], c->s_d2h);
         drain_prev(slot ^ 1);
         prev_s0 = s0; prev_ns = ns;
     }
+    if (enc && st == AW_OK && he == hipSuccess) he = hipMemcpyAsync(&n_clip, sp->d_clip, sizeof(n_clip), hipMemcpyDeviceToHost, c->stream);
     const hipError_t e1 = hipStreamSynchronize(c->s_h2d), e2 = hipStreamSynchronize(c->stream), e3 = hipStreamSynchronize(c->s_d2h);
-    if (page_out && (st != AW_OK || he != hipSuccess)) c->copy_pool_out->wait();       // no copy thread outlives the call
+    if (page_out) c->copy_pool_out->wait();               // no copy thread outlives the call, whatever returns below
     if (st != AW_OK) return st;          // (a failed chunk: the streams are drained, the history has not been flipped)
     AW_HIP_TRY(he); AW_HIP_TRY(e1); AW_HIP_TRY(e2); AW_HIP_TRY(e3);
     drain_prev((k - 1) & 1);             // the last chunk's output
     if (page_out) c->copy_pool_out->wait();
     AW_HIP_TRY(he);
+    sp->hist_cur ^= 1;
+    if (clipped) *clipped = n_clip;
+    return AW_OK;
+}
+
+aw_status aw_spatializer_process_host(aw_spatializer *sp, const float *in, float *out, int64_t frames) try {
+    if (!sp || !in || !out) return fail(AW_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (frames <= 0) return frames == 0 ? AW_OK : fail(AW_ERR_INVALID_ARGUMENT, "frames must be >= 0");
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    return host_process(sp, in, AW_SAMPLE_F32, out, AW_SAMPLE_F32, frames, nullptr);
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_spatializer_process_host_pcm(aw_spatializer *sp, const void *in, aw_sample_format in_format, void *out,
+                                          aw_sample_format out_format, int64_t frames, uint64_t *clipped) try {
+    if (!sp || !in || !out) return fail(AW_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!pcm_format_ok(in_format) || !pcm_format_ok(out_format)) return fail(AW_ERR_INVALID_ARGUMENT, "unknown sample format");
+    if (clipped) *clipped = 0;
+    if (frames <= 0) return frames == 0 ? AW_OK : fail(AW_ERR_INVALID_ARGUMENT, "frames must be >= 0");
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    return host_process(sp, in, in_format, out, out_format, frames, clipped);
+} AW_NOEXCEPT_TAIL
+
+// Device buffers in any pair of formats: the call's streams go in chunks (the host entry's chunking, memory bounded by the chunk) through
+// the float staging on the context's stream — decode -> kernels -> encode straight into the caller's buffer.  One kernel choice for the
+// whole call (sp_begin_call once; the overlap-add tile decides on the call's block count), so the chunks give the bits an unchunked run
+// gives.  float32 / float32 is aw_spatializer_process itself.
+aw_status aw_spatializer_process_pcm(aw_spatializer *sp, const void *in_v, aw_sample_format in_fmt, void *out_v, aw_sample_format out_fmt,
+                                     int64_t frames, uint64_t *clipped_device) try {
+    if (!sp || !in_v || !out_v) return fail(AW_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!pcm_format_ok(in_fmt) || !pcm_format_ok(out_fmt)) return fail(AW_ERR_INVALID_ARGUMENT, "unknown sample format");
+    if (in_fmt == AW_SAMPLE_F32 && out_fmt == AW_SAMPLE_F32)
+        return aw_spatializer_process(sp, static_cast<const float *>(in_v), static_cast<float *>(out_v), frames);
+    if (frames <= 0) return frames == 0 ? AW_OK : fail(AW_ERR_INVALID_ARGUMENT, "frames must be >= 0");
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    const unsigned char *in = static_cast<const unsigned char *>(in_v);
+    unsigned char *out = static_cast<unsigned char *>(out_v);
+    const bool dec = in_fmt != AW_SAMPLE_F32, enc = out_fmt != AW_SAMPLE_F32;
+    const size_t in_b = (size_t)awp::format_bytes(in_fmt), out_b = (size_t)awp::format_bytes(out_fmt);
+    const size_t in_ps = (size_t)frames * sp->n_channels, out_ps = (size_t)frames * 2;
+    int64_t cs = staged_chunk_streams(sp, frames, in_b);
+    aw_status st = host_stage_buffers(sp, frames, cs, false, false, in_fmt, out_fmt, /*host=*/false);
+    if (st != AW_OK) return st;
+    if (cs == 0) cs = sp->n_streams;
+    unsigned long long *clip = reinterpret_cast<unsigned long long *>(clipped_device);
+    const LwCallPlan lw = sp_begin_call(sp, frames);
+    for (int64_t s0 = 0; s0 < sp->n_streams; s0 += cs) {
+        const int ns = (int)std::min<int64_t>(cs, sp->n_streams - s0);
+        const unsigned char *src = in + (size_t)s0 * in_ps * in_b;
+        unsigned char *dst = out + (size_t)s0 * out_ps * out_b;
+        const float *f_in = dec ? sp->d_stage_in : reinterpret_cast<const float *>(src);
+        float *f_out = enc ? sp->d_stage_out : reinterpret_cast<float *>(dst);
+        if (dec && (st = pcm_decode(sp, in_fmt, src, sp->d_stage_in, (int64_t)ns * in_ps)) != AW_OK) return st;
+        if ((st = sp_run_streams(sp, lw, (int)s0, ns, f_in, f_out, frames)) != AW_OK) return st;
+        if (enc && (st = pcm_encode(sp, out_fmt, f_out, dst, (int64_t)ns * out_ps, clip)) != AW_OK) return st;
+    }
     sp->hist_cur ^= 1;
     return AW_OK;
 } AW_NOEXCEPT_TAIL

@@ -110,8 +110,13 @@ struct aw_spatializer {
     float *h_pin_in = nullptr, *h_pin_out = nullptr;
     size_t pin_in_cap = 0, pin_out_cap = 0;       // floats
     // multi-stream host entry on PAGEABLE caller buffers: page-locked bounce chunks (two each way), filled / drained by the context's copy threads
-    float *h_bounce_in = nullptr, *h_bounce_out = nullptr;
-    size_t bounce_in_cap = 0, bounce_out_cap = 0; // floats (both slots)
+    unsigned char *h_bounce_in = nullptr, *h_bounce_out = nullptr;
+    size_t bounce_in_cap = 0, bounce_out_cap = 0; // bytes (both slots)
+    // integer PCM entries (aw_spatializer_process_pcm / _process_host_pcm): the host entry's device PCM slots (two chunks each way; the
+    // float32 formats use d_stage_in / d_stage_out themselves) and the device counter of its clipped samples
+    unsigned char *d_pcm_in = nullptr, *d_pcm_out = nullptr;
+    size_t pcm_in_cap = 0, pcm_out_cap = 0;       // bytes
+    unsigned long long *d_clip = nullptr;
     int64_t host_chunk_streams = 0;               // streams per staged chunk of the last host call (0: the whole batch in one piece, serial)
     int64_t host_chunk_reserved = 0, host_reserved_frames = 0;   // aw_spatializer_reserve_host: the chunking its buffers were sized for, and up to which call length
     // what the last aw_spatializer_reserve spent where (microseconds): float64 table build on host threads, table upload (hipMalloc +

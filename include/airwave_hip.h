@@ -147,6 +147,38 @@ AW_API aw_status aw_spatializer_process_host(aw_spatializer *sp, const float *in
  * sizes it — for the whole batch — although the host entry only ever runs one staged chunk of streams at a time; AW_SPEC_SCRATCH_MB
  * bounds it for hosts that never use the device entry.) */
 AW_API aw_status aw_spatializer_reserve_host(aw_spatializer *sp, int64_t max_frames);
+/* ---- integer PCM sample formats ---------------------------------------------------------------
+ * The batch entries in any pair of sample formats: an offline host that holds 16- or 24-bit PCM hands it over as it is, and half
+ * the bytes cross PCIe.  Layouts are those of aw_spatializer_process: input [stream][frames][n_in_channels], output
+ * [stream][frames][2], elements of the given format; mixed pairs (s16 in, f32 out, ...) are allowed.  F32 / F32 through these
+ * entries is aw_spatializer_process / aw_spatializer_process_host, bit for bit.
+ *  - decode is aw_wav_load's rule: s16 (float)s / 32768, s24 (float)((double)s / 8388608), s32 (float)((double)s / 2147483648).
+ *    Each scale is a power of two, so every PCM input is an exact float32 input to the same kernels.
+ *  - encode is the inverse scale, rounded to nearest with ties to even, then saturated to the integer range (s32 computed in
+ *    double); NaN encodes to 0.  A sample is clipped when the rounded value lies outside the integer range, or when it is NaN
+ *    or +-inf.  No dither.
+ *  - a NULL handle or buffer, or an unknown format, returns AW_ERR_INVALID_ARGUMENT before any HIP call.  On a failed host call
+ *    the output contents are unspecified, as for aw_spatializer_process_host. */
+typedef int32_t aw_sample_format;
+enum {
+    AW_SAMPLE_F32 = 0,   /* float32 */
+    AW_SAMPLE_S16 = 1,   /* int16 */
+    AW_SAMPLE_S24 = 2,   /* packed 3-byte little-endian two's complement, as in WAV */
+    AW_SAMPLE_S32 = 3    /* int32 */
+};
+AW_API int32_t aw_sample_format_bytes(aw_sample_format f);   /* 4, 2, 3, 4; 0 for an unknown format */
+/* DEVICE buffers (any byte alignment), asynchronous on the context stream.  The call's streams go through the host entry's
+ * float32 staging in chunks of streams (AW_HOST_CHUNK_MB of input bytes), so memory is bounded by a chunk, not the batch.
+ * clipped_device: NULL, or a device uint64 that the call atomically adds its clipped-sample count to. */
+AW_API aw_status aw_spatializer_process_pcm(aw_spatializer *sp, const void *in_device, aw_sample_format in_format,
+                                            void *out_device, aw_sample_format out_format, int64_t frames, uint64_t *clipped_device);
+/* HOST buffers, synchronous: the chunked PCIe pipeline of aw_spatializer_process_host, chunked by PCM input bytes; each chunk is
+ * decoded and encoded on the device.  clipped: NULL, or receives the call's clipped-sample count. */
+AW_API aw_status aw_spatializer_process_host_pcm(aw_spatializer *sp, const void *in_host, aw_sample_format in_format,
+                                                 void *out_host, aw_sample_format out_format, int64_t frames, uint64_t *clipped);
+/* aw_spatializer_reserve_host for these formats: afterwards neither PCM entry allocates for calls of up to max_frames frames. */
+AW_API aw_status aw_spatializer_reserve_pcm(aw_spatializer *sp, int64_t max_frames, aw_sample_format in_format,
+                                            aw_sample_format out_format);
 /* StereoAudioProcessing.process shape (AudioPipeline.swift:3-11) for a 1-stream, 2-channel
  * spatializer: planar HOST buffers, input_right may be NULL (mono duplication). Zero latency. */
 AW_API aw_status aw_spatializer_process_planar(aw_spatializer *sp, const float *input_left, const float *input_right,

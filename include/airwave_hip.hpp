@@ -94,6 +94,19 @@ class Spatializer {
     }
     void reserve(int64_t maxFrames) { check(aw_spatializer_reserve(h_, maxFrames)); }
     void reserveHost(int64_t maxFrames) { check(aw_spatializer_reserve_host(h_, maxFrames)); }     // + the host entry's device-side staging
+    // integer PCM (aw_sample_format): device / host entries in any pair of formats; the host entry returns the clipped-sample count
+    void processPcmDevice(const void *in, aw_sample_format inFormat, void *out, aw_sample_format outFormat, int64_t frames,
+                          uint64_t *clippedDevice = nullptr) {
+        check(aw_spatializer_process_pcm(h_, in, inFormat, out, outFormat, frames, clippedDevice));
+    }
+    uint64_t processPcmHost(const void *in, aw_sample_format inFormat, void *out, aw_sample_format outFormat, int64_t frames) {
+        uint64_t clipped = 0;
+        check(aw_spatializer_process_host_pcm(h_, in, inFormat, out, outFormat, frames, &clipped));
+        return clipped;
+    }
+    void reservePcm(int64_t maxFrames, aw_sample_format inFormat, aw_sample_format outFormat) {
+        check(aw_spatializer_reserve_pcm(h_, maxFrames, inFormat, outFormat));
+    }
     int64_t info(int32_t what) const { return aw_spatializer_info(h_, what); }
     void reset() { check(aw_spatializer_reset(h_)); }
     aw_spatializer *get() const { return h_; }

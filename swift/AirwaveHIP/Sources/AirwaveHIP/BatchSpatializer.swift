@@ -76,6 +76,17 @@ public final class BatchSpatializer {
         guard st == AW_OK else { throw BatchSpatializer.error(st) }
     }
 
+    /// Host buffers of 16-bit PCM (`aw_spatializer_process_host_pcm`, s16 in / s16 out): the same chunked pipeline at half the
+    /// bytes; decoded and encoded on the device (round half to even, saturated).  Returns the call's clipped-sample count.
+    @discardableResult
+    public func process(hostInput: UnsafePointer<Int16>, hostOutput: UnsafeMutablePointer<Int16>, frames: Int64) throws -> UInt64 {
+        var clipped: UInt64 = 0
+        let st = aw_spatializer_process_host_pcm(handle, hostInput, aw_sample_format(AW_SAMPLE_S16), hostOutput,
+                                                 aw_sample_format(AW_SAMPLE_S16), frames, &clipped)
+        guard st == AW_OK else { throw BatchSpatializer.error(st) }
+        return clipped
+    }
+
     /// `reserve` plus the host entry's device-side staging: `process(hostInput:…)` never allocates afterwards either.
     public func reserveHost(maxFrames: Int64) throws {
         let st = aw_spatializer_reserve_host(handle, maxFrames)
