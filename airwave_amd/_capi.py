@@ -54,6 +54,7 @@ SIGNATURES = {
     "aw_spatializer_process_pcm": (_I32, [_V, _V, _I32, _V, _I32, _I64, _V]),
     "aw_spatializer_process_host_pcm": (_I32, [_V, _V, _I32, _V, _I32, _I64, ctypes.POINTER(ctypes.c_uint64)]),
     "aw_spatializer_reserve_pcm": (_I32, [_V, _I64, _I32, _I32]),
+    "aw_spatializer_set_dither": (_I32, [_V, _I32, _U64, _U64]),
     "aw_spatializer_reset": (_I32, [_V]),
     "aw_spatializer_stream_count": (_I32, [_V]),
     "aw_spatializer_channel_count": (_I32, [_V]),

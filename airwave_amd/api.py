@@ -75,6 +75,8 @@ def _i32p(a: np.ndarray):
 # aw_sample_format (include/airwave_hip.h): sample formats of the PCM entries
 SAMPLE_FORMATS = {"f32": 0, "s16": 1, "s24": 2, "s32": 3}
 _FORMAT_DTYPE = {0: np.dtype(np.float32), 1: np.dtype(np.int16), 2: np.dtype(np.uint8), 3: np.dtype(np.int32)}
+# aw_dither (include/airwave_hip.h): dither of the s16 / s24 encode (Spatializer.set_dither)
+DITHER_MODES = {"none": 0, "tpdf": 1, "tpdf_hp": 2}
 
 
 def sample_format_bytes(fmt) -> int:
@@ -424,7 +426,8 @@ class Spatializer:
                 "sync_copies": g(14),           # blocking table uploads likewise
                 "host_chunk_streams": g(15),    # streams per staged chunk of the last host-entry call (0: one piece)
                 "overlap_add_rows": g(16),      # the last call ran the overlap-add tile on blocks of 512 x this many frames (0: it did not)
-                "overlap_add_rows_policy": g(17)}   # ... which this spatializer's calls do when they have enough blocks (0: never)
+                "overlap_add_rows_policy": g(17),   # ... which this spatializer's calls do when they have enough blocks (0: never)
+                "position_frames": g(18)}       # frames processed since creation / the last reset (the dither's frame position)
 
     def process_device(self, in_ptr: int, out_ptr: int, frames: int) -> None:
         _check(self._lib.aw_spatializer_process(self._h, ctypes.c_void_p(in_ptr), ctypes.c_void_p(out_ptr), frames))
@@ -494,6 +497,15 @@ class Spatializer:
         fi = SAMPLE_FORMATS.get(in_format, -1) if isinstance(in_format, str) else int(in_format)
         fo = SAMPLE_FORMATS.get(out_format, -1) if isinstance(out_format, str) else int(out_format)
         _check(self._lib.aw_spatializer_reserve_pcm(self._h, int(max_frames), fi, fo))
+
+    def set_dither(self, mode, seed: int = 0, first_stream: int = 0) -> None:
+        """aw_spatializer_set_dither: dither of every later s16 / s24 encode ('none', 'tpdf', 'tpdf_hp', or the aw_dither code).
+        first_stream: the global index of this handle's stream 0, so that a batch sharded over handles gets one handle's noise."""
+        if isinstance(mode, str):
+            if mode not in DITHER_MODES:
+                raise ValueError(f"unknown dither mode {mode!r} (one of {', '.join(DITHER_MODES)})")
+            mode = DITHER_MODES[mode]
+        _check(self._lib.aw_spatializer_set_dither(self._h, int(mode), int(seed), int(first_stream)))
 
     def reset(self) -> None:
         _check(self._lib.aw_spatializer_reset(self._h))

@@ -7,6 +7,7 @@
 #include "kernels.hpp"
 #include "gpu_ctx.hpp"
 #include "ols2_kernel.hpp"
+#include "pcm.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -548,13 +549,8 @@ hipError_t launch_hist_update(const float *in, const float *hist_old, float *his
     return hipGetLastError();
 }
 
-// ---- synthetic input ------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// ---- synthetic input (splitmix64: pcm.hpp, shared with the PCM encode's dither) -------------
+using awp::splitmix64;
 
 __global__ void aw_synth_fill_kernel(float *__restrict__ dst, long long per_stream, unsigned long long seed,
                                      unsigned long long first_stream) {

@@ -748,6 +748,7 @@ int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what) {
         case 15: return sp->host_chunk_streams;   // streams per staged chunk of the host entry (0: the whole batch in one piece)
         case 16: return sp->last_ola_h;           // rows H of the overlap-add blocks (512 H frames) the last call ran on; 0: it ran another tile
         case 17: return sp->ola_h;                // rows H this spatializer's long-enough calls use (0: the overlap-add tile is not used)
+        case 18: return (int64_t)sp->position;    // frames processed since create / the last reset (the dither's frame position)
         default: return -1;
     }
 }
@@ -1410,7 +1411,11 @@ static aw_status sp_run_streams(aw_spatializer *sp, const LwCallPlan &lw, int s_
     return AW_OK;
 }
 
-static LwCallPlan sp_begin_call(aw_spatializer *sp, int64_t frames) {
+// Once per call of every process entry: the call's kernel plan, and the frame position moves past the call.  *pos0 (optional) receives
+// the position of the call's first frame, which every encode of the call keys its dither on.
+static LwCallPlan sp_begin_call(aw_spatializer *sp, int64_t frames, uint64_t *pos0 = nullptr) {
+    if (pos0) *pos0 = sp->position;
+    sp->position += (uint64_t)frames;
     const LwCallPlan lw = lw_choose(sp, frames);
     sp->last_lw_R = lw.n_groups ? lw.g[0].R : 0;
     sp->last_lw_R2 = lw.n_groups > 1 ? lw.g[1].R : 0;
@@ -1562,10 +1567,22 @@ static aw_status pcm_decode(aw_spatializer *sp, int in_fmt, const void *src, flo
     if (sp->profiling) tm.end("aw_pcm_decode_kernel");
     return AW_OK;
 }
-static aw_status pcm_encode(aw_spatializer *sp, int out_fmt, const float *src, void *dst, int64_t n, unsigned long long *clipped) {
+static_assert(AW_DITHER_NONE == awp::kDitherNone && AW_DITHER_TPDF == awp::kDitherTpdf && AW_DITHER_TPDF_HP == awp::kDitherTpdfHp, "aw_dither");
+// only s16 and s24 are dithered: float32's 24-bit mantissa is coarser than an s32 LSB for nearly every sample
+static bool sp_dithers(const aw_spatializer *sp, int out_fmt) {
+    return sp->dither != AW_DITHER_NONE && (out_fmt == AW_SAMPLE_S16 || out_fmt == AW_SAMPLE_S24);
+}
+// s0: the handle's index of the first of the n / (2 frames) streams encoded; pos: the call's first frame position (sp_begin_call)
+static aw_status pcm_encode(aw_spatializer *sp, int out_fmt, const float *src, void *dst, int64_t n, unsigned long long *clipped, int64_t s0,
+                            int64_t frames, uint64_t pos) {
     SpStageTimer tm(sp);
     if (sp->profiling) tm.begin();
-    AW_HIP_TRY(awk::launch_pcm_encode(out_fmt, src, dst, n, clipped, sp->ctx->stream));
+    if (sp_dithers(sp, out_fmt)) {
+        const awk::PcmDither d{sp->dither, sp->dither_seed, sp->dither_first_stream + (uint64_t)s0, pos, frames};
+        AW_HIP_TRY(awk::launch_pcm_encode_dithered(out_fmt, d, src, dst, n, clipped, sp->ctx->stream));
+    } else {
+        AW_HIP_TRY(awk::launch_pcm_encode(out_fmt, src, dst, n, clipped, sp->ctx->stream));
+    }
     if (sp->profiling) tm.end("aw_pcm_encode_kernel");
     return AW_OK;
 }
@@ -1585,14 +1602,21 @@ static aw_status host_process(aw_spatializer *sp, const void *in_v, int in_fmt, 
     if (sp_zero_copy(sp, frames)) {      // one stream, a callback's worth of frames: the kernels read and write page-locked host memory themselves
         if (dec) for (size_t i = 0; i < in_ps; ++i) sp->h_pin_in[i] = awp::decode_at(in_fmt, in + i * in_b);     // (the CPU converts on the way)
         else std::memcpy(sp->h_pin_in, in, in_psb);
-        const LwCallPlan lw0 = sp_begin_call(sp, frames);
+        uint64_t pos0 = 0;
+        const LwCallPlan lw0 = sp_begin_call(sp, frames, &pos0);
         aw_status st0 = sp_run_streams(sp, lw0, 0, 1, sp->h_pin_in, sp->h_pin_out, frames);
         if (st0 != AW_OK) return st0;
         sp->hist_cur ^= 1;
         AW_HIP_TRY(hipStreamSynchronize(c->stream));
         if (enc) {
             uint64_t n_clip = 0;
-            for (size_t i = 0; i < out_ps; ++i) { unsigned k = 0; awp::encode_at(out_fmt, sp->h_pin_out[i], out + i * out_b, &k); n_clip += k; }
+            const int mode = sp_dithers(sp, out_fmt) ? sp->dither : awp::kDitherNone;
+            const uint64_t key = awp::dither_key(sp->dither_seed, sp->dither_first_stream);
+            for (size_t i = 0; i < out_ps; ++i) {
+                unsigned k = 0;
+                awp::encode_dithered_at(out_fmt, mode, sp->h_pin_out[i], key, pos0 + i / 2, (int)(i & 1), out + i * out_b, &k);
+                n_clip += k;
+            }
             if (clipped) *clipped = n_clip;
         } else {
             std::memcpy(out, sp->h_pin_out, out_psb);
@@ -1609,15 +1633,16 @@ static aw_status host_process(aw_spatializer *sp, const void *in_v, int in_fmt, 
     unsigned char *pcm_in = dec ? sp->d_pcm_in : reinterpret_cast<unsigned char *>(sp->d_stage_in);
     unsigned char *pcm_out = enc ? sp->d_pcm_out : reinterpret_cast<unsigned char *>(sp->d_stage_out);
     if (enc) AW_HIP_TRY(hipMemsetAsync(sp->d_clip, 0, sizeof(unsigned long long), c->stream));
-    uint64_t n_clip = 0;
-    const LwCallPlan lw = sp_begin_call(sp, frames);
+    uint64_t n_clip = 0, pos0 = 0;
+    const LwCallPlan lw = sp_begin_call(sp, frames, &pos0);
     if (cs == 0) {                       // one piece: H2D -> kernels -> D2H on the context's stream
         AW_HIP_TRY(hipMemcpyAsync(pcm_in, in, in_psb * sp->n_streams, hipMemcpyHostToDevice, c->stream));
         if (dec && (st = pcm_decode(sp, in_fmt, pcm_in, sp->d_stage_in, (int64_t)(in_ps * sp->n_streams))) != AW_OK) return st;
         st = sp_run_streams(sp, lw, 0, sp->n_streams, sp->d_stage_in, sp->d_stage_out, frames);
         if (st != AW_OK) return st;
         sp->hist_cur ^= 1;
-        if (enc && (st = pcm_encode(sp, out_fmt, sp->d_stage_out, pcm_out, (int64_t)(out_ps * sp->n_streams), sp->d_clip)) != AW_OK) return st;
+        if (enc && (st = pcm_encode(sp, out_fmt, sp->d_stage_out, pcm_out, (int64_t)(out_ps * sp->n_streams), sp->d_clip, 0, frames, pos0)) != AW_OK)
+            return st;
         AW_HIP_TRY(hipMemcpyAsync(out, pcm_out, out_psb * sp->n_streams, hipMemcpyDeviceToHost, c->stream));
         if (enc) AW_HIP_TRY(hipMemcpyAsync(&n_clip, sp->d_clip, sizeof(n_clip), hipMemcpyDeviceToHost, c->stream));
         AW_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1664,7 +1689,7 @@ static aw_status host_process(aw_spatializer *sp, const void *in_v, int in_fmt, 
         if (he != hipSuccess) break;
         if (dec) st = pcm_decode(sp, in_fmt, d_in, f_in, (int64_t)ns * in_ps);
         if (st == AW_OK) st = sp_run_streams(sp, lw, (int)s0, ns, f_in, f_out, frames);
-        if (st == AW_OK && enc) st = pcm_encode(sp, out_fmt, f_out, d_out, (int64_t)ns * out_ps, sp->d_clip);
+        if (st == AW_OK && enc) st = pcm_encode(sp, out_fmt, f_out, d_out, (int64_t)ns * out_ps, sp->d_clip, s0, frames, pos0);
         if (st != AW_OK) break;
         he = hipEventRecord(c->ev_run[slot], c->stream);
         if (he == hipSuccess) he = hipStreamWaitEvent(c->s_d2h, c->ev_run[slot], 0);
@@ -1730,7 +1755,8 @@ aw_status aw_spatializer_process_pcm(aw_spatializer *sp, const void *in_v, aw_sa
     if (st != AW_OK) return st;
     if (cs == 0) cs = sp->n_streams;
     unsigned long long *clip = reinterpret_cast<unsigned long long *>(clipped_device);
-    const LwCallPlan lw = sp_begin_call(sp, frames);
+    uint64_t pos0 = 0;
+    const LwCallPlan lw = sp_begin_call(sp, frames, &pos0);
     for (int64_t s0 = 0; s0 < sp->n_streams; s0 += cs) {
         const int ns = (int)std::min<int64_t>(cs, sp->n_streams - s0);
         const unsigned char *src = in + (size_t)s0 * in_ps * in_b;
@@ -1739,7 +1765,7 @@ aw_status aw_spatializer_process_pcm(aw_spatializer *sp, const void *in_v, aw_sa
         float *f_out = enc ? sp->d_stage_out : reinterpret_cast<float *>(dst);
         if (dec && (st = pcm_decode(sp, in_fmt, src, sp->d_stage_in, (int64_t)ns * in_ps)) != AW_OK) return st;
         if ((st = sp_run_streams(sp, lw, (int)s0, ns, f_in, f_out, frames)) != AW_OK) return st;
-        if (enc && (st = pcm_encode(sp, out_fmt, f_out, dst, (int64_t)ns * out_ps, clip)) != AW_OK) return st;
+        if (enc && (st = pcm_encode(sp, out_fmt, f_out, dst, (int64_t)ns * out_ps, clip, s0, frames, pos0)) != AW_OK) return st;
     }
     sp->hist_cur ^= 1;
     return AW_OK;
@@ -1804,10 +1830,21 @@ aw_status aw_spatializer_process_planar(aw_spatializer *sp, const float *in_l, c
 
 aw_status aw_spatializer_reset(aw_spatializer *sp) try {
     if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    sp->position = 0;
     AW_HIP_TRY(hipSetDevice(sp->ctx->device));
     const size_t n = (size_t)sp->n_streams * sp->hist_len * sp->n_channels;
     for (int i = 0; i < 2; ++i)
         AW_HIP_TRY(hipMemsetAsync(sp->d_hist[i], 0, std::max<size_t>(n, 1) * sizeof(float), sp->ctx->stream));
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+// No HIP call and no allocation: the encode kernels take the dither as launch arguments.
+aw_status aw_spatializer_set_dither(aw_spatializer *sp, aw_dither mode, uint64_t seed, uint64_t first_stream) try {
+    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    if (mode != AW_DITHER_NONE && mode != AW_DITHER_TPDF && mode != AW_DITHER_TPDF_HP) return fail(AW_ERR_INVALID_ARGUMENT, "unknown dither mode");
+    sp->dither = mode;
+    sp->dither_seed = seed;
+    sp->dither_first_stream = first_stream;
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 

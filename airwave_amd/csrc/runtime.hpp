@@ -117,6 +117,11 @@ struct aw_spatializer {
     unsigned char *d_pcm_in = nullptr, *d_pcm_out = nullptr;
     size_t pcm_in_cap = 0, pcm_out_cap = 0;       // bytes
     unsigned long long *d_clip = nullptr;
+    // dither of the s16 / s24 encode (aw_spatializer_set_dither) and the frame position that keys it: frames processed since create /
+    // reset, advanced once per call by sp_begin_call (aw_spatializer_info 18)
+    int dither = 0;                               // aw_dither
+    uint64_t dither_seed = 0, dither_first_stream = 0;
+    uint64_t position = 0;
     int64_t host_chunk_streams = 0;               // streams per staged chunk of the last host call (0: the whole batch in one piece, serial)
     int64_t host_chunk_reserved = 0, host_reserved_frames = 0;   // aw_spatializer_reserve_host: the chunking its buffers were sized for, and up to which call length
     // what the last aw_spatializer_reserve spent where (microseconds): float64 table build on host threads, table upload (hipMalloc +

@@ -156,7 +156,7 @@ AW_API aw_status aw_spatializer_reserve_host(aw_spatializer *sp, int64_t max_fra
  *    Each scale is a power of two, so every PCM input is an exact float32 input to the same kernels.
  *  - encode is the inverse scale, rounded to nearest with ties to even, then saturated to the integer range (s32 computed in
  *    double); NaN encodes to 0.  A sample is clipped when the rounded value lies outside the integer range, or when it is NaN
- *    or +-inf.  No dither.
+ *    or +-inf.  No dither by default; aw_spatializer_set_dither (below) adds TPDF dither to s16 and s24 output.
  *  - a NULL handle or buffer, or an unknown format, returns AW_ERR_INVALID_ARGUMENT before any HIP call.  On a failed host call
  *    the output contents are unspecified, as for aw_spatializer_process_host. */
 typedef int32_t aw_sample_format;
@@ -179,6 +179,31 @@ AW_API aw_status aw_spatializer_process_host_pcm(aw_spatializer *sp, const void 
 /* aw_spatializer_reserve_host for these formats: afterwards neither PCM entry allocates for calls of up to max_frames frames. */
 AW_API aw_status aw_spatializer_reserve_pcm(aw_spatializer *sp, int64_t max_frames, aw_sample_format in_format,
                                             aw_sample_format out_format);
+/* Dither of the integer encode.  Applies to every later s16 / s24 encode of this handle's PCM entries (device, host, and the
+ * single-stream path of the host entry).  s32 and f32 output are never dithered: float32's 24-bit mantissa is coarser than an
+ * s32 LSB for nearly every sample, so s32 stays the rounding above.  AW_DITHER_NONE, the default, is that rounding byte for byte.
+ *  - position p: frames processed by this handle since it was created or last passed to aw_spatializer_reset.  Every process entry
+ *    advances it (float, PCM, host, device, planar; aw_spatializer_info 18); after a failed call it is as unspecified as the state.
+ *    The noise of a sample depends only on (seed, global stream, p, ear), so splitting a call in two, or chunking a batch by streams,
+ *    changes no output bit.
+ *  - first_stream: the global index of this handle's stream 0, as in aw_synth_fill: a batch sharded over several handles gets the
+ *    noise of one handle holding every stream.
+ *  - with g = first_stream + s, K = ((seed ^ 0xD1B54A32D192ED03) + g) * 0x9E3779B97F4A7C15 (mod 2^64) and splitmix64 as in
+ *    aw_synth_fill, the dither d in LSB of ear e (0 left, 1 right) of frame p is
+ *      AW_DITHER_TPDF:    h = splitmix64(K + 2p + e), d = (float)((int32_t)(h >> 40) - (int32_t)((h >> 16) & 0xFFFFFF)) * 2^-24
+ *      AW_DITHER_TPDF_HP: r(p) = ((splitmix64(K + p) >> (e ? 16 : 40)) & 0xFFFFFF) * 2^-24, d = r(p) - r(p - 1)  (p - 1 mod 2^64):
+ *                         high-pass TPDF, stateless (r(p - 1) is recomputed from the counter)
+ *    and the sample encodes as s16 rintf(x * 32768.0f + d), s24 rintf(x * 8388608.0f + d), saturated; the NaN and clip rules are
+ *    those above (a sample that the dither pushes past full scale counts as clipped).  d lies in (-1, 1): triangular, 1/6 LSB^2.
+ *  - a NULL handle or an unknown mode returns AW_ERR_INVALID_ARGUMENT before any HIP call.  Allocates nothing.  Do not call it while
+ *    a process call on the same handle is running. */
+typedef int32_t aw_dither;
+enum {
+    AW_DITHER_NONE = 0,      /* round to nearest, ties to even (the default) */
+    AW_DITHER_TPDF = 1,      /* triangular (two uniforms), white */
+    AW_DITHER_TPDF_HP = 2    /* triangular, high-pass (difference of consecutive uniforms) */
+};
+AW_API aw_status aw_spatializer_set_dither(aw_spatializer *sp, aw_dither mode, uint64_t seed, uint64_t first_stream);
 /* StereoAudioProcessing.process shape (AudioPipeline.swift:3-11) for a 1-stream, 2-channel
  * spatializer: planar HOST buffers, input_right may be NULL (mono duplication). Zero latency. */
 AW_API aw_status aw_spatializer_process_planar(aw_spatializer *sp, const float *input_left, const float *input_right,
@@ -200,7 +225,8 @@ AW_API int32_t aw_spatializer_channel_count(const aw_spatializer *sp);
  * 8 rows of the remainder window of a call that ran as two groups of windows, 9 long-window table sets built so far,
  * 10 / 11 / 12 microseconds the last aw_spatializer_reserve spent on the float64 table build (host threads) / the table upload /
  *   growing the context's scratch pool, 13 device or page-locked allocations and 14 blocking table uploads made so far on behalf
- *   of the context's handles (a reserved process path makes neither), 15 streams per staged chunk of the last host-entry call. */
+ *   of the context's handles (a reserved process path makes neither), 15 streams per staged chunk of the last host-entry call,
+ * 18 frames processed since create / the last aw_spatializer_reset (the dither's frame position, aw_spatializer_set_dither). */
 AW_API int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what);
 /* Average device time of the dominant kernel over the launches since the last call (HIP events
  * on the context stream); used for bench.py's roofline object.  Returns launches counted. */

@@ -107,6 +107,8 @@ class Spatializer {
     void reservePcm(int64_t maxFrames, aw_sample_format inFormat, aw_sample_format outFormat) {
         check(aw_spatializer_reserve_pcm(h_, maxFrames, inFormat, outFormat));
     }
+    // TPDF dither of later s16 / s24 encodes (aw_dither); firstStream: the global index of this handle's stream 0
+    void setDither(aw_dither mode, uint64_t seed = 0, uint64_t firstStream = 0) { check(aw_spatializer_set_dither(h_, mode, seed, firstStream)); }
     int64_t info(int32_t what) const { return aw_spatializer_info(h_, what); }
     void reset() { check(aw_spatializer_reset(h_)); }
     aw_spatializer *get() const { return h_; }

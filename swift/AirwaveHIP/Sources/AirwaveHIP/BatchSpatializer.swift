@@ -87,6 +87,14 @@ public final class BatchSpatializer {
         return clipped
     }
 
+    /// TPDF dither of every later s16 / s24 encode (`aw_spatializer_set_dither`; `AW_DITHER_NONE`, the default, rounds as above).
+    /// `firstStream`: the global index of this batch's stream 0, so that a batch split over several spatializers gets one batch's noise.
+    /// Not while a `process` call on this spatializer is running.
+    public func setDither(_ mode: Int32, seed: UInt64 = 0, firstStream: UInt64 = 0) throws {
+        let st = aw_spatializer_set_dither(handle, aw_dither(mode), seed, firstStream)
+        guard st == AW_OK else { throw BatchSpatializer.error(st) }
+    }
+
     /// `reserve` plus the host entry's device-side staging: `process(hostInput:…)` never allocates afterwards either.
     public func reserveHost(maxFrames: Int64) throws {
         let st = aw_spatializer_reserve_host(handle, maxFrames)

@@ -1,8 +1,9 @@
 """Host entry in integer PCM against float32 (aw_spatializer_process_host_pcm): G stereo frames/s and bytes moved per call for f32/f32,
-s16/s16 and s24/s24, alternating (format order rotates every repetition), on page-locked and optionally pageable buffers; then one
-profiled call per format for the decode / encode kernel times (HIP events around each launch: aw_spatializer_stage_time).
+s16/s16 and s24/s24 (with --dither also s16/s16 under TPDF and high-pass TPDF dither, aw_spatializer_set_dither), alternating (the order
+rotates every repetition), on page-locked and optionally pageable buffers; then one profiled call per format for the decode / encode kernel
+times (HIP events around each launch: aw_spatializer_stage_time).
 
-    python tools/pcm_host_entry.py [--channels 8] [--taps 4320] [--streams 128] [--seconds 10] [--reps 3] [--pageable]
+    python tools/pcm_host_entry.py [--channels 8] [--taps 4320] [--streams 128] [--seconds 10] [--reps 3] [--pageable] [--dither]
 
 One JSON line per measurement and a summary line per format (min / median / max over the repetitions, and the ratio to f32/f32)."""
 import argparse
@@ -17,6 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import airwave_amd as aw  # noqa: E402
 
 FORMATS = (("f32", np.float32, 4), ("s16", np.int16, 2), ("s24", np.uint8, 3))
+DITHERED = (("s16+tpdf", "s16", "tpdf"), ("s16+tpdf_hp", "s16", "tpdf_hp"))      # (label, format, aw_dither mode)
 
 
 def fill(buf, fmt, base):
@@ -41,6 +43,7 @@ def main() -> int:
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--pageable", action="store_true", help="also time pageable numpy buffers (bounced through page-locked chunks)")
+    ap.add_argument("--dither", action="store_true", help="also time s16/s16 with TPDF and high-pass TPDF dither")
     a = ap.parse_args()
     C, S, F = a.channels, a.streams, int(round(a.seconds * 48000))
     rng = np.random.default_rng(1)
@@ -63,43 +66,47 @@ def main() -> int:
             bufs[(kind, fmt)] = (x, y)
     for fmt, _, _ in FORMATS:
         sp.reserve_pcm(F, fmt, fmt)
+    # (label, format, bytes per sample, dither mode)
+    runs = [(fmt, fmt, b, "none") for fmt, _, b in FORMATS] + ([(lab, fmt, 2, mode) for lab, fmt, mode in DITHERED] if a.dither else [])
 
-    def call(kind, fmt):
+    def call(kind, fmt, mode="none"):
         x, y = bufs[(kind, fmt)]
+        sp.set_dither(mode)
         return sp.process_host_into(x, y, in_format=fmt, out_format=fmt)
 
     for kind in kinds:                              # warm-up: pipeline objects, tables, first-touch of every buffer
-        for fmt, _, _ in FORMATS:
-            call(kind, fmt)
+        for _, fmt, _, mode in runs:
+            call(kind, fmt, mode)
     rates = {}
     for kind in kinds:
         for rep in range(a.reps):
-            order = FORMATS[rep % 3:] + FORMATS[:rep % 3]
-            for fmt, _, b in order:
+            order = runs[rep % len(runs):] + runs[:rep % len(runs)]
+            for lab, fmt, b, mode in order:
                 t = time.perf_counter()
-                call(kind, fmt)
+                call(kind, fmt, mode)
                 dt_s = time.perf_counter() - t
                 gfs = S * F / dt_s / 1e9
-                rates.setdefault((kind, fmt), []).append(gfs)
+                rates.setdefault((kind, lab), []).append(gfs)
                 moved = S * F * (C + 2) * b
-                print(json.dumps({"kind": kind, "format": f"{fmt}/{fmt}", "rep": rep, "channels": C, "taps": a.taps, "streams": S, "frames": F,
+                print(json.dumps({"kind": kind, "format": f"{lab}/{fmt}" if mode != "none" else f"{fmt}/{fmt}", "rep": rep, "channels": C, "taps": a.taps, "streams": S, "frames": F,
                                   "seconds": round(dt_s, 4), "g_frames_per_s": round(gfs, 4), "bytes_moved": moved,
                                   "gb_per_s": round(moved / dt_s / 1e9, 2), "chunk_streams": sp.info()["host_chunk_streams"]}), flush=True)
     # the conversion kernels' own time: one profiled call per format (events around every launch of the call)
     kernels = {}
-    for fmt, _, _ in FORMATS:
+    for lab, fmt, _, mode in runs:
         sp.set_profiling(True)
-        call("pinned", fmt)
+        call("pinned", fmt, mode)
         stages = {name: (ms, n) for name, ms, n in sp.stage_times()}
         sp.set_profiling(False)
-        kernels[fmt] = {k: {"ms": round(stages[k][0], 3), "launches": stages[k][1]} for k in ("aw_pcm_decode_kernel", "aw_pcm_encode_kernel") if k in stages}
+        kernels[lab] = {k: {"ms": round(stages[k][0], 3), "launches": stages[k][1]} for k in ("aw_pcm_decode_kernel", "aw_pcm_encode_kernel") if k in stages}
+    sp.set_dither("none")
     for kind in kinds:
         f32 = float(np.median(rates[(kind, "f32")]))
-        for fmt, _, b in FORMATS:
-            r = rates[(kind, fmt)]
-            print(json.dumps({"summary": kind, "format": f"{fmt}/{fmt}", "channels": C, "taps": a.taps, "bytes_per_frame": (C + 2) * b,
+        for lab, fmt, b, mode in runs:
+            r = rates[(kind, lab)]
+            print(json.dumps({"summary": kind, "format": f"{fmt}/{fmt}", "dither": mode, "channels": C, "taps": a.taps, "bytes_per_frame": (C + 2) * b,
                               "g_frames_per_s_min": round(min(r), 4), "median": round(float(np.median(r)), 4), "max": round(max(r), 4),
-                              "vs_f32_median": round(float(np.median(r)) / f32, 3), "conversion_kernels": kernels[fmt] if kind == "pinned" else None}),
+                              "vs_f32_median": round(float(np.median(r)) / f32, 3), "conversion_kernels": kernels[lab] if kind == "pinned" else None}),
                   flush=True)
     return 0
 
