@@ -10,7 +10,7 @@ from . import _capi
 _capi.load()
 
 from .api import (  # noqa: E402
-    AirwaveError, Context, ConvolutionEngine, DITHER_MODES, HRIR, HRIRChannelMap, HRIRError, HRIRManager, InputLayout,
+    AirwaveError, Context, ConvolutionEngine, DITHER_MODES, GAIN_MODES, HRIR, HRIRChannelMap, HRIRError, HRIRManager, InputLayout, LEVELS_DTYPE,
     RealtimeAudioProcessor, Resampler, SAMPLE_FORMATS, Spatializer, WAVData, WAVError, WAVLoader, default_context, sample_format_bytes,
 )
 
@@ -30,5 +30,5 @@ __all__ = [
     "ParametricEqualizerPreparationError", "ParametricEqualizerProcessor", "ParametricEqualizerState", "EqualizerNotFoldable", "FoldedHRIR", "fold_equalizer",
     "AirwaveError", "Context", "ConvolutionEngine", "HRIR", "HRIRChannelMap", "HRIRError", "HRIRManager",
     "InputLayout", "RealtimeAudioProcessor", "Resampler", "Spatializer", "WAVData", "WAVError", "WAVLoader",
-    "default_context", "SAMPLE_FORMATS", "sample_format_bytes", "DITHER_MODES",
+    "default_context", "SAMPLE_FORMATS", "sample_format_bytes", "DITHER_MODES", "GAIN_MODES", "LEVELS_DTYPE",
 ]

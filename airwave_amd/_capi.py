@@ -55,6 +55,10 @@ SIGNATURES = {
     "aw_spatializer_process_host_pcm": (_I32, [_V, _V, _I32, _V, _I32, _I64, ctypes.POINTER(ctypes.c_uint64)]),
     "aw_spatializer_reserve_pcm": (_I32, [_V, _I64, _I32, _I32]),
     "aw_spatializer_set_dither": (_I32, [_V, _I32, _U64, _U64]),
+    "aw_spatializer_set_metering": (_I32, [_V, _I32]),
+    "aw_spatializer_get_levels": (_I32, [_V, _I32, _I32, _V]),
+    "aw_spatializer_reset_levels": (_I32, [_V]),
+    "aw_spatializer_set_gain": (_I32, [_V, _I32, c_float_p, _I32, ctypes.c_float]),
     "aw_spatializer_reset": (_I32, [_V]),
     "aw_spatializer_stream_count": (_I32, [_V]),
     "aw_spatializer_channel_count": (_I32, [_V]),
@@ -132,6 +136,14 @@ SIGNATURES = {
     "aw_eq_transition_length": (_I32, [_V]),
     "aw_eq_is_transitioning": (_I32, [_V]),
 }
+
+
+
+class StreamLevels(ctypes.Structure):
+    """aw_stream_levels (56 bytes)."""
+    _fields_ = [("peak", ctypes.c_float * 2), ("gain", ctypes.c_float), ("reserved", ctypes.c_uint32), ("energy", ctypes.c_double * 2),
+                ("frames", ctypes.c_uint64), ("clipped", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64)]
+
 
 _lib = None
 

@@ -77,6 +77,11 @@ SAMPLE_FORMATS = {"f32": 0, "s16": 1, "s24": 2, "s32": 3}
 _FORMAT_DTYPE = {0: np.dtype(np.float32), 1: np.dtype(np.int16), 2: np.dtype(np.uint8), 3: np.dtype(np.int32)}
 # aw_dither (include/airwave_hip.h): dither of the s16 / s24 encode (Spatializer.set_dither)
 DITHER_MODES = {"none": 0, "tpdf": 1, "tpdf_hp": 2}
+# aw_gain_mode: output gain of the batch entries (Spatializer.set_gain)
+GAIN_MODES = {"none": 0, "fixed": 1, "peak_ceiling": 2}
+# aw_stream_levels, byte for byte (Spatializer.levels)
+LEVELS_DTYPE = np.dtype([("peak", np.float32, (2,)), ("gain", np.float32), ("reserved", np.uint32), ("energy", np.float64, (2,)),
+                         ("frames", np.uint64), ("clipped", np.uint64), ("nonfinite", np.uint64)], align=False)
 
 
 def sample_format_bytes(fmt) -> int:
@@ -427,7 +432,9 @@ class Spatializer:
                 "host_chunk_streams": g(15),    # streams per staged chunk of the last host-entry call (0: one piece)
                 "overlap_add_rows": g(16),      # the last call ran the overlap-add tile on blocks of 512 x this many frames (0: it did not)
                 "overlap_add_rows_policy": g(17),   # ... which this spatializer's calls do when they have enough blocks (0: never)
-                "position_frames": g(18)}       # frames processed since creation / the last reset (the dither's frame position)
+                "position_frames": g(18),       # frames processed since creation / the last reset (the dither's frame position)
+                "metering": g(19),              # the level meter is on (set_metering)
+                "gain_mode": g(20)}             # aw_gain_mode of the batch entries (set_gain)
 
     def process_device(self, in_ptr: int, out_ptr: int, frames: int) -> None:
         _check(self._lib.aw_spatializer_process(self._h, ctypes.c_void_p(in_ptr), ctypes.c_void_p(out_ptr), frames))
@@ -506,6 +513,50 @@ class Spatializer:
                 raise ValueError(f"unknown dither mode {mode!r} (one of {', '.join(DITHER_MODES)})")
             mode = DITHER_MODES[mode]
         _check(self._lib.aw_spatializer_set_dither(self._h, int(mode), int(seed), int(first_stream)))
+
+    def set_metering(self, on: bool = True) -> None:
+        """aw_spatializer_set_metering: per-stream levels of every later batch call (process, process_host_into, the PCM entries).
+        Switching it on allocates the records here, not on the process path."""
+        _check(self._lib.aw_spatializer_set_metering(self._h, int(bool(on))))
+
+    def levels(self, first_stream: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """aw_spatializer_get_levels: the records of n streams from first_stream on (default: all) as a structured array of
+        LEVELS_DTYPE (peak[2], gain, energy[2], frames, clipped, nonfinite).  Synchronises the context's stream."""
+        first_stream = int(first_stream)
+        n = self.n_streams - first_stream if n is None else int(n)
+        if first_stream < 0 or n < 0 or first_stream + n > self.n_streams:
+            raise ValueError(f"streams [{first_stream}, {first_stream + n}) outside [0, {self.n_streams})")
+        out = np.zeros(n, LEVELS_DTYPE)
+        _check(self._lib.aw_spatializer_get_levels(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
+        return out
+
+    def reset_levels(self) -> None:
+        _check(self._lib.aw_spatializer_reset_levels(self._h))
+
+    def set_gain(self, mode, gains=None, ceiling: Optional[float] = None) -> None:
+        """aw_spatializer_set_gain: 'none'; 'fixed' with one gain (every stream) or one per stream; 'peak_ceiling' with 0 < ceiling <= 1,
+        which scales every stream of every call down to the ceiling where that call's peak exceeds it (or the aw_gain_mode code)."""
+        if isinstance(mode, str):
+            if mode not in GAIN_MODES:
+                raise ValueError(f"unknown gain mode {mode!r} (one of {', '.join(GAIN_MODES)})")
+            mode = GAIN_MODES[mode]
+        mode = int(mode)
+        if mode not in GAIN_MODES.values():
+            raise ValueError(f"unknown gain mode {mode}")
+        g, c = None, 0.0
+        if mode == GAIN_MODES["fixed"]:
+            if gains is None:
+                raise ValueError("fixed gain needs gains")
+            g = np.ascontiguousarray(np.atleast_1d(np.asarray(gains, np.float32)))
+            if g.ndim != 1 or g.size not in (1, self.n_streams):
+                raise ValueError(f"gains must be 1 or {self.n_streams} values, got shape {g.shape}")
+            if not np.all(np.isfinite(g)):
+                raise ValueError("gains must be finite")
+        elif mode == GAIN_MODES["peak_ceiling"]:
+            if ceiling is None or not (0.0 < float(np.float32(ceiling)) <= 1.0):
+                raise ValueError(f"peak_ceiling needs 0 < ceiling <= 1, got {ceiling!r}")
+            c = float(ceiling)
+        _check(self._lib.aw_spatializer_set_gain(self._h, mode, None if g is None else _fp(g), 0 if g is None else int(g.size), ctypes.c_float(c)))
 
     def reset(self) -> None:
         _check(self._lib.aw_spatializer_reset(self._h))

@@ -9,10 +9,18 @@
 // argument, so the funnel indexes registers.  The unaligned head (at most 15 elements) and the ragged tail (fewer than G) are one element
 // per thread, byte by byte (pcm.hpp).  The dithered encode (s16 / s24, aw_spatializer_set_dither) is the same pass with the group's dither
 // values computed in registers from the element index (group_dither); the undithered kernel is unchanged.
+//
+// Levels and gain (aw_spatializer_set_metering / _set_gain; rules: levels.hpp): aw_levels_kernel reads a chunk's float32 output once and
+// adds every stream's peak, energy and non-finite count to its record, one atomic per wave and quantity; aw_scale_kernel multiplies
+// float32 output by its stream's gain in place; the gained encode (aw_pcm_encode_gain_kernel) is the encode pass with the group's gains
+// looked up the way its dither is, and with the clipped samples also counted per stream.  None of them runs, and the kernels above run as
+// they always have, while the meter is off and no gain is set.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 
+#include "levels.hpp"
 #include "pcm.hpp"
 #include "pcm_kernels.hpp"
 
@@ -119,16 +127,52 @@ template <int MODE> __device__ __forceinline__ int32_t enc_s24(float x, float d,
     if constexpr (MODE == awp::kDitherNone) return awp::encode_s24(x, k); else return awp::encode_s24_dithered(x, d, k);
 }
 
+// The gain of a launch (aw_spatializer_set_gain) and its per-stream clip counts: the launch covers whole streams of spf samples; gain,
+// call_peak and rec point at the entry of its first stream.
+struct GainLaunch {
+    int mode;                         // awl::GainMode; kGainNone: every gain is 1 (a metered encode without gain)
+    float ceiling;                    // kGainPeakCeiling
+    const float *gain;                // kGainFixed: the streams' gains
+    const uint32_t *call_peak;        // kGainPeakCeiling: bits of the streams' peaks over this call (aw_levels_kernel wrote them)
+    awl::Record *rec;                 // NULL, or the streams' records: clipped samples are counted per stream too
+    uint64_t spf;
+};
+
+__device__ __forceinline__ float stream_gain(const GainLaunch &gl, uint64_t s) {
+    if (gl.mode == awl::kGainFixed) return gl.gain[s];
+    if (gl.mode == awl::kGainPeakCeiling) return awl::auto_gain(awl::bits_float(gl.call_peak[s]), gl.ceiling);
+    return 1.0f;
+}
+
+// Gains of the G elements from element e on: group_dither's stepping, one division per group.  s / r: stream and sample in stream of e;
+// s_last: the stream of the group's last element.
+template <int G>
+__device__ __forceinline__ void group_gain(const GainLaunch &gl, uint64_t e, float (&g)[G], uint64_t &s, uint64_t &r, uint64_t &s_last) {
+    s = e / gl.spf; r = e - s * gl.spf;
+    uint64_t si = s, ri = r;
+    float gs = stream_gain(gl, si);
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+        if (j > 0 && ++ri == gl.spf) { ri = 0; gs = stream_gain(gl, ++si); }
+        g[j] = gs;
+    }
+    s_last = si;
+}
+
 // The encode kernels' body.  Q: the body's first float lies at 16 * k + 4 * Q.  MODE kDitherNone is aw_pcm_encode_kernel as it always
-// was (dl unused); the dithered forms (s16 / s24) add the group's dither values before the rounding.
-template <int FMT, int Q, int MODE>
+// was (dl unused); the dithered forms (s16 / s24) add the group's dither values before the rounding.  GM (gain / meter, gl) multiplies
+// every sample by its stream's gain first and counts the clipped samples per stream as well; without it gl is unused and the code is
+// what it was.
+template <int FMT, int Q, int MODE, bool GM = false>
 __device__ __forceinline__ void encode_body(const float *__restrict__ src, unsigned char *__restrict__ dst, int64_t n, int64_t head,
-                                            int64_t n_body, unsigned long long *clipped, const DitherLaunch &dl) {
+                                            int64_t n_body, unsigned long long *clipped, const DitherLaunch &dl, const GainLaunch &gl = {}) {
     constexpr int G = Group<FMT>::G, W = Group<FMT>::words, BYTES = FMT == awp::kS24 ? 3 : FMT == awp::kS16 ? 2 : 4;
     constexpr int FW = G / 4;                                 // 16-B words of floats per group
     static_assert(MODE == awp::kDitherNone || FMT == awp::kS16 || FMT == awp::kS24, "only s16 and s24 are dithered");
     const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     unsigned c = 0;                                           // clipped samples of this lane
+    unsigned cm = 0, lane_count = 0;                          // GM: clip flags of the group's elements; clipped samples this lane reports for
+    uint32_t lane_stream = 0;                                 //     stream lane_stream at the end (a group inside one stream, or an edge element)
     if (t < n_body) {
         const int64_t e = head + t * G;
         const float4 *w = reinterpret_cast<const float4 *>(src + e - Q);
@@ -137,6 +181,13 @@ __device__ __forceinline__ void encode_body(const float *__restrict__ src, unsig
         for (int i = 0; i < FW; ++i) { const float4 v = w[i]; f[4 * i] = v.x; f[4 * i + 1] = v.y; f[4 * i + 2] = v.z; f[4 * i + 3] = v.w; }
         if (Q != 0) { const float4 v = w[FW]; f[4 * FW] = v.x; f[4 * FW + 1] = v.y; f[4 * FW + 2] = v.z; f[4 * FW + 3] = v.w; }
         else { f[4 * FW] = f[4 * FW + 1] = f[4 * FW + 2] = f[4 * FW + 3] = 0.0f; }
+        uint64_t gs0 = 0, gr0 = 0, gs1 = 0;
+        if constexpr (GM) {
+            float g[G];
+            group_gain<G>(gl, (uint64_t)e, g, gs0, gr0, gs1);
+#pragma unroll
+            for (int j = 0; j < G; ++j) f[Q + j] = awl::apply_gain(f[Q + j], g[j]);
+        }
         float d[G];
         if constexpr (MODE != awp::kDitherNone) group_dither<MODE, G>(dl, (uint64_t)e, d);
         else {
@@ -152,6 +203,7 @@ __device__ __forceinline__ void encode_body(const float *__restrict__ src, unsig
                 const uint32_t hi = (uint32_t)enc_s16<MODE>(f[Q + 2 * i + 1], d[2 * i + 1], &c1) & 0xFFFFu;
                 s[i] = lo | (hi << 16);
                 c += c0 + c1;
+                if constexpr (GM) cm |= (c0 << (2 * i)) | (c1 << (2 * i + 1));
             }
         } else if constexpr (FMT == awp::kS24) {
 #pragma unroll
@@ -164,23 +216,63 @@ __device__ __forceinline__ void encode_body(const float *__restrict__ src, unsig
                 s[3 * q + 1] = (u[1] >> 8) | (u[2] << 16);
                 s[3 * q + 2] = (u[2] >> 16) | (u[3] << 8);
                 c += k[0] + k[1] + k[2] + k[3];
+                if constexpr (GM) cm |= (k[0] | (k[1] << 1) | (k[2] << 2) | (k[3] << 3)) << (4 * q);
             }
         } else {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { unsigned k = 0; s[i] = (uint32_t)awp::encode_s32(f[Q + i], &k); c += k; }
+            for (int i = 0; i < 4; ++i) {
+                unsigned k = 0;
+                s[i] = (uint32_t)awp::encode_s32(f[Q + i], &k);
+                c += k;
+                if constexpr (GM) cm |= k << i;
+            }
         }
         uint4 *o = reinterpret_cast<uint4 *>(dst + e * BYTES);
 #pragma unroll
         for (int i = 0; i < W; ++i) o[i] = make_uint4(s[4 * i], s[4 * i + 1], s[4 * i + 2], s[4 * i + 3]);
+        if constexpr (GM) {
+            if (gl.rec && cm) {
+                if (gs0 == gs1) { lane_stream = (uint32_t)gs0; lane_count = (unsigned)__popc(cm); }
+                else {                                        // the group crosses streams: one add per clipped element
+#pragma unroll
+                    for (int j = 0; j < G; ++j) {
+                        if (j > 0 && ++gr0 == gl.spf) { gr0 = 0; ++gs0; }
+                        if ((cm >> j) & 1u) atomicAdd(&gl.rec[gs0].clipped, 1ull);
+                    }
+                }
+            }
+        }
     } else {
         const int64_t idx = t - n_body, body_end = head + n_body * G;
         if (idx < n - n_body * G) {
             const int64_t e = edge_element(idx, head, body_end);
-            if constexpr (MODE == awp::kDitherNone) {
+            if constexpr (GM) {
+                const uint64_t s = (uint64_t)e / gl.spf, r = (uint64_t)e - s * gl.spf;
+                unsigned k = 0;
+                awl::encode_gained_at(FMT, MODE, src[e], stream_gain(gl, s), MODE == awp::kDitherNone ? 0 : awp::dither_key(dl.seed, dl.g0 + s),
+                                      dl.pos + (r >> 1), (int)(r & 1), dst + e * BYTES, &k);
+                c = k;
+                if (gl.rec) { lane_stream = (uint32_t)s; lane_count = k; }
+            } else if constexpr (MODE == awp::kDitherNone) {
                 awp::encode_at(FMT, src[e], dst + e * BYTES, &c);
             } else {
                 const uint64_t s = (uint64_t)e / dl.spf, r = (uint64_t)e - s * dl.spf;
                 awp::encode_dithered_at(FMT, MODE, src[e], awp::dither_key(dl.seed, dl.g0 + s), dl.pos + (r >> 1), (int)(r & 1), dst + e * BYTES, &c);
+            }
+        }
+    }
+    if constexpr (GM) {
+        // per stream: one ballot-summed add where every reporting lane of the wave lies in one stream, else one add per lane
+        if (lane_count) {
+            const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)lane_stream);
+            const unsigned long long lanes = __ballot(1);
+            if (__ballot(lane_stream != first) == 0) {
+                unsigned long long sum = 0;
+#pragma unroll
+                for (int bit = 0; bit < 5; ++bit) sum += (unsigned long long)__popcll(__ballot((lane_count >> bit) & 1u)) << bit;
+                if ((int)__lane_id() == __ffsll((long long)lanes) - 1) atomicAdd(&gl.rec[first].clipped, sum);
+            } else {
+                atomicAdd(&gl.rec[lane_stream].clipped, (unsigned long long)lane_count);
             }
         }
     }
@@ -203,6 +295,131 @@ template <int FMT, int Q, int MODE>
 __global__ __launch_bounds__(kThreads) void aw_pcm_encode_dither_kernel(const float *__restrict__ src, unsigned char *__restrict__ dst, int64_t n,
                                                                         int64_t head, int64_t n_body, unsigned long long *clipped, DitherLaunch dl) {
     encode_body<FMT, Q, MODE>(src, dst, n, head, n_body, clipped, dl);
+}
+
+template <int FMT, int Q, int MODE>
+__global__ __launch_bounds__(kThreads) void aw_pcm_encode_gain_kernel(const float *__restrict__ src, unsigned char *__restrict__ dst, int64_t n,
+                                                                      int64_t head, int64_t n_body, unsigned long long *clipped, DitherLaunch dl,
+                                                                      GainLaunch gl) {
+    encode_body<FMT, Q, MODE, true>(src, dst, n, head, n_body, clipped, dl, gl);
+}
+
+// ---- levels: peak, energy and non-finite count of every stream of a chunk's float32 output ---------------------------------------------
+// The launch covers whole streams of spf samples; rec (NULL: the meter is off and only the automatic gain wants the peaks) and call_peak
+// point at the entry of its first stream.
+struct LevelsLaunch { awl::Record *rec; uint32_t *call_peak; uint64_t spf; };
+
+constexpr int kLevelsIter = 8;                                // 16-B words per lane: a wave covers 8 KB, one set of atomics where it lies in one stream
+
+// adds one lane's (or one reduced wave's) sums of stream s; ears as given
+__device__ __forceinline__ void levels_add(const LevelsLaunch &ll, uint64_t s, uint32_t pk0, uint32_t pk1, double en0, double en1, unsigned nf) {
+    if (ll.rec) {
+        awl::Record *r = ll.rec + s;
+        if (pk0) atomicMax(&r->peak_bits[0], pk0);
+        if (pk1) atomicMax(&r->peak_bits[1], pk1);
+        if (en0 != 0.0) atomicAdd(&r->energy[0], en0);
+        if (en1 != 0.0) atomicAdd(&r->energy[1], en1);
+        if (nf) atomicAdd(&r->nonfinite, (unsigned long long)nf);
+    }
+    const uint32_t m = pk0 > pk1 ? pk0 : pk1;
+    if (m) atomicMax(&ll.call_peak[s], m);
+}
+
+// the whole wave's sums of stream s (every lane calls; a[0] / a[1]: even / odd elements, swapped = the launch's body starts on a right ear)
+__device__ __forceinline__ void levels_wave_add(const LevelsLaunch &ll, uint64_t s, bool swapped, uint32_t (&pk)[2], double (&en)[2], unsigned &nf) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t p0 = __shfl_xor(pk[0], m), p1 = __shfl_xor(pk[1], m);
+        pk[0] = p0 > pk[0] ? p0 : pk[0];
+        pk[1] = p1 > pk[1] ? p1 : pk[1];
+        en[0] += __shfl_xor(en[0], m);
+        en[1] += __shfl_xor(en[1], m);
+        nf += __shfl_xor(nf, m);
+    }
+    if (__lane_id() == 0) {
+        if (swapped) levels_add(ll, s, pk[1], pk[0], en[1], en[0], nf);
+        else levels_add(ll, s, pk[0], pk[1], en[0], en[1], nf);
+    }
+    pk[0] = pk[1] = 0u; en[0] = en[1] = 0.0; nf = 0u;
+}
+
+// src: n floats, 4-byte aligned; the body of n_body 16-B words starts at element head; the at most 6 elements before and after it are
+// one thread each in workgroup 0.  Every wave is launched whole and keeps its lanes together, so the shuffles see all 64 lanes.
+__global__ __launch_bounds__(kThreads) void aw_levels_kernel(const float *__restrict__ src, int64_t n, int64_t head, int64_t n_body, LevelsLaunch ll) {
+    const int lane = (int)(threadIdx.x & 63u);
+    if (blockIdx.x == 0 && (int64_t)threadIdx.x < n - 4 * n_body) {
+        const uint64_t e = (uint64_t)edge_element((int64_t)threadIdx.x, head, head + 4 * n_body), s = e / ll.spf;
+        uint32_t pk[2] = {0u, 0u}; double en[2] = {0.0, 0.0}; unsigned nf = 0;
+        const int ear = (int)((e - s * ll.spf) & 1u);
+        awl::contribute(src[e], pk[ear], en[ear], nf);
+        levels_add(ll, s, pk[0], pk[1], en[0], en[1], nf);
+    }
+    const float4 *w = reinterpret_cast<const float4 *>(src + head);
+    const bool swapped = (head & 1) != 0;
+    const int64_t wave = (int64_t)blockIdx.x * (kThreads / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int64_t w0 = wave * (64 * kLevelsIter);
+    if (w0 >= n_body) return;
+    // stream and sample in stream of the wave's first element: one division per wave, then steps of 256 samples
+    uint64_t s0 = ((uint64_t)head + 4 * (uint64_t)w0) / ll.spf, r0 = (uint64_t)head + 4 * (uint64_t)w0 - s0 * ll.spf;
+    uint32_t pk[2] = {0u, 0u}; double en[2] = {0.0, 0.0}; unsigned nf = 0;
+    bool open = false;                                        // the registers hold sums of stream cur
+    uint64_t cur = 0;
+    for (int i = 0; i < kLevelsIter && w0 < n_body; ++i, w0 += 64) {
+        const int64_t w_last = w0 + 63 < n_body ? w0 + 63 : n_body - 1;
+        const bool one_stream = r0 + (uint64_t)(4 * (w_last - w0) + 3) < ll.spf;
+        const int64_t wi = w0 + lane;
+        const bool valid = wi < n_body;
+        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (valid) v = w[wi];
+        if (one_stream) {
+            if (open && cur != s0) { levels_wave_add(ll, cur, swapped, pk, en, nf); open = false; }
+            open = true; cur = s0;
+            if (valid) {
+                awl::contribute(v.x, pk[0], en[0], nf); awl::contribute(v.y, pk[1], en[1], nf);
+                awl::contribute(v.z, pk[0], en[0], nf); awl::contribute(v.w, pk[1], en[1], nf);
+            }
+        } else {                                              // the wave's 256 samples cross streams: every lane adds its own
+            if (open) { levels_wave_add(ll, cur, swapped, pk, en, nf); open = false; }
+            if (valid) {
+                const float y[4] = {v.x, v.y, v.z, v.w};
+                const uint64_t e = (uint64_t)head + 4 * (uint64_t)wi;
+                uint64_t s = e / ll.spf, r = e - s * ll.spf;
+                uint32_t lp[2] = {0u, 0u}; double le[2] = {0.0, 0.0}; unsigned ln = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (j > 0 && ++r == ll.spf) {
+                        levels_add(ll, s, lp[0], lp[1], le[0], le[1], ln);
+                        lp[0] = lp[1] = 0u; le[0] = le[1] = 0.0; ln = 0u; r = 0; ++s;
+                    }
+                    awl::contribute(y[j], lp[r & 1u], le[r & 1u], ln);
+                }
+                levels_add(ll, s, lp[0], lp[1], le[0], le[1], ln);
+            }
+        }
+        r0 += 256;
+        while (r0 >= ll.spf) { r0 -= ll.spf; ++s0; }
+    }
+    if (open) levels_wave_add(ll, cur, swapped, pk, en, nf);
+}
+
+// ---- scale: float32 output times its stream's gain, in place ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void aw_scale_kernel(float *__restrict__ buf, int64_t n, int64_t head, int64_t n_body, GainLaunch gl) {
+    const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (t < n_body) {
+        const int64_t e = head + 4 * t;
+        float4 *w = reinterpret_cast<float4 *>(buf + e);
+        const float4 v = *w;
+        float g[4];
+        uint64_t s, r, s_last;
+        group_gain<4>(gl, (uint64_t)e, g, s, r, s_last);
+        *w = make_float4(awl::apply_gain(v.x, g[0]), awl::apply_gain(v.y, g[1]), awl::apply_gain(v.z, g[2]), awl::apply_gain(v.w, g[3]));
+    } else {
+        const int64_t idx = t - n_body;
+        if (idx < n - 4 * n_body) {
+            const int64_t e = edge_element(idx, head, head + 4 * n_body);
+            buf[e] = awl::apply_gain(buf[e], stream_gain(gl, (uint64_t)e / gl.spf));
+        }
+    }
 }
 
 // element count of the unaligned head: 16-B alignment of the address + head * bytes; n (all one-element threads) when there is none
@@ -235,15 +452,18 @@ hipError_t decode_fmt(const unsigned char *src, float *dst, int64_t n, hipStream
 
 template <int FMT, int Q, int MODE>
 void encode_launch(dim3 grid, hipStream_t stream, const float *src, unsigned char *dst, int64_t n, int64_t head, int64_t n_body,
-                   unsigned long long *clipped, const DitherLaunch &dl) {
-    if constexpr (MODE == awp::kDitherNone)
+                   unsigned long long *clipped, const DitherLaunch &dl, const GainLaunch *gl) {
+    if (gl)
+        hipLaunchKernelGGL((aw_pcm_encode_gain_kernel<FMT, Q, MODE>), grid, dim3(kThreads), 0, stream, src, dst, n, head, n_body, clipped, dl, *gl);
+    else if constexpr (MODE == awp::kDitherNone)
         hipLaunchKernelGGL((aw_pcm_encode_kernel<FMT, Q>), grid, dim3(kThreads), 0, stream, src, dst, n, head, n_body, clipped);
     else
         hipLaunchKernelGGL((aw_pcm_encode_dither_kernel<FMT, Q, MODE>), grid, dim3(kThreads), 0, stream, src, dst, n, head, n_body, clipped, dl);
 }
 
 template <int FMT, int MODE = awp::kDitherNone>
-hipError_t encode_fmt(const float *src, unsigned char *dst, int64_t n, unsigned long long *clipped, hipStream_t stream, const DitherLaunch &dl = {}) {
+hipError_t encode_fmt(const float *src, unsigned char *dst, int64_t n, unsigned long long *clipped, hipStream_t stream, const DitherLaunch &dl = {},
+                      const GainLaunch *gl = nullptr) {
     constexpr int G = Group<FMT>::G, BYTES = FMT == awp::kS24 ? 3 : FMT == awp::kS16 ? 2 : 4;
     if (reinterpret_cast<uintptr_t>(src) & 3u) return hipErrorInvalidValue;
     const int64_t head = head_to_align(reinterpret_cast<uintptr_t>(dst), BYTES, n);
@@ -252,10 +472,10 @@ hipError_t encode_fmt(const float *src, unsigned char *dst, int64_t n, unsigned 
     const unsigned q = (unsigned)(((reinterpret_cast<uintptr_t>(src) + (uintptr_t)head * 4) & 15u) >> 2);
     const dim3 grid((unsigned)((threads + kThreads - 1) / kThreads));
     switch (q) {
-        case 0: encode_launch<FMT, 0, MODE>(grid, stream, src, dst, n, head, n_body, clipped, dl); break;
-        case 1: encode_launch<FMT, 1, MODE>(grid, stream, src, dst, n, head, n_body, clipped, dl); break;
-        case 2: encode_launch<FMT, 2, MODE>(grid, stream, src, dst, n, head, n_body, clipped, dl); break;
-        default: encode_launch<FMT, 3, MODE>(grid, stream, src, dst, n, head, n_body, clipped, dl); break;
+        case 0: encode_launch<FMT, 0, MODE>(grid, stream, src, dst, n, head, n_body, clipped, dl, gl); break;
+        case 1: encode_launch<FMT, 1, MODE>(grid, stream, src, dst, n, head, n_body, clipped, dl, gl); break;
+        case 2: encode_launch<FMT, 2, MODE>(grid, stream, src, dst, n, head, n_body, clipped, dl, gl); break;
+        default: encode_launch<FMT, 3, MODE>(grid, stream, src, dst, n, head, n_body, clipped, dl, gl); break;
     }
     return hipGetLastError();
 }
@@ -301,6 +521,55 @@ hipError_t launch_pcm_encode_dithered(int fmt, const PcmDither &dither, const fl
         case awp::kS24 * 4 + awp::kDitherTpdfHp: return encode_fmt<awp::kS24, awp::kDitherTpdfHp>(src, d, n, clipped, stream, dl);
         default: return hipErrorInvalidValue;
     }
+}
+
+static GainLaunch gain_launch(const PcmGain &gain, int64_t frames) {
+    return GainLaunch{gain.mode, gain.ceiling, gain.gain, gain.call_peak, gain.rec, 2 * (uint64_t)frames};
+}
+static bool gain_ok(const PcmGain &gain) {
+    if (gain.mode == awl::kGainFixed) return gain.gain != nullptr;
+    if (gain.mode == awl::kGainPeakCeiling) return gain.call_peak != nullptr;
+    return gain.mode == awl::kGainNone;
+}
+
+hipError_t launch_pcm_encode_gained(int fmt, const PcmDither &dither, const PcmGain &gain, const float *src, void *dst, int64_t n,
+                                    unsigned long long *clipped, hipStream_t stream) {
+    if (!gain_ok(gain) || dither.frames <= 0 || n < 0 || n % (2 * dither.frames)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    unsigned char *d = static_cast<unsigned char *>(dst);
+    const DitherLaunch dl{dither.seed, dither.first_stream, dither.position, 2 * (uint64_t)dither.frames};
+    const GainLaunch gl = gain_launch(gain, dither.frames);
+    const int mode = fmt == awp::kS32 ? awp::kDitherNone : dither.mode;
+    switch (fmt * 4 + mode) {
+        case awp::kS16 * 4 + awp::kDitherNone: return encode_fmt<awp::kS16, awp::kDitherNone>(src, d, n, clipped, stream, dl, &gl);
+        case awp::kS16 * 4 + awp::kDitherTpdf: return encode_fmt<awp::kS16, awp::kDitherTpdf>(src, d, n, clipped, stream, dl, &gl);
+        case awp::kS16 * 4 + awp::kDitherTpdfHp: return encode_fmt<awp::kS16, awp::kDitherTpdfHp>(src, d, n, clipped, stream, dl, &gl);
+        case awp::kS24 * 4 + awp::kDitherNone: return encode_fmt<awp::kS24, awp::kDitherNone>(src, d, n, clipped, stream, dl, &gl);
+        case awp::kS24 * 4 + awp::kDitherTpdf: return encode_fmt<awp::kS24, awp::kDitherTpdf>(src, d, n, clipped, stream, dl, &gl);
+        case awp::kS24 * 4 + awp::kDitherTpdfHp: return encode_fmt<awp::kS24, awp::kDitherTpdfHp>(src, d, n, clipped, stream, dl, &gl);
+        case awp::kS32 * 4 + awp::kDitherNone: return encode_fmt<awp::kS32, awp::kDitherNone>(src, d, n, clipped, stream, dl, &gl);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_levels(const float *src, int64_t n, int64_t frames, awl::Record *rec, uint32_t *call_peak, hipStream_t stream) {
+    if (!call_peak || frames <= 0 || n < 0 || n % (2 * frames) || (reinterpret_cast<uintptr_t>(src) & 3u)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const int64_t head = head_to_align(reinterpret_cast<uintptr_t>(src), 4, n), n_body = (n - head) / 4;
+    const int64_t per_block = (int64_t)(kThreads / 64) * 64 * kLevelsIter;               // 16-B words per workgroup
+    const dim3 grid((unsigned)std::max<int64_t>(1, (n_body + per_block - 1) / per_block));
+    hipLaunchKernelGGL(aw_levels_kernel, grid, dim3(kThreads), 0, stream, src, n, head, n_body, LevelsLaunch{rec, call_peak, 2 * (uint64_t)frames});
+    return hipGetLastError();
+}
+
+hipError_t launch_scale(float *buf, int64_t n, int64_t frames, const PcmGain &gain, hipStream_t stream) {
+    if (!gain_ok(gain) || frames <= 0 || n < 0 || n % (2 * frames) || (reinterpret_cast<uintptr_t>(buf) & 3u)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const int64_t head = head_to_align(reinterpret_cast<uintptr_t>(buf), 4, n), n_body = (n - head) / 4;
+    const int64_t threads = n_body + (n - 4 * n_body);
+    const dim3 grid((unsigned)((threads + kThreads - 1) / kThreads));
+    hipLaunchKernelGGL(aw_scale_kernel, grid, dim3(kThreads), 0, stream, buf, n, head, n_body, gain_launch(gain, frames));
+    return hipGetLastError();
 }
 
 }  // namespace awk

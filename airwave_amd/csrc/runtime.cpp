@@ -717,6 +717,7 @@ void aw_spatializer_destroy(aw_spatializer *sp) {
     if (sp->d_pcm_in) (void)hipFree(sp->d_pcm_in);
     if (sp->d_pcm_out) (void)hipFree(sp->d_pcm_out);
     if (sp->d_clip) (void)hipFree(sp->d_clip);
+    if (sp->d_levels) (void)hipFree(sp->d_levels);
     if (sp->k0) (void)hipEventDestroy(sp->k0);
     if (sp->k1) (void)hipEventDestroy(sp->k1);
     for (auto &pr : sp->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -749,6 +750,8 @@ int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what) {
         case 16: return sp->last_ola_h;           // rows H of the overlap-add blocks (512 H frames) the last call ran on; 0: it ran another tile
         case 17: return sp->ola_h;                // rows H this spatializer's long-enough calls use (0: the overlap-add tile is not used)
         case 18: return (int64_t)sp->position;    // frames processed since create / the last reset (the dither's frame position)
+        case 19: return sp->metering ? 1 : 0;     // the level meter is on (aw_spatializer_set_metering)
+        case 20: return sp->gain_mode;            // aw_gain_mode of the batch entries (aw_spatializer_set_gain)
         default: return -1;
     }
 }
@@ -1422,16 +1425,101 @@ static LwCallPlan sp_begin_call(aw_spatializer *sp, int64_t frames, uint64_t *po
     return lw;
 }
 
-aw_status aw_spatializer_process(aw_spatializer *sp, const float *in, float *out, int64_t frames) try {
+/* ---- level meter and output gain of the batch entries (aw_spatializer_set_metering / _set_gain; rules: device/levels.hpp) ------------- */
+static_assert(AW_GAIN_NONE == awl::kGainNone && AW_GAIN_FIXED == awl::kGainFixed && AW_GAIN_PEAK_CEILING == awl::kGainPeakCeiling, "aw_gain_mode");
+static_assert(sizeof(aw_stream_levels) == 56 && sizeof(awl::Record) == 40, "aw_stream_levels");
+static awl::Record *lv_records(const aw_spatializer *sp) { return reinterpret_cast<awl::Record *>(sp->d_levels); }
+static uint32_t *lv_call_peaks(const aw_spatializer *sp) { return reinterpret_cast<uint32_t *>(sp->d_levels + (size_t)sp->n_streams * sizeof(awl::Record)); }
+static float *lv_gains(const aw_spatializer *sp) { return reinterpret_cast<float *>(lv_call_peaks(sp) + sp->n_streams); }
+// a batch call has anything to do here; while this is false every entry launches what it always has
+static bool lv_active(const aw_spatializer *sp) { return sp->metering || sp->gain_mode != AW_GAIN_NONE; }
+// the levels kernel runs: the meter wants the sums, the automatic gain the call's peaks
+static bool lv_measures(const aw_spatializer *sp) { return sp->metering || sp->gain_mode == AW_GAIN_PEAK_CEILING; }
+
+// the one allocation (set_metering(1) / set_gain make it: never the process path), zeroed
+static aw_status lv_buffers(aw_spatializer *sp) {
+    if (sp->d_levels) return AW_OK;
+    const size_t bytes = (size_t)sp->n_streams * (sizeof(awl::Record) + sizeof(uint32_t) + sizeof(float));
+    AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sp->d_levels), bytes));
+    sp->ctx->device_allocs += 1;
+    AW_HIP_TRY(hipMemsetAsync(sp->d_levels, 0, bytes, sp->ctx->stream));
+    return AW_OK;
+}
+
+// Once per batch call, before its first launch: what the call applies (aw_stream_levels::gain), the frames it meters, and — where the
+// levels kernel runs (device) — the call-local peaks start from zero.
+static aw_status lv_begin_call(aw_spatializer *sp, int64_t frames, bool device) {
+    if (!lv_active(sp)) { sp->applied_mode = AW_GAIN_NONE; return AW_OK; }
+    sp->applied_mode = sp->gain_mode;
+    sp->applied_ceiling = sp->gain_ceiling;
+    sp->applied_on_host = !device;
+    if (sp->gain_mode == AW_GAIN_FIXED) sp->applied_gains = sp->gains;
+    if (sp->metering) sp->metered_frames += (uint64_t)frames;
+    if (device && lv_measures(sp)) AW_HIP_TRY(hipMemsetAsync(lv_call_peaks(sp), 0, (size_t)sp->n_streams * sizeof(uint32_t), sp->ctx->stream));
+    return AW_OK;
+}
+
+static awk::PcmGain lv_gain_launch(const aw_spatializer *sp, int64_t s0) {
+    return awk::PcmGain{sp->gain_mode, sp->gain_ceiling, lv_gains(sp) + s0, lv_call_peaks(sp) + s0, sp->metering ? lv_records(sp) + s0 : nullptr};
+}
+
+// After the kernels of the streams [s0, s0 + ns) have written their float32 output to f_out: meter it, and — float32 output with a gain
+// set — scale it in place (integer output is gained by its encode).
+static aw_status lv_after_run(aw_spatializer *sp, float *f_out, int64_t s0, int ns, int64_t frames, bool float_out) {
+    if (!lv_active(sp)) return AW_OK;
+    const int64_t n = (int64_t)ns * 2 * frames;
+    if (lv_measures(sp)) {
+        SpStageTimer tm(sp);
+        if (sp->profiling) tm.begin();
+        AW_HIP_TRY(awk::launch_levels(f_out, n, frames, sp->metering ? lv_records(sp) + s0 : nullptr, lv_call_peaks(sp) + s0, sp->ctx->stream));
+        if (sp->profiling) tm.end("aw_levels_kernel");
+    }
+    if (float_out && sp->gain_mode != AW_GAIN_NONE) {
+        SpStageTimer tm(sp);
+        if (sp->profiling) tm.begin();
+        AW_HIP_TRY(awk::launch_scale(f_out, n, frames, lv_gain_launch(sp, s0), sp->ctx->stream));
+        if (sp->profiling) tm.end("aw_scale_kernel");
+    }
+    return AW_OK;
+}
+
+// The single-stream page-locked path: the same rules on the CPU, over the n = 2 * frames output samples y.  Returns the call's gain.
+static float lv_host_call(aw_spatializer *sp, const float *y, size_t n) {
+    uint32_t pk[2] = {0u, 0u};
+    double en[2] = {0.0, 0.0};
+    unsigned nf = 0;
+    if (lv_measures(sp)) for (size_t i = 0; i < n; ++i) awl::contribute(y[i], pk[i & 1], en[i & 1], nf);
+    if (sp->metering) {
+        for (int e = 0; e < 2; ++e) {
+            sp->h_levels.peak_bits[e] = std::max(sp->h_levels.peak_bits[e], pk[e]);
+            sp->h_levels.energy[e] += en[e];
+        }
+        sp->h_levels.nonfinite += nf;
+    }
+    float g = 1.0f;
+    if (sp->gain_mode == AW_GAIN_FIXED) g = sp->gains[0];
+    else if (sp->gain_mode == AW_GAIN_PEAK_CEILING) g = awl::auto_gain(awl::bits_float(std::max(pk[0], pk[1])), sp->gain_ceiling);
+    sp->applied_host_gain = g;
+    return g;
+}
+
+// metered: a batch entry's call (metered and gained as the handle is set); the planar entry's inner call is not
+static aw_status process_device(aw_spatializer *sp, const float *in, float *out, int64_t frames, bool metered) {
     if (!sp || !in || !out) return fail(AW_ERR_INVALID_ARGUMENT, "NULL argument");
     if (frames <= 0) return frames == 0 ? AW_OK : fail(AW_ERR_INVALID_ARGUMENT, "frames must be >= 0");
     AW_HIP_TRY(hipSetDevice(sp->ctx->device));
     std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);       // this call's launches stay together on the stream (the scratch pool is the context's)
     const LwCallPlan lw = sp_begin_call(sp, frames);
-    aw_status st = sp_run_streams(sp, lw, 0, sp->n_streams, in, out, frames);
+    aw_status st = metered ? lv_begin_call(sp, frames, true) : AW_OK;
+    if (st == AW_OK) st = sp_run_streams(sp, lw, 0, sp->n_streams, in, out, frames);
+    if (st == AW_OK && metered) st = lv_after_run(sp, out, 0, sp->n_streams, frames, true);
     if (st != AW_OK) return st;
     sp->hist_cur ^= 1;
     return AW_OK;
+}
+
+aw_status aw_spatializer_process(aw_spatializer *sp, const float *in, float *out, int64_t frames) try {
+    return process_device(sp, in, out, frames, true);
 } AW_NOEXCEPT_TAIL
 
 /* ---- host entry ------------------------------------------------------------------------------------
@@ -1577,7 +1665,10 @@ static aw_status pcm_encode(aw_spatializer *sp, int out_fmt, const float *src, v
                             int64_t frames, uint64_t pos) {
     SpStageTimer tm(sp);
     if (sp->profiling) tm.begin();
-    if (sp_dithers(sp, out_fmt)) {
+    if (lv_active(sp)) {                 // the gained / metered encode; the two below stay the ones launched without gain and meter
+        const awk::PcmDither d{sp_dithers(sp, out_fmt) ? sp->dither : awp::kDitherNone, sp->dither_seed, sp->dither_first_stream + (uint64_t)s0, pos, frames};
+        AW_HIP_TRY(awk::launch_pcm_encode_gained(out_fmt, d, lv_gain_launch(sp, s0), src, dst, n, clipped, sp->ctx->stream));
+    } else if (sp_dithers(sp, out_fmt)) {
         const awk::PcmDither d{sp->dither, sp->dither_seed, sp->dither_first_stream + (uint64_t)s0, pos, frames};
         AW_HIP_TRY(awk::launch_pcm_encode_dithered(out_fmt, d, src, dst, n, clipped, sp->ctx->stream));
     } else {
@@ -1604,20 +1695,28 @@ static aw_status host_process(aw_spatializer *sp, const void *in_v, int in_fmt, 
         else std::memcpy(sp->h_pin_in, in, in_psb);
         uint64_t pos0 = 0;
         const LwCallPlan lw0 = sp_begin_call(sp, frames, &pos0);
-        aw_status st0 = sp_run_streams(sp, lw0, 0, 1, sp->h_pin_in, sp->h_pin_out, frames);
+        aw_status st0 = lv_begin_call(sp, frames, false);
+        if (st0 == AW_OK) st0 = sp_run_streams(sp, lw0, 0, 1, sp->h_pin_in, sp->h_pin_out, frames);
         if (st0 != AW_OK) return st0;
         sp->hist_cur ^= 1;
         AW_HIP_TRY(hipStreamSynchronize(c->stream));
+        const bool lv = lv_active(sp);
+        const float gain = lv ? lv_host_call(sp, sp->h_pin_out, out_ps) : 1.0f;
         if (enc) {
             uint64_t n_clip = 0;
             const int mode = sp_dithers(sp, out_fmt) ? sp->dither : awp::kDitherNone;
             const uint64_t key = awp::dither_key(sp->dither_seed, sp->dither_first_stream);
             for (size_t i = 0; i < out_ps; ++i) {
                 unsigned k = 0;
-                awp::encode_dithered_at(out_fmt, mode, sp->h_pin_out[i], key, pos0 + i / 2, (int)(i & 1), out + i * out_b, &k);
+                if (lv) awl::encode_gained_at(out_fmt, mode, sp->h_pin_out[i], gain, key, pos0 + i / 2, (int)(i & 1), out + i * out_b, &k);
+                else awp::encode_dithered_at(out_fmt, mode, sp->h_pin_out[i], key, pos0 + i / 2, (int)(i & 1), out + i * out_b, &k);
                 n_clip += k;
             }
+            if (sp->metering) sp->h_levels.clipped += n_clip;
             if (clipped) *clipped = n_clip;
+        } else if (sp->gain_mode != AW_GAIN_NONE) {
+            float *o = reinterpret_cast<float *>(out);
+            for (size_t i = 0; i < out_ps; ++i) o[i] = awl::apply_gain(sp->h_pin_out[i], gain);
         } else {
             std::memcpy(out, sp->h_pin_out, out_psb);
         }
@@ -1635,10 +1734,12 @@ static aw_status host_process(aw_spatializer *sp, const void *in_v, int in_fmt, 
     if (enc) AW_HIP_TRY(hipMemsetAsync(sp->d_clip, 0, sizeof(unsigned long long), c->stream));
     uint64_t n_clip = 0, pos0 = 0;
     const LwCallPlan lw = sp_begin_call(sp, frames, &pos0);
+    if ((st = lv_begin_call(sp, frames, true)) != AW_OK) return st;
     if (cs == 0) {                       // one piece: H2D -> kernels -> D2H on the context's stream
         AW_HIP_TRY(hipMemcpyAsync(pcm_in, in, in_psb * sp->n_streams, hipMemcpyHostToDevice, c->stream));
         if (dec && (st = pcm_decode(sp, in_fmt, pcm_in, sp->d_stage_in, (int64_t)(in_ps * sp->n_streams))) != AW_OK) return st;
         st = sp_run_streams(sp, lw, 0, sp->n_streams, sp->d_stage_in, sp->d_stage_out, frames);
+        if (st == AW_OK) st = lv_after_run(sp, sp->d_stage_out, 0, sp->n_streams, frames, !enc);
         if (st != AW_OK) return st;
         sp->hist_cur ^= 1;
         if (enc && (st = pcm_encode(sp, out_fmt, sp->d_stage_out, pcm_out, (int64_t)(out_ps * sp->n_streams), sp->d_clip, 0, frames, pos0)) != AW_OK)
@@ -1689,6 +1790,7 @@ static aw_status host_process(aw_spatializer *sp, const void *in_v, int in_fmt, 
         if (he != hipSuccess) break;
         if (dec) st = pcm_decode(sp, in_fmt, d_in, f_in, (int64_t)ns * in_ps);
         if (st == AW_OK) st = sp_run_streams(sp, lw, (int)s0, ns, f_in, f_out, frames);
+        if (st == AW_OK) st = lv_after_run(sp, f_out, s0, ns, frames, !enc);
         if (st == AW_OK && enc) st = pcm_encode(sp, out_fmt, f_out, d_out, (int64_t)ns * out_ps, sp->d_clip, s0, frames, pos0);
         if (st != AW_OK) break;
         he = hipEventRecord(c->ev_run[slot], c->stream);
@@ -1757,6 +1859,7 @@ aw_status aw_spatializer_process_pcm(aw_spatializer *sp, const void *in_v, aw_sa
     unsigned long long *clip = reinterpret_cast<unsigned long long *>(clipped_device);
     uint64_t pos0 = 0;
     const LwCallPlan lw = sp_begin_call(sp, frames, &pos0);
+    if ((st = lv_begin_call(sp, frames, true)) != AW_OK) return st;
     for (int64_t s0 = 0; s0 < sp->n_streams; s0 += cs) {
         const int ns = (int)std::min<int64_t>(cs, sp->n_streams - s0);
         const unsigned char *src = in + (size_t)s0 * in_ps * in_b;
@@ -1765,6 +1868,7 @@ aw_status aw_spatializer_process_pcm(aw_spatializer *sp, const void *in_v, aw_sa
         float *f_out = enc ? sp->d_stage_out : reinterpret_cast<float *>(dst);
         if (dec && (st = pcm_decode(sp, in_fmt, src, sp->d_stage_in, (int64_t)ns * in_ps)) != AW_OK) return st;
         if ((st = sp_run_streams(sp, lw, (int)s0, ns, f_in, f_out, frames)) != AW_OK) return st;
+        if ((st = lv_after_run(sp, f_out, s0, ns, frames, !enc)) != AW_OK) return st;
         if (enc && (st = pcm_encode(sp, out_fmt, f_out, dst, (int64_t)ns * out_ps, clip, s0, frames, pos0)) != AW_OK) return st;
     }
     sp->hist_cur ^= 1;
@@ -1819,7 +1923,7 @@ aw_status aw_spatializer_process_planar(aw_spatializer *sp, const float *in_l, c
     AW_HIP_TRY(hipMemcpyAsync(d_il, in_l, sizeof(float) * frames, hipMemcpyHostToDevice, s));
     AW_HIP_TRY(hipMemcpyAsync(d_ir, in_r ? in_r : in_l, sizeof(float) * frames, hipMemcpyHostToDevice, s));   // mono dup, RealtimeAudioProcessor.swift:95-107
     AW_HIP_TRY(awk::launch_interleave2(d_il, d_ir, sp->d_stage_in, frames, s));
-    st = aw_spatializer_process(sp, sp->d_stage_in, sp->d_stage_out, frames);
+    st = process_device(sp, sp->d_stage_in, sp->d_stage_out, frames, /*metered=*/false);     // (the planar entry is neither metered nor gained)
     if (st != AW_OK) return st;
     AW_HIP_TRY(awk::launch_deinterleave2(sp->d_stage_out, d_ol, d_or, frames, s));
     AW_HIP_TRY(hipMemcpyAsync(out_l, d_ol, sizeof(float) * frames, hipMemcpyDeviceToHost, s));
@@ -1828,6 +1932,15 @@ aw_status aw_spatializer_process_planar(aw_spatializer *sp, const float *in_l, c
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 
+// the records start over (the setting stays)
+static aw_status lv_reset(aw_spatializer *sp) {
+    sp->h_levels = awl::Record{};
+    sp->metered_frames = 0;
+    sp->applied_mode = AW_GAIN_NONE;
+    if (sp->d_levels) AW_HIP_TRY(hipMemsetAsync(sp->d_levels, 0, (size_t)sp->n_streams * (sizeof(awl::Record) + sizeof(uint32_t)), sp->ctx->stream));
+    return AW_OK;
+}
+
 aw_status aw_spatializer_reset(aw_spatializer *sp) try {
     if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
     sp->position = 0;
@@ -1835,6 +1948,90 @@ aw_status aw_spatializer_reset(aw_spatializer *sp) try {
     const size_t n = (size_t)sp->n_streams * sp->hist_len * sp->n_channels;
     for (int i = 0; i < 2; ++i)
         AW_HIP_TRY(hipMemsetAsync(sp->d_hist[i], 0, std::max<size_t>(n, 1) * sizeof(float), sp->ctx->stream));
+    return lv_reset(sp);
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_spatializer_set_metering(aw_spatializer *sp, int32_t on) try {
+    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    if (on) {
+        AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+        std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+        const aw_status st = lv_buffers(sp);
+        if (st != AW_OK) return st;
+    }
+    sp->metering = on != 0;
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_spatializer_reset_levels(aw_spatializer *sp) try {
+    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    return lv_reset(sp);
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_spatializer_get_levels(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_levels *out) try {
+    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    if (first_stream < 0 || n < 0 || (int64_t)first_stream + n > sp->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "streams out of range");
+    if (n == 0) return AW_OK;
+    if (!out) return fail(AW_ERR_INVALID_ARGUMENT, "out_host is NULL");
+    if (!sp->d_levels) return fail(AW_ERR_INVALID_ARGUMENT, "no levels: neither aw_spatializer_set_metering nor aw_spatializer_set_gain has been called");
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
+    std::vector<awl::Record> rec((size_t)n);
+    std::vector<uint32_t> peaks((size_t)n);
+    AW_HIP_TRY(hipMemcpy(rec.data(), lv_records(sp) + first_stream, (size_t)n * sizeof(awl::Record), hipMemcpyDeviceToHost));
+    AW_HIP_TRY(hipMemcpy(peaks.data(), lv_call_peaks(sp) + first_stream, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int32_t i = 0; i < n; ++i) {
+        awl::Record r = rec[(size_t)i];
+        const int32_t s = first_stream + i;
+        if (s == 0) {                    // the single-stream path's share (a handle of one stream)
+            for (int e = 0; e < 2; ++e) { r.peak_bits[e] = std::max(r.peak_bits[e], sp->h_levels.peak_bits[e]); r.energy[e] += sp->h_levels.energy[e]; }
+            r.clipped += sp->h_levels.clipped;
+            r.nonfinite += sp->h_levels.nonfinite;
+        }
+        aw_stream_levels &o = out[i];
+        o.peak[0] = awl::bits_float(r.peak_bits[0]); o.peak[1] = awl::bits_float(r.peak_bits[1]);
+        o.gain = 1.0f;
+        if (sp->applied_mode == AW_GAIN_FIXED && (size_t)s < sp->applied_gains.size()) o.gain = sp->applied_gains[(size_t)s];
+        else if (sp->applied_mode == AW_GAIN_PEAK_CEILING)
+            o.gain = sp->applied_on_host ? sp->applied_host_gain : awl::auto_gain(awl::bits_float(peaks[(size_t)i]), sp->applied_ceiling);
+        o.reserved = 0;
+        o.energy[0] = r.energy[0]; o.energy[1] = r.energy[1];
+        o.frames = sp->metered_frames;
+        o.clipped = r.clipped;
+        o.nonfinite = r.nonfinite;
+    }
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+// Checks first, then the allocation and the upload (here, never on the process path); the setting changes only when all of it worked.
+aw_status aw_spatializer_set_gain(aw_spatializer *sp, aw_gain_mode mode, const float *gains_host, int32_t n, float ceiling) try {
+    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    if (mode != AW_GAIN_NONE && mode != AW_GAIN_FIXED && mode != AW_GAIN_PEAK_CEILING) return fail(AW_ERR_INVALID_ARGUMENT, "unknown gain mode");
+    if (mode == AW_GAIN_FIXED) {
+        if (!gains_host) return fail(AW_ERR_INVALID_ARGUMENT, "gains_host is NULL");
+        if (n != 1 && n != sp->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "n must be 1 or the stream count");
+        for (int32_t i = 0; i < n; ++i)
+            if (!std::isfinite(gains_host[i])) return fail(AW_ERR_INVALID_ARGUMENT, "gains must be finite");
+    }
+    if (mode == AW_GAIN_PEAK_CEILING && !(ceiling > 0.0f && ceiling <= 1.0f)) return fail(AW_ERR_INVALID_ARGUMENT, "ceiling must lie in (0, 1]");
+    if (mode == AW_GAIN_NONE) { sp->gain_mode = AW_GAIN_NONE; return AW_OK; }
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    const aw_status st = lv_buffers(sp);
+    if (st != AW_OK) return st;
+    if (mode == AW_GAIN_FIXED) {
+        std::vector<float> g((size_t)sp->n_streams);
+        for (int32_t s = 0; s < sp->n_streams; ++s) g[(size_t)s] = gains_host[n == 1 ? 0 : s];
+        // ordered behind whatever the context's stream still reads the old gains for
+        AW_HIP_TRY(hipMemcpyAsync(lv_gains(sp), g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice, sp->ctx->stream));
+        AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
+        sp->gains.swap(g);
+    } else {
+        sp->gain_ceiling = ceiling;
+    }
+    sp->gain_mode = mode;
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 

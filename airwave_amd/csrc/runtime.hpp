@@ -11,6 +11,7 @@
 
 #include "../../include/airwave_hip.h"
 #include "device/kernels.hpp"
+#include "device/levels.hpp"
 
 namespace awr {
 
@@ -122,6 +123,21 @@ struct aw_spatializer {
     int dither = 0;                               // aw_dither
     uint64_t dither_seed = 0, dither_first_stream = 0;
     uint64_t position = 0;
+    // level meter and output gain of the four batch entries (aw_spatializer_set_metering / _set_gain; rules: device/levels.hpp).  One
+    // device allocation, made by set_metering(1) or the first set_gain that is not NONE: [n_streams] awl::Record, then [n_streams] uint32
+    // call-local peaks (zeroed at the start of every call that runs the levels kernel), then [n_streams] float FIXED gains.
+    bool metering = false;
+    int gain_mode = 0;                            // aw_gain_mode
+    float gain_ceiling = 1.0f;
+    std::vector<float> gains;                     // FIXED: one per stream
+    unsigned char *d_levels = nullptr;
+    awl::Record h_levels{};                       // what the single-stream page-locked path metered on the CPU (added to stream 0's record on read)
+    uint64_t metered_frames = 0;                  // frames metered since reset_levels (the same for every stream)
+    // what the last batch call applied, for aw_stream_levels::gain
+    int applied_mode = 0;
+    float applied_ceiling = 1.0f, applied_host_gain = 1.0f;
+    bool applied_on_host = false;                 // PEAK_CEILING: the single-stream path computed it (applied_host_gain), else the call-local peaks hold it
+    std::vector<float> applied_gains;
     int64_t host_chunk_streams = 0;               // streams per staged chunk of the last host call (0: the whole batch in one piece, serial)
     int64_t host_chunk_reserved = 0, host_reserved_frames = 0;   // aw_spatializer_reserve_host: the chunking its buffers were sized for, and up to which call length
     // what the last aw_spatializer_reserve spent where (microseconds): float64 table build on host threads, table upload (hipMalloc +

@@ -204,6 +204,55 @@ enum {
     AW_DITHER_TPDF_HP = 2    /* triangular, high-pass (difference of consecutive uniforms) */
 };
 AW_API aw_status aw_spatializer_set_dither(aw_spatializer *sp, aw_dither mode, uint64_t seed, uint64_t first_stream);
+/* Per-stream output levels and gain of the four batch entries: aw_spatializer_process, _process_pcm, _process_host and
+ * _process_host_pcm.  An output ear is the sum of up to 14 convolutions, so output beyond full scale is the normal case; the meter
+ * tells a host which of its streams clipped and by how much, the gain prevents it, and neither moves float32 output over PCIe.  The
+ * planar entry and the engine / realtime adapters are neither metered nor gained.  With the meter off and the gain AW_GAIN_NONE
+ * (the defaults) every entry launches the kernels and writes the bytes it always has.
+ *  - the meter sees every float32 output sample y BEFORE the gain.  A y that is NaN or +-inf counts in nonfinite and in nothing else;
+ *    otherwise peak = max(peak, |y|) and energy += (double)y * (double)y, per ear.  The product is exact in double; the order of the
+ *    additions is unspecified, so energy may differ between runs by summation order (at most N * 2^-53 relative over N samples) while
+ *    every other field is exact.  clipped counts what the integer encodes of this stream clipped, after gain and dither.
+ *  - the gain multiplies once in float32: the gained sample is (float)(y * g), and the encode rules above (dither included) see that
+ *    value; float32 output is that value.
+ *  - AW_GAIN_PEAK_CEILING gives every stream, in every call, g = p > c ? c / p : 1, where p is the larger of the stream's two ear peaks
+ *    over THIS CALL's frames (non-finite samples excluded) and c / p is the correctly rounded float32 quotient.  It is per call: a host
+ *    that splits a file over calls in time should meter first (pass one), then set AW_GAIN_FIXED gains (pass two), or every call gets
+ *    a gain of its own.  A ceiling of exactly 1 can still clip by one LSB, through the rounding of the quotient or through dither.
+ *  - levels accumulate over every later batch call until aw_spatializer_reset_levels or aw_spatializer_reset.  Chunking a batch by
+ *    streams (AW_HOST_CHUNK_MB), sharding it over handles, pinned or pageable, aligned or unaligned buffers change no output bit and
+ *    no field but energy's summation order; splitting calls in time changes none either under AW_GAIN_NONE and AW_GAIN_FIXED.
+ *  - peak and energy are raw material: loudness in LUFS (K-weighting), true-peak oversampling, limiters and compressors are a host's
+ *    business and are not provided. */
+typedef struct aw_stream_levels {
+    float    peak[2];      /* max |y| per ear (left, right) over finite samples, before gain */
+    float    gain;         /* the gain the last call applied to this stream (1 if none) */
+    uint32_t reserved;     /* 0 */
+    double   energy[2];    /* sum of y^2 per ear, before gain */
+    uint64_t frames;       /* frames metered */
+    uint64_t clipped;      /* samples this stream's integer encodes clipped (after gain and dither) */
+    uint64_t nonfinite;    /* NaN / inf samples, both ears */
+} aw_stream_levels;        /* 56 bytes */
+typedef int32_t aw_gain_mode;
+enum {
+    AW_GAIN_NONE = 0,          /* no gain (the default) */
+    AW_GAIN_FIXED = 1,         /* one gain per stream, given by the host */
+    AW_GAIN_PEAK_CEILING = 2   /* per stream and call: scale down to the ceiling where the call's peak exceeds it */
+};
+/* on != 0: allocates the per-stream records at once (a later aw_spatializer_reserve / _reserve_pcm still means "no allocation on the
+ * process path") and meters every later batch call; 0: stops metering, the records stay readable.  Do not call these four setters while
+ * a process call on the same handle is running. */
+AW_API aw_status aw_spatializer_set_metering(aw_spatializer *sp, int32_t on);
+/* Synchronises the context's stream and copies the records of streams [first_stream, first_stream + n) to out_host.  A range outside the
+ * handle's streams returns AW_ERR_INVALID_ARGUMENT, as does a handle on which neither set_metering nor set_gain was ever called. */
+AW_API aw_status aw_spatializer_get_levels(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_levels *out_host);
+/* Zeroes every record (asynchronous on the context's stream); the meter and gain settings stay. */
+AW_API aw_status aw_spatializer_reset_levels(aw_spatializer *sp);
+/* AW_GAIN_NONE: gains_host, n and ceiling are ignored.  AW_GAIN_FIXED: n finite gains, n == 1 (every stream) or n == the stream count,
+ * uploaded by this call (never on the process path); ceiling is ignored.  AW_GAIN_PEAK_CEILING: 0 < ceiling <= 1; gains_host and n are
+ * ignored.  A NULL handle, an unknown mode, a bad n, a NaN / inf gain or a bad ceiling returns AW_ERR_INVALID_ARGUMENT before any HIP
+ * call, and the previous setting stays. */
+AW_API aw_status aw_spatializer_set_gain(aw_spatializer *sp, aw_gain_mode mode, const float *gains_host, int32_t n, float ceiling);
 /* StereoAudioProcessing.process shape (AudioPipeline.swift:3-11) for a 1-stream, 2-channel
  * spatializer: planar HOST buffers, input_right may be NULL (mono duplication). Zero latency. */
 AW_API aw_status aw_spatializer_process_planar(aw_spatializer *sp, const float *input_left, const float *input_right,
@@ -226,7 +275,8 @@ AW_API int32_t aw_spatializer_channel_count(const aw_spatializer *sp);
  * 10 / 11 / 12 microseconds the last aw_spatializer_reserve spent on the float64 table build (host threads) / the table upload /
  *   growing the context's scratch pool, 13 device or page-locked allocations and 14 blocking table uploads made so far on behalf
  *   of the context's handles (a reserved process path makes neither), 15 streams per staged chunk of the last host-entry call,
- * 18 frames processed since create / the last aw_spatializer_reset (the dither's frame position, aw_spatializer_set_dither). */
+ * 18 frames processed since create / the last aw_spatializer_reset (the dither's frame position, aw_spatializer_set_dither),
+ * 19 the level meter is on (aw_spatializer_set_metering), 20 the aw_gain_mode of the batch entries (aw_spatializer_set_gain). */
 AW_API int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what);
 /* Average device time of the dominant kernel over the launches since the last call (HIP events
  * on the context stream); used for bench.py's roofline object.  Returns launches counted. */

@@ -109,6 +109,17 @@ class Spatializer {
     }
     // TPDF dither of later s16 / s24 encodes (aw_dither); firstStream: the global index of this handle's stream 0
     void setDither(aw_dither mode, uint64_t seed = 0, uint64_t firstStream = 0) { check(aw_spatializer_set_dither(h_, mode, seed, firstStream)); }
+    // per-stream levels and gain of the batch entries (aw_stream_levels, aw_gain_mode)
+    void setMetering(bool on) { check(aw_spatializer_set_metering(h_, on ? 1 : 0)); }
+    std::vector<aw_stream_levels> levels() {
+        std::vector<aw_stream_levels> out((size_t)aw_spatializer_stream_count(h_));
+        check(aw_spatializer_get_levels(h_, 0, (int32_t)out.size(), out.data()));
+        return out;
+    }
+    void resetLevels() { check(aw_spatializer_reset_levels(h_)); }
+    void setGainNone() { check(aw_spatializer_set_gain(h_, AW_GAIN_NONE, nullptr, 0, 0.0f)); }
+    void setGainFixed(const std::vector<float> &gains) { check(aw_spatializer_set_gain(h_, AW_GAIN_FIXED, gains.data(), (int32_t)gains.size(), 0.0f)); }
+    void setGainPeakCeiling(float ceiling) { check(aw_spatializer_set_gain(h_, AW_GAIN_PEAK_CEILING, nullptr, 0, ceiling)); }
     int64_t info(int32_t what) const { return aw_spatializer_info(h_, what); }
     void reset() { check(aw_spatializer_reset(h_)); }
     aw_spatializer *get() const { return h_; }

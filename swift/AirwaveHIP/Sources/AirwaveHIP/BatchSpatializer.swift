@@ -95,6 +95,34 @@ public final class BatchSpatializer {
         guard st == AW_OK else { throw BatchSpatializer.error(st) }
     }
 
+    /// Per-stream level meter of every later batch call (`aw_spatializer_set_metering`); switching it on allocates the records here.
+    public func setMetering(_ on: Bool) throws {
+        let st = aw_spatializer_set_metering(handle, on ? 1 : 0)
+        guard st == AW_OK else { throw BatchSpatializer.error(st) }
+    }
+
+    /// The records of every stream (`aw_spatializer_get_levels`): peak and energy per ear before gain, the gain the last call applied,
+    /// frames metered, clipped and non-finite samples.  Synchronises the context's stream.
+    public func levels() throws -> [aw_stream_levels] {
+        let n = aw_spatializer_stream_count(handle)
+        var out = [aw_stream_levels](repeating: aw_stream_levels(), count: Int(n))
+        let st = out.withUnsafeMutableBufferPointer { aw_spatializer_get_levels(handle, 0, n, $0.baseAddress) }
+        guard st == AW_OK else { throw BatchSpatializer.error(st) }
+        return out
+    }
+
+    public func resetLevels() throws {
+        let st = aw_spatializer_reset_levels(handle)
+        guard st == AW_OK else { throw BatchSpatializer.error(st) }
+    }
+
+    /// Output gain of the batch entries (`aw_spatializer_set_gain`): `AW_GAIN_NONE`; `AW_GAIN_FIXED` with one gain or one per stream;
+    /// `AW_GAIN_PEAK_CEILING` with 0 < ceiling <= 1, per stream and per call.
+    public func setGain(_ mode: Int32, gains: [Float] = [], ceiling: Float = 0) throws {
+        let st = gains.withUnsafeBufferPointer { aw_spatializer_set_gain(handle, aw_gain_mode(mode), $0.baseAddress, Int32(gains.count), ceiling) }
+        guard st == AW_OK else { throw BatchSpatializer.error(st) }
+    }
+
     /// `reserve` plus the host entry's device-side staging: `process(hostInput:…)` never allocates afterwards either.
     public func reserveHost(maxFrames: Int64) throws {
         let st = aw_spatializer_reserve_host(handle, maxFrames)
