@@ -15,6 +15,8 @@
 // float32 output by its stream's gain in place; the gained encode (aw_pcm_encode_gain_kernel) is the encode pass with the group's gains
 // looked up the way its dither is, and with the clipped samples also counted per stream.  None of them runs, and the kernels above run as
 // they always have, while the meter is off and no gain is set.
+// One launcher serves the three encode kernels (launch_pcm_encode: a gain struct selects the gained kernel, a dither struct alone the
+// dithered one, neither the plain one); the batch entries' one chunk step calls it (runtime.cpp: batch_chunk).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -461,9 +463,9 @@ void encode_launch(dim3 grid, hipStream_t stream, const float *src, unsigned cha
         hipLaunchKernelGGL((aw_pcm_encode_dither_kernel<FMT, Q, MODE>), grid, dim3(kThreads), 0, stream, src, dst, n, head, n_body, clipped, dl);
 }
 
-template <int FMT, int MODE = awp::kDitherNone>
-hipError_t encode_fmt(const float *src, unsigned char *dst, int64_t n, unsigned long long *clipped, hipStream_t stream, const DitherLaunch &dl = {},
-                      const GainLaunch *gl = nullptr) {
+template <int FMT, int MODE>
+hipError_t encode_fmt(const float *src, unsigned char *dst, int64_t n, unsigned long long *clipped, hipStream_t stream, const DitherLaunch &dl,
+                      const GainLaunch *gl) {
     constexpr int G = Group<FMT>::G, BYTES = FMT == awp::kS24 ? 3 : FMT == awp::kS16 ? 2 : 4;
     if (reinterpret_cast<uintptr_t>(src) & 3u) return hipErrorInvalidValue;
     const int64_t head = head_to_align(reinterpret_cast<uintptr_t>(dst), BYTES, n);
@@ -495,34 +497,6 @@ hipError_t launch_pcm_decode(int fmt, const void *src, float *dst, int64_t n, hi
     }
 }
 
-hipError_t launch_pcm_encode(int fmt, const float *src, void *dst, int64_t n, unsigned long long *clipped, hipStream_t stream) {
-    if (n <= 0) return hipSuccess;
-    unsigned char *d = static_cast<unsigned char *>(dst);
-    switch (fmt) {
-        case awp::kS16: return encode_fmt<awp::kS16>(src, d, n, clipped, stream);
-        case awp::kS24: return encode_fmt<awp::kS24>(src, d, n, clipped, stream);
-        case awp::kS32: return encode_fmt<awp::kS32>(src, d, n, clipped, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_pcm_encode_dithered(int fmt, const PcmDither &dither, const float *src, void *dst, int64_t n, unsigned long long *clipped,
-                                      hipStream_t stream) {
-    if (dither.mode != awp::kDitherTpdf && dither.mode != awp::kDitherTpdfHp) return hipErrorInvalidValue;
-    if (dither.frames <= 0 || n < 0 || n % (2 * dither.frames)) return hipErrorInvalidValue;
-    if (n == 0) return hipSuccess;
-    unsigned char *d = static_cast<unsigned char *>(dst);
-    const DitherLaunch dl{dither.seed, dither.first_stream, dither.position, 2 * (uint64_t)dither.frames};
-    const int key = fmt * 4 + dither.mode;
-    switch (key) {
-        case awp::kS16 * 4 + awp::kDitherTpdf: return encode_fmt<awp::kS16, awp::kDitherTpdf>(src, d, n, clipped, stream, dl);
-        case awp::kS16 * 4 + awp::kDitherTpdfHp: return encode_fmt<awp::kS16, awp::kDitherTpdfHp>(src, d, n, clipped, stream, dl);
-        case awp::kS24 * 4 + awp::kDitherTpdf: return encode_fmt<awp::kS24, awp::kDitherTpdf>(src, d, n, clipped, stream, dl);
-        case awp::kS24 * 4 + awp::kDitherTpdfHp: return encode_fmt<awp::kS24, awp::kDitherTpdfHp>(src, d, n, clipped, stream, dl);
-        default: return hipErrorInvalidValue;
-    }
-}
-
 static GainLaunch gain_launch(const PcmGain &gain, int64_t frames) {
     return GainLaunch{gain.mode, gain.ceiling, gain.gain, gain.call_peak, gain.rec, 2 * (uint64_t)frames};
 }
@@ -532,22 +506,29 @@ static bool gain_ok(const PcmGain &gain) {
     return gain.mode == awl::kGainNone;
 }
 
-hipError_t launch_pcm_encode_gained(int fmt, const PcmDither &dither, const PcmGain &gain, const float *src, void *dst, int64_t n,
-                                    unsigned long long *clipped, hipStream_t stream) {
-    if (!gain_ok(gain) || dither.frames <= 0 || n < 0 || n % (2 * dither.frames)) return hipErrorInvalidValue;
-    if (n == 0) return hipSuccess;
+hipError_t launch_pcm_encode(int fmt, const float *src, void *dst, int64_t n, unsigned long long *clipped, const PcmDither *dither,
+                             const PcmGain *gain, hipStream_t stream) {
+    int mode = dither ? dither->mode : awp::kDitherNone;
+    if (gain) {
+        if (!dither || !gain_ok(*gain)) return hipErrorInvalidValue;
+        if (fmt == awp::kS32) mode = awp::kDitherNone;
+    } else if (dither && mode != awp::kDitherTpdf && mode != awp::kDitherTpdfHp) {
+        return hipErrorInvalidValue;
+    }
+    if (dither && (dither->frames <= 0 || n < 0 || n % (2 * dither->frames))) return hipErrorInvalidValue;
+    if (n <= 0) return hipSuccess;
     unsigned char *d = static_cast<unsigned char *>(dst);
-    const DitherLaunch dl{dither.seed, dither.first_stream, dither.position, 2 * (uint64_t)dither.frames};
-    const GainLaunch gl = gain_launch(gain, dither.frames);
-    const int mode = fmt == awp::kS32 ? awp::kDitherNone : dither.mode;
+    const DitherLaunch dl = dither ? DitherLaunch{dither->seed, dither->first_stream, dither->position, 2 * (uint64_t)dither->frames} : DitherLaunch{};
+    const GainLaunch gl = gain ? gain_launch(*gain, dither->frames) : GainLaunch{};
+    const GainLaunch *g = gain ? &gl : nullptr;
     switch (fmt * 4 + mode) {
-        case awp::kS16 * 4 + awp::kDitherNone: return encode_fmt<awp::kS16, awp::kDitherNone>(src, d, n, clipped, stream, dl, &gl);
-        case awp::kS16 * 4 + awp::kDitherTpdf: return encode_fmt<awp::kS16, awp::kDitherTpdf>(src, d, n, clipped, stream, dl, &gl);
-        case awp::kS16 * 4 + awp::kDitherTpdfHp: return encode_fmt<awp::kS16, awp::kDitherTpdfHp>(src, d, n, clipped, stream, dl, &gl);
-        case awp::kS24 * 4 + awp::kDitherNone: return encode_fmt<awp::kS24, awp::kDitherNone>(src, d, n, clipped, stream, dl, &gl);
-        case awp::kS24 * 4 + awp::kDitherTpdf: return encode_fmt<awp::kS24, awp::kDitherTpdf>(src, d, n, clipped, stream, dl, &gl);
-        case awp::kS24 * 4 + awp::kDitherTpdfHp: return encode_fmt<awp::kS24, awp::kDitherTpdfHp>(src, d, n, clipped, stream, dl, &gl);
-        case awp::kS32 * 4 + awp::kDitherNone: return encode_fmt<awp::kS32, awp::kDitherNone>(src, d, n, clipped, stream, dl, &gl);
+        case awp::kS16 * 4 + awp::kDitherNone: return encode_fmt<awp::kS16, awp::kDitherNone>(src, d, n, clipped, stream, dl, g);
+        case awp::kS16 * 4 + awp::kDitherTpdf: return encode_fmt<awp::kS16, awp::kDitherTpdf>(src, d, n, clipped, stream, dl, g);
+        case awp::kS16 * 4 + awp::kDitherTpdfHp: return encode_fmt<awp::kS16, awp::kDitherTpdfHp>(src, d, n, clipped, stream, dl, g);
+        case awp::kS24 * 4 + awp::kDitherNone: return encode_fmt<awp::kS24, awp::kDitherNone>(src, d, n, clipped, stream, dl, g);
+        case awp::kS24 * 4 + awp::kDitherTpdf: return encode_fmt<awp::kS24, awp::kDitherTpdf>(src, d, n, clipped, stream, dl, g);
+        case awp::kS24 * 4 + awp::kDitherTpdfHp: return encode_fmt<awp::kS24, awp::kDitherTpdfHp>(src, d, n, clipped, stream, dl, g);
+        case awp::kS32 * 4 + awp::kDitherNone: return encode_fmt<awp::kS32, awp::kDitherNone>(src, d, n, clipped, stream, dl, g);
         default: return hipErrorInvalidValue;
     }
 }

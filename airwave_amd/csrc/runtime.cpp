@@ -153,6 +153,21 @@ aw_status caught() noexcept {
 
 using awr::fail;
 
+// Grows one of the grow-only buffers to `need` elements of T (free, then allocate; nothing happens while the capacity suffices): device
+// memory, or — PINNED — page-locked host memory.  Every allocation counts in device_allocs.
+template <bool PINNED = false, typename T>
+static aw_status sp_grow(aw_spatializer *sp, T **buf, size_t *cap, size_t need) {
+    if (*cap >= need) return AW_OK;
+    if (*buf) AW_HIP_TRY(PINNED ? hipHostFree(*buf) : hipFree(*buf));
+    *buf = nullptr; *cap = 0;
+    void *p = nullptr;
+    AW_HIP_TRY(PINNED ? hipHostMalloc(&p, need * sizeof(T), hipHostMallocDefault) : hipMalloc(&p, need * sizeof(T)));
+    *buf = static_cast<T *>(p);
+    sp->ctx->device_allocs += 1;
+    *cap = need;
+    return AW_OK;
+}
+
 extern "C" {
 
 const char *aw_version(void) { return "airwave-hip 0.1 (gfx950)"; }
@@ -1282,26 +1297,6 @@ static aw_status sp_process_longwin(aw_spatializer *sp, const LwCallPlan &call, 
     return AW_OK;
 }
 
-static aw_status sp_grow(aw_spatializer *sp, float **buf, size_t *cap, size_t need) {
-    if (*cap >= need) return AW_OK;
-    if (*buf) AW_HIP_TRY(hipFree(*buf));
-    *buf = nullptr; *cap = 0;
-    AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(buf), need * sizeof(float)));
-    sp->ctx->device_allocs += 1;
-    *cap = need;
-    return AW_OK;
-}
-
-static aw_status sp_grow_pinned(aw_spatializer *sp, float **buf, size_t *cap, size_t need) {
-    if (*cap >= need) return AW_OK;
-    if (*buf) AW_HIP_TRY(hipHostFree(*buf));
-    *buf = nullptr; *cap = 0;
-    AW_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(buf), need * sizeof(float), hipHostMallocDefault));
-    sp->ctx->device_allocs += 1;
-    *cap = need;
-    return AW_OK;
-}
-
 // Callback-sized calls of a one-stream spatializer take the zero-copy staging (runtime.hpp) when aw_spatializer_reserve has made it;
 // longer calls move by DMA (a fused tile reads every input line about twice: not over PCIe).
 static constexpr int64_t kZeroCopyFrames = 16384;
@@ -1376,8 +1371,8 @@ aw_status aw_spatializer_reserve(aw_spatializer *sp, int64_t max_frames) try {
         if (st == AW_OK) st = sp_grow(sp, &sp->d_stage_out, &sp->stage_out_cap, (size_t)max_frames * 4);
         // callback-sized calls: page-locked staging the kernels address directly
         const size_t zf = (size_t)std::min<int64_t>(max_frames, kZeroCopyFrames);
-        if (st == AW_OK) st = sp_grow_pinned(sp, &sp->h_pin_in, &sp->pin_in_cap, zf * sp->n_channels);
-        if (st == AW_OK) st = sp_grow_pinned(sp, &sp->h_pin_out, &sp->pin_out_cap, zf * 2);
+        if (st == AW_OK) st = sp_grow<true>(sp, &sp->h_pin_in, &sp->pin_in_cap, zf * sp->n_channels);
+        if (st == AW_OK) st = sp_grow<true>(sp, &sp->h_pin_out, &sp->pin_out_cap, zf * 2);
         if (st != AW_OK) return st;
     }
     sp->reserved_frames = std::max<int64_t>(sp->reserved_frames, max_frames);
@@ -1503,32 +1498,14 @@ static float lv_host_call(aw_spatializer *sp, const float *y, size_t n) {
     return g;
 }
 
-// metered: a batch entry's call (metered and gained as the handle is set); the planar entry's inner call is not
-static aw_status process_device(aw_spatializer *sp, const float *in, float *out, int64_t frames, bool metered) {
-    if (!sp || !in || !out) return fail(AW_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (frames <= 0) return frames == 0 ? AW_OK : fail(AW_ERR_INVALID_ARGUMENT, "frames must be >= 0");
-    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
-    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);       // this call's launches stay together on the stream (the scratch pool is the context's)
-    const LwCallPlan lw = sp_begin_call(sp, frames);
-    aw_status st = metered ? lv_begin_call(sp, frames, true) : AW_OK;
-    if (st == AW_OK) st = sp_run_streams(sp, lw, 0, sp->n_streams, in, out, frames);
-    if (st == AW_OK && metered) st = lv_after_run(sp, out, 0, sp->n_streams, frames, true);
-    if (st != AW_OK) return st;
-    sp->hist_cur ^= 1;
-    return AW_OK;
-}
-
-aw_status aw_spatializer_process(aw_spatializer *sp, const float *in, float *out, int64_t frames) try {
-    return process_device(sp, in, out, frames, true);
-} AW_NOEXCEPT_TAIL
-
 /* ---- host entry ------------------------------------------------------------------------------------
  * The reference's callers hand over host buffers (AudioPipeline.swift:3-11: the four planar pointers of a render callback); an offline
  * batch host does too.  A multi-stream batch crosses PCIe in CHUNKS OF STREAMS (streams are independent: state is per stream), double
  * buffered on three HIP streams: H2D of chunk k+1 || kernels of chunk k || D2H of chunk k-1.  Page-locked caller buffers
  * (aw_host_alloc_pinned, hipHostMalloc, hipHostRegister) are read and written by the DMA engines directly; pageable ones are bounced
  * through page-locked chunks by the context's copy threads (below).  aw_spatializer_reserve_host() sizes the device-side chunk buffers
- * and the bounce chunks ahead of time; without it they grow on the first call. */
+ * and the bounce chunks ahead of time; without it they grow on the first call.  The kernels of a chunk are the batch entries' one chunk
+ * step (batch_chunk, below): the host entry adds the copies and the events around it. */
 // in_bytes: bytes per input sample (4 for float32; aw_spatializer_process_host_pcm: 2 / 3 / 4).  AW_HOST_CHUNK_MB counts input bytes as
 // they cross PCIe, so a 16-bit batch moves twice the streams per chunk of a float32 one.
 static int64_t host_chunk_streams(const aw_spatializer *sp, int64_t frames, size_t in_bytes = sizeof(float)) {
@@ -1568,26 +1545,6 @@ static aw_status host_pipeline_objects(aw_context *c) {
     return AW_OK;
 }
 
-static aw_status sp_grow_bytes(aw_spatializer *sp, unsigned char **buf, size_t *cap, size_t need) {
-    if (*cap >= need) return AW_OK;
-    if (*buf) AW_HIP_TRY(hipFree(*buf));
-    *buf = nullptr; *cap = 0;
-    AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(buf), need));
-    sp->ctx->device_allocs += 1;
-    *cap = need;
-    return AW_OK;
-}
-
-static aw_status sp_grow_pinned_bytes(aw_spatializer *sp, unsigned char **buf, size_t *cap, size_t need) {
-    if (*cap >= need) return AW_OK;
-    if (*buf) AW_HIP_TRY(hipHostFree(*buf));
-    *buf = nullptr; *cap = 0;
-    AW_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(buf), need, hipHostMallocDefault));
-    sp->ctx->device_allocs += 1;
-    *cap = need;
-    return AW_OK;
-}
-
 // the clipped-sample counter of the host entry (made once, with the first integer output)
 static aw_status sp_clip_counter(aw_spatializer *sp) {
     if (sp->d_clip) return AW_OK;
@@ -1606,11 +1563,11 @@ static aw_status host_stage_buffers(aw_spatializer *sp, int64_t frames, int64_t 
     const size_t in_b = (size_t)awp::format_bytes(in_fmt), out_b = (size_t)awp::format_bytes(out_fmt);
     aw_status st = sp_grow(sp, &sp->d_stage_in, &sp->stage_in_cap, in_n);
     if (st == AW_OK) st = sp_grow(sp, &sp->d_stage_out, &sp->stage_out_cap, out_n);
-    if (st == AW_OK && host && in_fmt != AW_SAMPLE_F32) st = sp_grow_bytes(sp, &sp->d_pcm_in, &sp->pcm_in_cap, in_n * in_b);
-    if (st == AW_OK && host && out_fmt != AW_SAMPLE_F32) st = sp_grow_bytes(sp, &sp->d_pcm_out, &sp->pcm_out_cap, out_n * out_b);
+    if (st == AW_OK && host && in_fmt != AW_SAMPLE_F32) st = sp_grow(sp, &sp->d_pcm_in, &sp->pcm_in_cap, in_n * in_b);
+    if (st == AW_OK && host && out_fmt != AW_SAMPLE_F32) st = sp_grow(sp, &sp->d_pcm_out, &sp->pcm_out_cap, out_n * out_b);
     if (st == AW_OK && host && out_fmt != AW_SAMPLE_F32) st = sp_clip_counter(sp);
-    if (st == AW_OK && host && cs > 0 && bounce_in) st = sp_grow_pinned_bytes(sp, &sp->h_bounce_in, &sp->bounce_in_cap, in_n * in_b);
-    if (st == AW_OK && host && cs > 0 && bounce_out) st = sp_grow_pinned_bytes(sp, &sp->h_bounce_out, &sp->bounce_out_cap, out_n * out_b);
+    if (st == AW_OK && host && cs > 0 && bounce_in) st = sp_grow<true>(sp, &sp->h_bounce_in, &sp->bounce_in_cap, in_n * in_b);
+    if (st == AW_OK && host && cs > 0 && bounce_out) st = sp_grow<true>(sp, &sp->h_bounce_out, &sp->bounce_out_cap, out_n * out_b);
     return st;
 }
 
@@ -1660,90 +1617,176 @@ static_assert(AW_DITHER_NONE == awp::kDitherNone && AW_DITHER_TPDF == awp::kDith
 static bool sp_dithers(const aw_spatializer *sp, int out_fmt) {
     return sp->dither != AW_DITHER_NONE && (out_fmt == AW_SAMPLE_S16 || out_fmt == AW_SAMPLE_S24);
 }
-// s0: the handle's index of the first of the n / (2 frames) streams encoded; pos: the call's first frame position (sp_begin_call)
-static aw_status pcm_encode(aw_spatializer *sp, int out_fmt, const float *src, void *dst, int64_t n, unsigned long long *clipped, int64_t s0,
-                            int64_t frames, uint64_t pos) {
+/* ---- one call plan, one chunk step: batch_args (argument prologue), then under the launch lock batch_formats + batch_begin (the plan),
+ * batch_chunk per chunk of streams (decode -> kernels -> meter / gain -> encode) and batch_end (the history flip).  The entries differ in
+ * where a chunk's bytes come from and go to; the single-stream page-locked calls run batch_run_pinned and convert on the CPU. */
+struct BatchCall {
+    int64_t frames;                         // (down to out_psb: batch_formats; the rest: batch_begin)
+    int in_fmt, out_fmt;
+    bool dec, enc;                          // an integer format on that side: the chunk step converts
+    size_t in_b, out_b;                     // bytes per sample
+    size_t in_ps, out_ps;                   // samples per stream
+    size_t in_psb, out_psb;                 // bytes per stream
+    LwCallPlan lw;                          // the call's kernel plan
+    uint64_t pos0;                          // position of the call's first frame: every encode of the call keys its dither on it
+    unsigned long long *clip;               // NULL, or the device counter this call's encodes add their clipped samples to
+    bool metered;                           // metered and gained as the handle is set (the planar entry's inner call is not)
+};
+
+// s0: the handle's index of the first of the ns streams encoded.  No dither and neither gain nor meter: the plain encode kernel, as ever.
+static aw_status pcm_encode(aw_spatializer *sp, const BatchCall &call, const float *src, void *dst, int64_t s0, int ns) {
     SpStageTimer tm(sp);
     if (sp->profiling) tm.begin();
-    if (lv_active(sp)) {                 // the gained / metered encode; the two below stay the ones launched without gain and meter
-        const awk::PcmDither d{sp_dithers(sp, out_fmt) ? sp->dither : awp::kDitherNone, sp->dither_seed, sp->dither_first_stream + (uint64_t)s0, pos, frames};
-        AW_HIP_TRY(awk::launch_pcm_encode_gained(out_fmt, d, lv_gain_launch(sp, s0), src, dst, n, clipped, sp->ctx->stream));
-    } else if (sp_dithers(sp, out_fmt)) {
-        const awk::PcmDither d{sp->dither, sp->dither_seed, sp->dither_first_stream + (uint64_t)s0, pos, frames};
-        AW_HIP_TRY(awk::launch_pcm_encode_dithered(out_fmt, d, src, dst, n, clipped, sp->ctx->stream));
-    } else {
-        AW_HIP_TRY(awk::launch_pcm_encode(out_fmt, src, dst, n, clipped, sp->ctx->stream));
-    }
+    const bool lv = lv_active(sp), dithers = sp_dithers(sp, call.out_fmt);
+    const awk::PcmDither d{dithers ? sp->dither : awp::kDitherNone, sp->dither_seed, sp->dither_first_stream + (uint64_t)s0, call.pos0, call.frames};
+    const awk::PcmGain g = lv ? lv_gain_launch(sp, s0) : awk::PcmGain{};
+    AW_HIP_TRY(awk::launch_pcm_encode(call.out_fmt, src, dst, (int64_t)ns * call.out_ps, call.clip, lv || dithers ? &d : nullptr, lv ? &g : nullptr,
+                                      sp->ctx->stream));
     if (sp->profiling) tm.end("aw_pcm_encode_kernel");
+    return AW_OK;
+}
+
+// The argument prologue of every batch entry, answered in this order: a NULL pointer, an unknown format, *zero_clipped = 0 (the host PCM
+// entry's count), frames < 0.  frames == 0 is AW_OK with *nothing set (the call is over); otherwise the context's device is made current.
+static aw_status batch_args(const aw_spatializer *sp, bool pointers, aw_sample_format in_fmt, aw_sample_format out_fmt, int64_t frames, bool *nothing,
+                            uint64_t *zero_clipped = nullptr, const char *negative = "frames must be >= 0") {
+    *nothing = true;
+    if (!sp || !pointers) return fail(AW_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!pcm_format_ok(in_fmt) || !pcm_format_ok(out_fmt)) return fail(AW_ERR_INVALID_ARGUMENT, "unknown sample format");
+    if (zero_clipped) *zero_clipped = 0;
+    if (frames <= 0) return frames == 0 ? AW_OK : fail(AW_ERR_INVALID_ARGUMENT, negative);
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    *nothing = false;
+    return AW_OK;
+}
+
+static BatchCall batch_formats(const aw_spatializer *sp, int64_t frames, int in_fmt, int out_fmt) {
+    BatchCall b{};
+    b.frames = frames; b.in_fmt = in_fmt; b.out_fmt = out_fmt;
+    b.dec = in_fmt != AW_SAMPLE_F32; b.enc = out_fmt != AW_SAMPLE_F32;
+    b.in_b = (size_t)awp::format_bytes(in_fmt); b.out_b = (size_t)awp::format_bytes(out_fmt);
+    b.in_ps = (size_t)frames * sp->n_channels; b.out_ps = (size_t)frames * 2;
+    b.in_psb = b.in_ps * b.in_b; b.out_psb = b.out_ps * b.out_b;
+    return b;
+}
+
+// Once per call, before its first launch.  The kernel plan comes first: the frame position moves past the call even if the call fails
+// later.  zero_clip: the counter is the handle's own (host entry) and starts the call at zero.
+static aw_status batch_begin(aw_spatializer *sp, BatchCall *call, unsigned long long *clip, bool zero_clip, bool metered) {
+    call->lw = sp_begin_call(sp, call->frames, &call->pos0);
+    call->clip = clip;
+    call->metered = metered;
+    if (metered) {
+        const aw_status st = lv_begin_call(sp, call->frames, true);
+        if (st != AW_OK) return st;
+    }
+    if (zero_clip) AW_HIP_TRY(hipMemsetAsync(clip, 0, sizeof(unsigned long long), sp->ctx->stream));
+    return AW_OK;
+}
+
+static void batch_end(aw_spatializer *sp) { sp->hist_cur ^= 1; }      // every chunk's kernels are queued: the history they wrote is the next call's
+
+// The streams [s0, s0 + ns) of a call, on the context's stream: pcm_src -> decode into f_in -> kernels -> meter / gain -> encode of f_out
+// into pcm_dst.  A float32 side has no conversion and no staging: the kernels read pcm_src / write pcm_dst, f_in / f_out is not looked at.
+static aw_status batch_chunk(aw_spatializer *sp, const BatchCall &call, int64_t s0, int ns, const void *pcm_src, float *f_in, float *f_out, void *pcm_dst) {
+    aw_status st = AW_OK;
+    if (call.dec) st = pcm_decode(sp, call.in_fmt, pcm_src, f_in, (int64_t)ns * call.in_ps);
+    const float *x = call.dec ? f_in : static_cast<const float *>(pcm_src);
+    float *y = call.enc ? f_out : static_cast<float *>(pcm_dst);
+    if (st == AW_OK) st = sp_run_streams(sp, call.lw, (int)s0, ns, x, y, call.frames);
+    if (st == AW_OK && call.metered) st = lv_after_run(sp, y, s0, ns, call.frames, !call.enc);
+    if (st == AW_OK && call.enc) st = pcm_encode(sp, call, y, pcm_dst, s0, ns);
+    return st;
+}
+
+// One stream, a callback's worth of frames (sp_zero_copy): the kernels read h_pin_in and write h_pin_out, page-locked host memory, over
+// PCIe, and the call is over when this returns.  metered: the host entry, which then meters, gains and encodes h_pin_out on the CPU.
+static aw_status batch_run_pinned(aw_spatializer *sp, int64_t frames, bool metered, uint64_t *pos0) {
+    const LwCallPlan lw = sp_begin_call(sp, frames, pos0);
+    aw_status st = metered ? lv_begin_call(sp, frames, false) : AW_OK;
+    if (st == AW_OK) st = sp_run_streams(sp, lw, 0, 1, sp->h_pin_in, sp->h_pin_out, frames);
+    if (st != AW_OK) return st;
+    batch_end(sp);
+    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
+    return AW_OK;
+}
+
+// The device entry; metered = false: the planar entry's inner call.
+static aw_status process_device(aw_spatializer *sp, const float *in, float *out, int64_t frames, bool metered) {
+    bool nothing;
+    aw_status st = batch_args(sp, in && out, AW_SAMPLE_F32, AW_SAMPLE_F32, frames, &nothing);
+    if (st != AW_OK || nothing) return st;
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);       // this call's launches stay together on the stream (the scratch pool is the context's)
+    BatchCall call = batch_formats(sp, frames, AW_SAMPLE_F32, AW_SAMPLE_F32);
+    st = batch_begin(sp, &call, nullptr, false, metered);
+    if (st == AW_OK) st = batch_chunk(sp, call, 0, sp->n_streams, in, nullptr, nullptr, out);
+    if (st == AW_OK) batch_end(sp);
+    return st;
+}
+
+aw_status aw_spatializer_process(aw_spatializer *sp, const float *in, float *out, int64_t frames) try {
+    return process_device(sp, in, out, frames, true);
+} AW_NOEXCEPT_TAIL
+
+// The host entry's single-stream page-locked call: the CPU converts on the way into and out of the staging (rules: pcm.hpp, levels.hpp).
+static aw_status host_process_pinned(aw_spatializer *sp, const BatchCall &call, const unsigned char *in, unsigned char *out, uint64_t *clipped) {
+    const int out_fmt = call.out_fmt;
+    const size_t out_b = call.out_b, out_ps = call.out_ps;
+    if (call.dec) for (size_t i = 0; i < call.in_ps; ++i) sp->h_pin_in[i] = awp::decode_at(call.in_fmt, in + i * call.in_b);
+    else std::memcpy(sp->h_pin_in, in, call.in_psb);
+    uint64_t pos0 = 0;
+    const aw_status st = batch_run_pinned(sp, call.frames, true, &pos0);
+    if (st != AW_OK) return st;
+    const bool lv = lv_active(sp);
+    const float gain = lv ? lv_host_call(sp, sp->h_pin_out, out_ps) : 1.0f;
+    if (call.enc) {
+        uint64_t n_clip = 0;
+        const int mode = sp_dithers(sp, out_fmt) ? sp->dither : awp::kDitherNone;
+        const uint64_t key = awp::dither_key(sp->dither_seed, sp->dither_first_stream);
+        for (size_t i = 0; i < out_ps; ++i) {
+            unsigned k = 0;
+            if (lv) awl::encode_gained_at(out_fmt, mode, sp->h_pin_out[i], gain, key, pos0 + i / 2, (int)(i & 1), out + i * out_b, &k);
+            else awp::encode_dithered_at(out_fmt, mode, sp->h_pin_out[i], key, pos0 + i / 2, (int)(i & 1), out + i * out_b, &k);
+            n_clip += k;
+        }
+        if (sp->metering) sp->h_levels.clipped += n_clip;
+        if (clipped) *clipped = n_clip;
+    } else if (sp->gain_mode != AW_GAIN_NONE) {
+        float *o = reinterpret_cast<float *>(out);
+        for (size_t i = 0; i < out_ps; ++i) o[i] = awl::apply_gain(sp->h_pin_out[i], gain);
+    } else {
+        std::memcpy(out, sp->h_pin_out, call.out_psb);
+    }
+    sp->host_chunk_streams = 0;
     return AW_OK;
 }
 
 // The host entry for every pair of sample formats.  float32 / float32 (aw_spatializer_process_host) moves the bytes, chunks and launches
 // it always has: the device PCM slots of float32 ARE the float staging, and neither conversion kernel runs.  Otherwise each chunk goes
-// H2D into its PCM slot -> decode into the float staging -> kernels -> encode into the PCM out slot -> D2H, the conversions on the
-// context's stream between the events that already order the slots (ev_run[slot] covers the PCM slots too).
+// H2D into its PCM slot -> batch_chunk (decode into the float staging -> kernels -> encode into the PCM out slot) -> D2H, the chunk step
+// on the context's stream between the events that already order the slots (ev_run[slot] covers the PCM slots too).
 static aw_status host_process(aw_spatializer *sp, const void *in_v, int in_fmt, void *out_v, int out_fmt, int64_t frames, uint64_t *clipped) {
     aw_context *c = sp->ctx;
     const unsigned char *in = static_cast<const unsigned char *>(in_v);
     unsigned char *out = static_cast<unsigned char *>(out_v);
-    const bool dec = in_fmt != AW_SAMPLE_F32, enc = out_fmt != AW_SAMPLE_F32;
-    const size_t in_b = (size_t)awp::format_bytes(in_fmt), out_b = (size_t)awp::format_bytes(out_fmt);
-    const size_t in_ps = (size_t)frames * sp->n_channels, out_ps = (size_t)frames * 2;          // samples per stream
-    const size_t in_psb = in_ps * in_b, out_psb = out_ps * out_b;                                // bytes per stream
-    if (sp_zero_copy(sp, frames)) {      // one stream, a callback's worth of frames: the kernels read and write page-locked host memory themselves
-        if (dec) for (size_t i = 0; i < in_ps; ++i) sp->h_pin_in[i] = awp::decode_at(in_fmt, in + i * in_b);     // (the CPU converts on the way)
-        else std::memcpy(sp->h_pin_in, in, in_psb);
-        uint64_t pos0 = 0;
-        const LwCallPlan lw0 = sp_begin_call(sp, frames, &pos0);
-        aw_status st0 = lv_begin_call(sp, frames, false);
-        if (st0 == AW_OK) st0 = sp_run_streams(sp, lw0, 0, 1, sp->h_pin_in, sp->h_pin_out, frames);
-        if (st0 != AW_OK) return st0;
-        sp->hist_cur ^= 1;
-        AW_HIP_TRY(hipStreamSynchronize(c->stream));
-        const bool lv = lv_active(sp);
-        const float gain = lv ? lv_host_call(sp, sp->h_pin_out, out_ps) : 1.0f;
-        if (enc) {
-            uint64_t n_clip = 0;
-            const int mode = sp_dithers(sp, out_fmt) ? sp->dither : awp::kDitherNone;
-            const uint64_t key = awp::dither_key(sp->dither_seed, sp->dither_first_stream);
-            for (size_t i = 0; i < out_ps; ++i) {
-                unsigned k = 0;
-                if (lv) awl::encode_gained_at(out_fmt, mode, sp->h_pin_out[i], gain, key, pos0 + i / 2, (int)(i & 1), out + i * out_b, &k);
-                else awp::encode_dithered_at(out_fmt, mode, sp->h_pin_out[i], key, pos0 + i / 2, (int)(i & 1), out + i * out_b, &k);
-                n_clip += k;
-            }
-            if (sp->metering) sp->h_levels.clipped += n_clip;
-            if (clipped) *clipped = n_clip;
-        } else if (sp->gain_mode != AW_GAIN_NONE) {
-            float *o = reinterpret_cast<float *>(out);
-            for (size_t i = 0; i < out_ps; ++i) o[i] = awl::apply_gain(sp->h_pin_out[i], gain);
-        } else {
-            std::memcpy(out, sp->h_pin_out, out_psb);
-        }
-        sp->host_chunk_streams = 0;
-        return AW_OK;
-    }
-    const int64_t cs = staged_chunk_streams(sp, frames, in_b);
+    BatchCall call = batch_formats(sp, frames, in_fmt, out_fmt);
+    if (sp_zero_copy(sp, frames)) return host_process_pinned(sp, call, in, out, clipped);
+    const bool enc = call.enc;
+    const size_t in_ps = call.in_ps, out_ps = call.out_ps, in_psb = call.in_psb, out_psb = call.out_psb;
+    const int64_t cs = staged_chunk_streams(sp, frames, call.in_b);
     const bool page_in = cs > 0 && !host_ptr_is_pinned(in), page_out = cs > 0 && !host_ptr_is_pinned(out);
     aw_status st = host_stage_buffers(sp, frames, cs, page_in, page_out, in_fmt, out_fmt);
     if (st == AW_OK && cs > 0) st = host_pipeline_objects(c);
     if (st != AW_OK) return st;
     sp->host_chunk_streams = cs;
-    unsigned char *pcm_in = dec ? sp->d_pcm_in : reinterpret_cast<unsigned char *>(sp->d_stage_in);
+    unsigned char *pcm_in = call.dec ? sp->d_pcm_in : reinterpret_cast<unsigned char *>(sp->d_stage_in);
     unsigned char *pcm_out = enc ? sp->d_pcm_out : reinterpret_cast<unsigned char *>(sp->d_stage_out);
-    if (enc) AW_HIP_TRY(hipMemsetAsync(sp->d_clip, 0, sizeof(unsigned long long), c->stream));
-    uint64_t n_clip = 0, pos0 = 0;
-    const LwCallPlan lw = sp_begin_call(sp, frames, &pos0);
-    if ((st = lv_begin_call(sp, frames, true)) != AW_OK) return st;
+    if ((st = batch_begin(sp, &call, enc ? sp->d_clip : nullptr, enc, true)) != AW_OK) return st;
+    uint64_t n_clip = 0;
     if (cs == 0) {                       // one piece: H2D -> kernels -> D2H on the context's stream
         AW_HIP_TRY(hipMemcpyAsync(pcm_in, in, in_psb * sp->n_streams, hipMemcpyHostToDevice, c->stream));
-        if (dec && (st = pcm_decode(sp, in_fmt, pcm_in, sp->d_stage_in, (int64_t)(in_ps * sp->n_streams))) != AW_OK) return st;
-        st = sp_run_streams(sp, lw, 0, sp->n_streams, sp->d_stage_in, sp->d_stage_out, frames);
-        if (st == AW_OK) st = lv_after_run(sp, sp->d_stage_out, 0, sp->n_streams, frames, !enc);
-        if (st != AW_OK) return st;
-        sp->hist_cur ^= 1;
-        if (enc && (st = pcm_encode(sp, out_fmt, sp->d_stage_out, pcm_out, (int64_t)(out_ps * sp->n_streams), sp->d_clip, 0, frames, pos0)) != AW_OK)
-            return st;
+        if ((st = batch_chunk(sp, call, 0, sp->n_streams, pcm_in, sp->d_stage_in, sp->d_stage_out, pcm_out)) != AW_OK) return st;
+        batch_end(sp);
         AW_HIP_TRY(hipMemcpyAsync(out, pcm_out, out_psb * sp->n_streams, hipMemcpyDeviceToHost, c->stream));
         if (enc) AW_HIP_TRY(hipMemcpyAsync(&n_clip, sp->d_clip, sizeof(n_clip), hipMemcpyDeviceToHost, c->stream));
         AW_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1788,11 +1831,7 @@ static aw_status host_process(aw_spatializer *sp, const void *in_v, int in_fmt, 
         if (he == hipSuccess) he = hipStreamWaitEvent(c->stream, c->ev_h2d[slot], 0);
         if (he == hipSuccess && k >= 2) he = hipStreamWaitEvent(c->stream, c->ev_d2h[slot], 0); // chunk k-2's output has left this device slot
         if (he != hipSuccess) break;
-        if (dec) st = pcm_decode(sp, in_fmt, d_in, f_in, (int64_t)ns * in_ps);
-        if (st == AW_OK) st = sp_run_streams(sp, lw, (int)s0, ns, f_in, f_out, frames);
-        if (st == AW_OK) st = lv_after_run(sp, f_out, s0, ns, frames, !enc);
-        if (st == AW_OK && enc) st = pcm_encode(sp, out_fmt, f_out, d_out, (int64_t)ns * out_ps, sp->d_clip, s0, frames, pos0);
-        if (st != AW_OK) break;
+        if ((st = batch_chunk(sp, call, s0, ns, d_in, f_in, f_out, d_out)) != AW_OK) break;
         he = hipEventRecord(c->ev_run[slot], c->stream);
         if (he == hipSuccess) he = hipStreamWaitEvent(c->s_d2h, c->ev_run[slot], 0);
         if (page_out) c->copy_pool_out->wait();          // chunk k-2's copy-out has left this bounce slot (it had a whole chunk's time)
@@ -1810,68 +1849,53 @@ static aw_status host_process(aw_spatializer *sp, const void *in_v, int in_fmt, 
     drain_prev((k - 1) & 1);             // the last chunk's output
     if (page_out) c->copy_pool_out->wait();
     AW_HIP_TRY(he);
-    sp->hist_cur ^= 1;
+    batch_end(sp);
     if (clipped) *clipped = n_clip;
     return AW_OK;
 }
 
 aw_status aw_spatializer_process_host(aw_spatializer *sp, const float *in, float *out, int64_t frames) try {
-    if (!sp || !in || !out) return fail(AW_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (frames <= 0) return frames == 0 ? AW_OK : fail(AW_ERR_INVALID_ARGUMENT, "frames must be >= 0");
-    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    bool nothing;
+    const aw_status st = batch_args(sp, in && out, AW_SAMPLE_F32, AW_SAMPLE_F32, frames, &nothing);
+    if (st != AW_OK || nothing) return st;
     std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
     return host_process(sp, in, AW_SAMPLE_F32, out, AW_SAMPLE_F32, frames, nullptr);
 } AW_NOEXCEPT_TAIL
 
 aw_status aw_spatializer_process_host_pcm(aw_spatializer *sp, const void *in, aw_sample_format in_format, void *out,
                                           aw_sample_format out_format, int64_t frames, uint64_t *clipped) try {
-    if (!sp || !in || !out) return fail(AW_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!pcm_format_ok(in_format) || !pcm_format_ok(out_format)) return fail(AW_ERR_INVALID_ARGUMENT, "unknown sample format");
-    if (clipped) *clipped = 0;
-    if (frames <= 0) return frames == 0 ? AW_OK : fail(AW_ERR_INVALID_ARGUMENT, "frames must be >= 0");
-    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    bool nothing;
+    const aw_status st = batch_args(sp, in && out, in_format, out_format, frames, &nothing, clipped);
+    if (st != AW_OK || nothing) return st;
     std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
     return host_process(sp, in, in_format, out, out_format, frames, clipped);
 } AW_NOEXCEPT_TAIL
 
 // Device buffers in any pair of formats: the call's streams go in chunks (the host entry's chunking, memory bounded by the chunk) through
-// the float staging on the context's stream — decode -> kernels -> encode straight into the caller's buffer.  One kernel choice for the
-// whole call (sp_begin_call once; the overlap-add tile decides on the call's block count), so the chunks give the bits an unchunked run
-// gives.  float32 / float32 is aw_spatializer_process itself.
+// the float staging — batch_chunk straight from and into the caller's buffers.  One kernel choice for the whole call (batch_begin once),
+// so the chunks give the bits an unchunked run gives.  float32 / float32 is aw_spatializer_process itself.
 aw_status aw_spatializer_process_pcm(aw_spatializer *sp, const void *in_v, aw_sample_format in_fmt, void *out_v, aw_sample_format out_fmt,
                                      int64_t frames, uint64_t *clipped_device) try {
-    if (!sp || !in_v || !out_v) return fail(AW_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!pcm_format_ok(in_fmt) || !pcm_format_ok(out_fmt)) return fail(AW_ERR_INVALID_ARGUMENT, "unknown sample format");
-    if (in_fmt == AW_SAMPLE_F32 && out_fmt == AW_SAMPLE_F32)
+    if (in_fmt == AW_SAMPLE_F32 && out_fmt == AW_SAMPLE_F32)   // (whose prologue answers what this one would)
         return aw_spatializer_process(sp, static_cast<const float *>(in_v), static_cast<float *>(out_v), frames);
-    if (frames <= 0) return frames == 0 ? AW_OK : fail(AW_ERR_INVALID_ARGUMENT, "frames must be >= 0");
-    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    bool nothing;
+    aw_status st = batch_args(sp, in_v && out_v, in_fmt, out_fmt, frames, &nothing);
+    if (st != AW_OK || nothing) return st;
     std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
     const unsigned char *in = static_cast<const unsigned char *>(in_v);
     unsigned char *out = static_cast<unsigned char *>(out_v);
-    const bool dec = in_fmt != AW_SAMPLE_F32, enc = out_fmt != AW_SAMPLE_F32;
-    const size_t in_b = (size_t)awp::format_bytes(in_fmt), out_b = (size_t)awp::format_bytes(out_fmt);
-    const size_t in_ps = (size_t)frames * sp->n_channels, out_ps = (size_t)frames * 2;
-    int64_t cs = staged_chunk_streams(sp, frames, in_b);
-    aw_status st = host_stage_buffers(sp, frames, cs, false, false, in_fmt, out_fmt, /*host=*/false);
+    BatchCall call = batch_formats(sp, frames, in_fmt, out_fmt);
+    int64_t cs = staged_chunk_streams(sp, frames, call.in_b);
+    st = host_stage_buffers(sp, frames, cs, false, false, in_fmt, out_fmt, /*host=*/false);
     if (st != AW_OK) return st;
     if (cs == 0) cs = sp->n_streams;
-    unsigned long long *clip = reinterpret_cast<unsigned long long *>(clipped_device);
-    uint64_t pos0 = 0;
-    const LwCallPlan lw = sp_begin_call(sp, frames, &pos0);
-    if ((st = lv_begin_call(sp, frames, true)) != AW_OK) return st;
+    if ((st = batch_begin(sp, &call, reinterpret_cast<unsigned long long *>(clipped_device), false, true)) != AW_OK) return st;
     for (int64_t s0 = 0; s0 < sp->n_streams; s0 += cs) {
         const int ns = (int)std::min<int64_t>(cs, sp->n_streams - s0);
-        const unsigned char *src = in + (size_t)s0 * in_ps * in_b;
-        unsigned char *dst = out + (size_t)s0 * out_ps * out_b;
-        const float *f_in = dec ? sp->d_stage_in : reinterpret_cast<const float *>(src);
-        float *f_out = enc ? sp->d_stage_out : reinterpret_cast<float *>(dst);
-        if (dec && (st = pcm_decode(sp, in_fmt, src, sp->d_stage_in, (int64_t)ns * in_ps)) != AW_OK) return st;
-        if ((st = sp_run_streams(sp, lw, (int)s0, ns, f_in, f_out, frames)) != AW_OK) return st;
-        if ((st = lv_after_run(sp, f_out, s0, ns, frames, !enc)) != AW_OK) return st;
-        if (enc && (st = pcm_encode(sp, out_fmt, f_out, dst, (int64_t)ns * out_ps, clip, s0, frames, pos0)) != AW_OK) return st;
+        const unsigned char *src = in + (size_t)s0 * call.in_psb;
+        if ((st = batch_chunk(sp, call, s0, ns, src, sp->d_stage_in, sp->d_stage_out, out + (size_t)s0 * call.out_psb)) != AW_OK) return st;
     }
-    sp->hist_cur ^= 1;
+    batch_end(sp);
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 
@@ -1894,8 +1918,9 @@ aw_status aw_spatializer_process_planar(aw_spatializer *sp, const float *in_l, c
     if (!sp || !in_l || !out_l || !out_r) return fail(AW_ERR_INVALID_ARGUMENT, "NULL argument");
     if (sp->n_streams != 1 || sp->n_channels != 2)
         return fail(AW_ERR_INVALID_ARGUMENT, "planar entry needs a 1-stream, 2-channel spatializer");
-    if (frames <= 0) return frames == 0 ? AW_OK : fail(AW_ERR_INVALID_ARGUMENT, "frameCount must be >= 0");
-    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    bool nothing;
+    aw_status st = batch_args(sp, true, AW_SAMPLE_F32, AW_SAMPLE_F32, frames, &nothing, nullptr, "frameCount must be >= 0");
+    if (st != AW_OK || nothing) return st;
     hipStream_t s = sp->ctx->stream;
     if (sp_zero_copy(sp, frames)) {
         // The render-callback shape (AudioPipeline.swift:3-11).  Interleave on the way into the page-locked staging (mono duplication,
@@ -1905,17 +1930,13 @@ aw_status aw_spatializer_process_planar(aw_spatializer *sp, const float *in_l, c
         const float *r_src = in_r ? in_r : in_l;
         float *pi = sp->h_pin_in;
         for (int i = 0; i < frames; ++i) { pi[2 * (size_t)i] = in_l[i]; pi[2 * (size_t)i + 1] = r_src[i]; }
-        const LwCallPlan lw0 = sp_begin_call(sp, frames);
-        aw_status st0 = sp_run_streams(sp, lw0, 0, 1, sp->h_pin_in, sp->h_pin_out, frames);
-        if (st0 != AW_OK) return st0;
-        sp->hist_cur ^= 1;
-        AW_HIP_TRY(hipStreamSynchronize(s));
+        if ((st = batch_run_pinned(sp, frames, /*metered=*/false, nullptr)) != AW_OK) return st;
         const float *po = sp->h_pin_out;
         for (int i = 0; i < frames; ++i) { out_l[i] = po[2 * (size_t)i]; out_r[i] = po[2 * (size_t)i + 1]; }
         return AW_OK;
     }
     // staging layout: [in interleaved 2F | planar L F | planar R F] and [out interleaved 2F | L F | R F]
-    aw_status st = sp_grow(sp, &sp->d_stage_in, &sp->stage_in_cap, (size_t)frames * 4);
+    st = sp_grow(sp, &sp->d_stage_in, &sp->stage_in_cap, (size_t)frames * 4);
     if (st == AW_OK) st = sp_grow(sp, &sp->d_stage_out, &sp->stage_out_cap, (size_t)frames * 4);
     if (st != AW_OK) return st;
     float *d_il = sp->d_stage_in + 2 * (size_t)frames, *d_ir = d_il + frames;

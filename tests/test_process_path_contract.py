@@ -26,7 +26,8 @@ def test_no_environment_lookups_on_process_paths():
     rt = open(os.path.join(ROOT, "airwave_amd", "csrc", "runtime.cpp")).read()
     for fn in ("sp_process_fused", "sp_process_partitioned", "sp_process_longwin", "sp_run_streams", "sp_begin_call", "aw_spatializer_process",
                "aw_spatializer_process_host", "aw_spatializer_process_planar", "aw_realtime_process", "aw_engine_process", "part_plan",
-               "part_ensure_scratch", "host_chunk_streams", "host_stage_buffers", "aw_spatializer_reserve", "aw_spatializer_reserve_host"):
+               "part_ensure_scratch", "host_chunk_streams", "host_stage_buffers", "aw_spatializer_reserve", "aw_spatializer_reserve_host",
+               "batch_args", "batch_formats", "batch_begin", "batch_chunk", "batch_run_pinned", "host_process_pinned"):
         assert "getenv" not in _body(rt, fn), fn
     eq = open(os.path.join(ROOT, "airwave_amd", "csrc", "eq_runtime.cpp")).read()
     assert "getenv" not in eq
