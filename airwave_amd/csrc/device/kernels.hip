@@ -110,22 +110,6 @@ __global__ void __launch_bounds__(kThreads) aw_part_inverse_kernel(TileParams p,
 // (real channels, batches): 2C pseudo-channels in batches of four
 #define AW_FOR_EACH_VEC2(X) X(1, 1) X(2, 1) X(3, 2) X(5, 3) X(7, 4)      // 4, 6 and 8 channels live in ols2_even_kernels.hip (SLP on)
 
-const char *fused_ols2_kernel_name(int C) {
-    switch (C) {
-        case 1: return "aw_fused_ols2_kernel<1, 1, true>";
-        case 2: return "aw_fused_ols2_kernel<2, 1, true>";
-        case 3: return "aw_fused_ols2_kernel<3, 2, true>";
-        case 4: return "aw_fused_ols2_kernel<4, 2, true>";
-        case 5: return "aw_fused_ols2_kernel<5, 3, true>";
-        case 6: return "aw_fused_ols2_kernel<6, 3, true>";
-        case 7: return "aw_fused_ols2_kernel<7, 4, true>";
-        case 8: return "aw_fused_ols2_kernel<8, 4, true>";
-        default: return "aw_fused_ols2_kernel<0, 0, false>";
-    }
-}
-static bool has_vec2_variant(int C) { return C >= 1 && C <= 8; }
-static bool ols2_slp_layout(int C) { return C == 4 || C == 6 || C == 8; }      // built in ols2_even_kernels.hip
-
 // Kernel variants.  Vectorised interior kernels <CS, NP, true> exist for 2-16 channels (frames that are not whole float4s are
 // loaded 16 B per lane at dword alignment, zero tables cancel the lanes that run into the next frame; 9-14 channels in one
 // pass over two eight-channel groups, 15-16 in two passes); the boundary tiles of every layout, and mono, run the
@@ -142,135 +126,114 @@ static bool ols2_slp_layout(int C) { return C == 4 || C == 6 || C == 8; }      /
 // boundary tiles of the common layouts keep whole-frame vector loads (history / zero-page selects per frame)
 #define AW_FOR_EACH_BVEC(X) X(2, 1) X(4, 2) X(8, 4)
 
-hipError_t prepare_kernels(LaunchCfg *cfg) {
-    hipError_t e = hipSuccess;
-    if (cfg) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) {
-            cfg->cus = cus;
-            cfg->persistent_wgs = cus;            // one resident workgroup per CU (152 KB LDS each)
-        }
-        int &g_persistent_wgs = cfg->persistent_wgs;
-        if (const char *e2 = getenv("AW_PERSISTENT_WGS")) g_persistent_wgs = atoi(e2) > 0 ? atoi(e2) : g_persistent_wgs;
-        // the persistent kernels deal tiles to 8 XCD groups (blockIdx % 8): a grid below 8 workgroups with more tiles than
-        // workgroups would leave groups without a workgroup and their tiles uncomputed
-        if (g_persistent_wgs < 8) g_persistent_wgs = 8;
-        if (const char *e3 = getenv("AW_WIDE_TWO_PASS")) cfg->wide_two_pass = atoi(e3) != 0;      // A/B: 1 = two passes, 0 = run-time loop
-        cfg->debug_occupancy = getenv("AW_DEBUG_OCCUPANCY") != nullptr;
-        if (const char *e5 = getenv("AW_STAMP_THREAD")) cfg->stamp_thread = atoi(e5);
-        if (const char *e6 = getenv("AW_EQ_EAR_SPLIT")) cfg->eq_ear_split = atoi(e6);
-        if (const char *e7 = getenv("AW_LW_ROWS_PB")) cfg->lw_rows_pb = atoi(e7) == 2 ? 2 : 1;
-        if (const char *e8 = getenv("AW_HOP_ALIGN")) cfg->hop_align = atoi(e8);
-        if (const char *e9 = getenv("AW_LW_ROWS_FORM")) cfg->lw_rows_form = atoi(e9) == 8 ? 8 : 16;
-        if (const char *e10 = getenv("AW_LW_ROWS16_WGS")) cfg->lw_rows16_wgs = atoi(e10) >= 1 && atoi(e10) <= 4 ? atoi(e10) : cfg->lw_rows16_wgs;
-        if (const char *e12 = getenv("AW_LW_TABLES")) cfg->lw_tables_on_gpu = std::strcmp(e12, "host") == 0 ? 0 : 1;
-        if (const char *e13 = getenv("AW_OLA_MIN_BLOCKS")) cfg->ola_min_blocks_per_wg = atoi(e13) >= 0 ? atoi(e13) : cfg->ola_min_blocks_per_wg;
-        if (const char *e14 = getenv("AW_HOST_OUT_ASYNC")) cfg->host_out_async = atoi(e14) != 0;
-        if (const char *e11 = getenv("AW_HOST_CHUNK_MB")) cfg->host_chunk_mb = atoi(e11) >= 1 ? atoi(e11) : cfg->host_chunk_mb;
-    }
-#define AW_SET_VEC(CS, NP)                                                                           \
-    if (e == hipSuccess)                                                                             \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_fused_ols_kernel<CS, NP, true>),  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-#define AW_SET_GEN(NP)                                                                               \
-    if (e == hipSuccess)                                                                             \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_fused_ols_kernel<0, NP, false>),  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-#define AW_SET_BVEC(CS, NP)                                                                          \
-    if (e == hipSuccess)                                                                             \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_fused_ols_kernel<CS, NP, false>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    AW_FOR_EACH_VEC(AW_SET_VEC)
-#define AW_SET_WIDE(CS, NPA, NPB)                                                                              \
-    if (e == hipSuccess)                                                                                       \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_fused_ols_kernel<CS, NPA, true, false>),    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);                        \
-    if (e == hipSuccess)                                                                                       \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_fused_ols_kernel<CS, NPB, true, true>),     \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    AW_FOR_EACH_WIDE(AW_SET_WIDE)
-#undef AW_SET_WIDE
-    AW_FOR_EACH_WIDE1(AW_SET_VEC)
-#define AW_SET_GENACC(NP)                                                                                      \
-    if (e == hipSuccess)                                                                                       \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_fused_ols_kernel<0, NP, false, true>),      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    AW_SET_GENACC(1) AW_SET_GENACC(2) AW_SET_GENACC(3) AW_SET_GENACC(4)
-#undef AW_SET_GENACC
-    AW_FOR_EACH_GEN(AW_SET_GEN)
-    AW_FOR_EACH_BVEC(AW_SET_BVEC)
-#define AW_SET_VEC2(CS, NB)                                                                          \
-    if (e == hipSuccess)                                                                             \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_fused_ols2_kernel<CS, NB, true>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    AW_FOR_EACH_VEC2(AW_SET_VEC2)
-#undef AW_SET_VEC2
-#define AW_SET_BVEC2(CS, NB)                                                                          \
-    if (e == hipSuccess)                                                                              \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_fused_ols2_kernel<CS, NB, false>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    AW_FOR_EACH_VEC2(AW_SET_BVEC2)
-#undef AW_SET_BVEC2
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_fused_ols2_kernel<0, 0, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+// The launch tables (launch_table.hpp): one row per instantiation, built from the lists above.  Keys: channels, or pairs for the
+// generic kernels; 4 channels + MODE for the partitioned path's forward kernels, whose names are their StageTimer stage names.
+#define AW_ROW(CS, NP) {CS, &aw_fused_ols_kernel<CS, NP, true>, kLdsBytes, "aw_fused_ols_kernel<" #CS ", " #NP ", true>"},
+static const TileEntry kVec[] = {AW_FOR_EACH_VEC(AW_ROW)};
+static const TileEntry kWide1[] = {AW_FOR_EACH_WIDE1(AW_ROW)};
+#undef AW_ROW
+#define AW_ROW(CS, NPA, NPB) {CS, &aw_fused_ols_kernel<CS, NPA, true, false>, kLdsBytes, "aw_fused_ols_kernel<" #CS ", " #NPA ", true>"},
+static const TileEntry kWideFirst[] = {AW_FOR_EACH_WIDE(AW_ROW)};
+#undef AW_ROW
+#define AW_ROW(CS, NPA, NPB) {CS, &aw_fused_ols_kernel<CS, NPB, true, true>, kLdsBytes, "aw_fused_ols_kernel<" #CS ", " #NPB ", true, accumulate>"},
+static const TileEntry kWideSecond[] = {AW_FOR_EACH_WIDE(AW_ROW)};
+#undef AW_ROW
+#define AW_ROW(CS, NP) {CS, &aw_fused_ols_kernel<CS, NP, false>, kLdsBytes, "aw_fused_ols_kernel<" #CS ", " #NP ", false>"},
+static const TileEntry kBvec[] = {AW_FOR_EACH_BVEC(AW_ROW)};
+#undef AW_ROW
+#define AW_ROW(NP) {NP, &aw_fused_ols_kernel<0, NP, false>, kLdsBytes, "aw_fused_ols_kernel<0, " #NP ", false>"},
+static const TileEntry kGen[] = {AW_FOR_EACH_GEN(AW_ROW)};
+#undef AW_ROW
+#define AW_ROW(NP) {NP, &aw_fused_ols_kernel<0, NP, false, true>, kLdsBytes, "aw_fused_ols_kernel<0, " #NP ", false, accumulate>"},
+static const TileEntry kGenAcc[] = {AW_ROW(1) AW_ROW(2) AW_ROW(3) AW_ROW(4)};      // second pass of 9-16 channels: the pairs beyond the first four
+#undef AW_ROW
+#define AW_ROW(CS, NB) {CS, &aw_fused_ols2_kernel<CS, NB, true>, kLdsBytes, "aw_fused_ols2_kernel<" #CS ", " #NB ", true>"},
+static const TileEntry kVec2[] = {AW_FOR_EACH_VEC2(AW_ROW)};
+#undef AW_ROW
+#define AW_ROW(CS, NB) {CS, &aw_fused_ols2_kernel<CS, NB, false>, kLdsBytes, "aw_fused_ols2_kernel<" #CS ", " #NB ", false>"},
+static const TileEntry kBnd2[] = {AW_FOR_EACH_VEC2(AW_ROW) {0, &aw_fused_ols2_kernel<0, 0, false>, kLdsBytes, "aw_fused_ols2_kernel<0, 0, false>"}};
+#undef AW_ROW
+using FwdEntry = KernelEntry<TileParams, long long, int>;
+#define AW_ROW(CS, NP)                                                                                         \
+    {4 * CS + 1, &aw_part_forward_kernel<CS, 1>, kLdsBytes, "aw_part_forward_kernel<CS, interior>"},           \
+    {4 * CS + 2, &aw_part_forward_kernel<CS, 2>, kLdsBytes, "aw_part_forward_kernel<CS, head>"},
+static const FwdEntry kFwd[] = {AW_FOR_EACH_VEC(AW_ROW) {0, &aw_part_forward_kernel<0, 0>, kLdsBytes, "aw_part_forward_kernel<generic>"}};
+#undef AW_ROW
+#define AW_ROW(CS, NP)                                                                                         \
+    {4 * CS + 1, &aw_part_forward1_kernel<CS, 1>, kInvLdsBytes, "aw_part_forward1_kernel<CS, interior>"},      \
+    {4 * CS + 2, &aw_part_forward1_kernel<CS, 2>, kInvLdsBytes, "aw_part_forward1_kernel<CS, head>"},
+static const FwdEntry kFwd1[] = {AW_FOR_EACH_VEC(AW_ROW) {0, &aw_part_forward1_kernel<0, 0>, kInvLdsBytes, "aw_part_forward1_kernel<generic>"}};
+#undef AW_ROW
+
+// the 16384-frame tile of a layout: the even layouts' table first (ols2_even_kernels.hip), then this unit's
+static const TileEntry *find_ols2(int C, bool interior) {
+    if (const TileEntry *k = find_ols2_even(C, interior)) return k;
+    return interior ? find(kVec2, C) : find(kBnd2, C);
+}
+const char *fused_ols2_kernel_name(int C) {
+    const TileEntry *k = find_ols2(C, true);
+    return k ? k->name : find(kBnd2, 0)->name;
+}
+
+// the dynamic-LDS attribute of every tile kernel of this unit and of ols2_even_kernels.hip
+static hipError_t set_tile_kernel_lds() {
+    hipError_t e = set_dynamic_lds(kVec);
+    if (e == hipSuccess) e = set_dynamic_lds(kWideFirst);
+    if (e == hipSuccess) e = set_dynamic_lds(kWideSecond);
+    if (e == hipSuccess) e = set_dynamic_lds(kWide1);
+    if (e == hipSuccess) e = set_dynamic_lds(kGenAcc);
+    if (e == hipSuccess) e = set_dynamic_lds(kGen);
+    if (e == hipSuccess) e = set_dynamic_lds(kBvec);
+    if (e == hipSuccess) e = set_dynamic_lds(kVec2);
+    if (e == hipSuccess) e = set_dynamic_lds(kBnd2);
     if (e == hipSuccess) e = prepare_ols2_even();
-#undef AW_SET_BVEC
-#undef AW_SET_VEC
-#undef AW_SET_GEN
-#define AW_SET_FWD(CS, NP)                                                                              \
-    if (e == hipSuccess)                                                                                \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_part_forward_kernel<CS, 1>),         \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);                 \
-    if (e == hipSuccess)                                                                                \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_part_forward_kernel<CS, 2>),         \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    AW_FOR_EACH_VEC(AW_SET_FWD)
-#undef AW_SET_FWD
-#define AW_SET_FWD1(CS, NP)                                                                             \
-    if (e == hipSuccess)                                                                                \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_part_forward1_kernel<CS, 1>),        \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kInvLdsBytes);              \
-    if (e == hipSuccess)                                                                                \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_part_forward1_kernel<CS, 2>),        \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kInvLdsBytes);
-    AW_FOR_EACH_VEC(AW_SET_FWD1)
-#undef AW_SET_FWD1
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_part_forward1_kernel<0, 0>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kInvLdsBytes);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_part_forward_kernel<0, 0>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+    if (e == hipSuccess) e = set_dynamic_lds(kFwd);
+    if (e == hipSuccess) e = set_dynamic_lds(kFwd1);
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_part_inverse_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, kInvLdsBytes);
     return e;
 }
 
-static bool has_vec_variant(int C) { return (C >= 2 && C <= 8) || C == 12 || C == 14 || C == 16; }
-static bool has_fused_vec_variant(int C) { return has_vec_variant(C) || (C >= 9 && C <= 15); }       // 9, 10, 11, 13, 15 channels: the fused kernels only
+// The device query and the AW_* knobs of a context, then the kernels' attributes: the one place of the device code that reads the environment.
+hipError_t prepare_kernels(LaunchCfg *cfg) {
+    if (!cfg) return set_tile_kernel_lds();
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) {
+        cfg->cus = cus;
+        cfg->persistent_wgs = cus;            // one resident workgroup per CU (152 KB LDS each)
+    }
+    int &g_persistent_wgs = cfg->persistent_wgs;
+    if (const char *e2 = getenv("AW_PERSISTENT_WGS")) g_persistent_wgs = atoi(e2) > 0 ? atoi(e2) : g_persistent_wgs;
+    // the persistent kernels deal tiles to 8 XCD groups (blockIdx % 8): a grid below 8 workgroups with more tiles than
+    // workgroups would leave groups without a workgroup and their tiles uncomputed
+    if (g_persistent_wgs < 8) g_persistent_wgs = 8;
+    if (const char *e3 = getenv("AW_WIDE_TWO_PASS")) cfg->wide_two_pass = atoi(e3) != 0;      // A/B: 1 = two passes, 0 = run-time loop
+    cfg->debug_occupancy = getenv("AW_DEBUG_OCCUPANCY") != nullptr;
+    if (const char *e5 = getenv("AW_STAMP_THREAD")) cfg->stamp_thread = atoi(e5);
+    if (const char *e6 = getenv("AW_EQ_EAR_SPLIT")) cfg->eq_ear_split = atoi(e6);
+    if (const char *e7 = getenv("AW_LW_ROWS_PB")) cfg->lw_rows_pb = atoi(e7) == 2 ? 2 : 1;
+    if (const char *e8 = getenv("AW_HOP_ALIGN")) cfg->hop_align = atoi(e8);
+    if (const char *e9 = getenv("AW_LW_ROWS_FORM")) cfg->lw_rows_form = atoi(e9) == 8 ? 8 : 16;
+    if (const char *e10 = getenv("AW_LW_ROWS16_WGS")) cfg->lw_rows16_wgs = atoi(e10) >= 1 && atoi(e10) <= 4 ? atoi(e10) : cfg->lw_rows16_wgs;
+    if (const char *e12 = getenv("AW_LW_TABLES")) cfg->lw_tables_on_gpu = std::strcmp(e12, "host") == 0 ? 0 : 1;
+    if (const char *e13 = getenv("AW_OLA_MIN_BLOCKS")) cfg->ola_min_blocks_per_wg = atoi(e13) >= 0 ? atoi(e13) : cfg->ola_min_blocks_per_wg;
+    if (const char *e14 = getenv("AW_HOST_OUT_ASYNC")) cfg->host_out_async = atoi(e14) != 0;
+    if (const char *e11 = getenv("AW_HOST_CHUNK_MB")) cfg->host_chunk_mb = atoi(e11) >= 1 ? atoi(e11) : cfg->host_chunk_mb;
+    return set_tile_kernel_lds();
+}
+
+static bool has_vec_variant(int C) { return find(kVec, C) != nullptr; }
+// 9, 10, 11, 13, 15 channels: the fused kernels only
+static bool has_fused_vec_variant(int C) { return has_vec_variant(C) || find(kWide1, C) || find(kWideFirst, C); }
 
 const char *fused_ols_kernel_name(int C) {
-    switch (C) {
-        case 2: return "aw_fused_ols_kernel<2, 1, true>";
-        case 3: return "aw_fused_ols_kernel<3, 2, true>";
-        case 4: return "aw_fused_ols_kernel<4, 2, true>";
-        case 5: return "aw_fused_ols_kernel<5, 3, true>";
-        case 6: return "aw_fused_ols_kernel<6, 3, true>";
-        case 7: return "aw_fused_ols_kernel<7, 4, true>";
-        case 8: return "aw_fused_ols_kernel<8, 4, true>";
-        case 9: return "aw_fused_ols_kernel<9, 5, true>";
-        case 10: return "aw_fused_ols_kernel<10, 5, true>";
-        case 11: return "aw_fused_ols_kernel<11, 6, true>";
-        case 12: return "aw_fused_ols_kernel<12, 6, true>";
-        case 13: return "aw_fused_ols_kernel<13, 7, true>";
-        case 14: return "aw_fused_ols_kernel<14, 7, true>";
-        case 15: return "aw_fused_ols_kernel<15, 4, true> + <15, 4, true, accumulate>";
-        case 16: return "aw_fused_ols_kernel<16, 4, true> + <16, 4, true, accumulate>";
-        default: return "aw_fused_ols_kernel<0, NP, false>";
-    }
+    if (C == 15) return "aw_fused_ols_kernel<15, 4, true> + <15, 4, true, accumulate>";
+    if (C == 16) return "aw_fused_ols_kernel<16, 4, true> + <16, 4, true, accumulate>";
+    if (const TileEntry *k = find(kWide1, C)) return k->name;
+    if (const TileEntry *k = find(kVec, C)) return k->name;
+    return "aw_fused_ols_kernel<0, NP, false>";
 }
 
 static dim3 persistent_grid(long long n_tiles, const TileParams &p) {
@@ -278,87 +241,66 @@ static dim3 persistent_grid(long long n_tiles, const TileParams &p) {
     return dim3((unsigned)(n_tiles < wgs ? n_tiles : wgs));
 }
 
+// one persistent launch over n_tiles tiles; no kernel, no launch (the callers' variant checks keep layouts without one away)
+static void launch_tiles(const TileEntry *k, const TileParams &p, long long n_tiles, hipStream_t stream) {
+    if (k) launch(*k, persistent_grid(n_tiles, p), dim3(kThreads), stream, p, n_tiles);
+}
+
 static void launch_vec(const TileParams &p, long long n_tiles, hipStream_t stream) {
-    const dim3 grid = persistent_grid(n_tiles, p), block(kThreads);
-    if (p.wide_two_pass == 2) {      // 10/12/14 channels in one pass over two eight-channel groups (the default)
-        switch (p.n_channels) {
-#define AW_CASE(CS, NP) case CS: hipLaunchKernelGGL((aw_fused_ols_kernel<CS, NP, true>), grid, block, kLdsBytes, stream, p, n_tiles); return;
-            AW_FOR_EACH_WIDE1(AW_CASE)
-#undef AW_CASE
-            default: break;
-        }
-    }
-    if (p.wide_two_pass || p.n_channels == 10) {
+    const TileEntry *one = p.wide_two_pass == 2 ? find(kWide1, p.n_channels) : nullptr;
+    if (one) return launch_tiles(one, p, n_tiles, stream);      // 10/12/14 channels in one pass over two eight-channel groups (the default)
+    const TileEntry *first = find(kWideFirst, p.n_channels);
+    if ((p.wide_two_pass || p.n_channels == 10) && first) {
         // second pass: input and tables shifted by the first pass's 4 pairs (8 channels), result added to the output
         TileParams q = p;
         q.in = p.in + 8;
         q.tab = p.tab + 4 * (long long)kN;
-        switch (p.n_channels) {
-#define AW_CASE(CS, NPA, NPB) case CS:                                                                                               \
-            hipLaunchKernelGGL((aw_fused_ols_kernel<CS, NPA, true, false>), grid, block, kLdsBytes, stream, p, n_tiles);           \
-            hipLaunchKernelGGL((aw_fused_ols_kernel<CS, NPB, true, true>), grid, block, kLdsBytes, stream, q, n_tiles);            \
-            return;
-            AW_FOR_EACH_WIDE(AW_CASE)
-#undef AW_CASE
-            default: break;
-        }
+        launch_tiles(first, p, n_tiles, stream);
+        return launch_tiles(find(kWideSecond, p.n_channels), q, n_tiles, stream);
     }
-    switch (p.n_channels) {
-#define AW_CASE(CS, NP) case CS: hipLaunchKernelGGL((aw_fused_ols_kernel<CS, NP, true>), grid, block, kLdsBytes, stream, p, n_tiles); break;
-        AW_FOR_EACH_VEC(AW_CASE)
-#undef AW_CASE
-        default: break;
-    }
+    launch_tiles(find(kVec, p.n_channels), p, n_tiles, stream);
 }
 
 static void launch_gen(const TileParams &p, long long n_tiles, hipStream_t stream) {
-    const dim3 grid = persistent_grid(n_tiles, p), block(kThreads);
-    switch (p.n_channels) {
-#define AW_CASE(CS, NP) case CS: hipLaunchKernelGGL((aw_fused_ols_kernel<CS, NP, false>), grid, block, kLdsBytes, stream, p, n_tiles); return;
-        AW_FOR_EACH_BVEC(AW_CASE)
-#undef AW_CASE
-        default: break;
-    }
+    if (const TileEntry *k = find(kBvec, p.n_channels)) return launch_tiles(k, p, n_tiles, stream);
     if (p.n_pairs > 4 && p.n_pairs <= 8 && p.wide_two_pass) {
         // 9-16 channels: compile-time 4-pair pass, then an accumulating compile-time pass over the remaining pairs
         // (input, history and tables shifted by 8 channels; ch_base keeps the padding-channel test right)
         TileParams q = p;
         q.in = p.in + 8; q.hist = p.hist + 8; q.tab = p.tab + 4 * (long long)kN; q.ch_base = 8;
-        hipLaunchKernelGGL((aw_fused_ols_kernel<0, 4, false, false>), grid, block, kLdsBytes, stream, p, n_tiles);
-        switch (p.n_pairs - 4) {
-            case 1: hipLaunchKernelGGL((aw_fused_ols_kernel<0, 1, false, true>), grid, block, kLdsBytes, stream, q, n_tiles); break;
-            case 2: hipLaunchKernelGGL((aw_fused_ols_kernel<0, 2, false, true>), grid, block, kLdsBytes, stream, q, n_tiles); break;
-            case 3: hipLaunchKernelGGL((aw_fused_ols_kernel<0, 3, false, true>), grid, block, kLdsBytes, stream, q, n_tiles); break;
-            default: hipLaunchKernelGGL((aw_fused_ols_kernel<0, 4, false, true>), grid, block, kLdsBytes, stream, q, n_tiles); break;
-        }
-        return;
+        launch_tiles(find(kGen, 4), p, n_tiles, stream);
+        return launch_tiles(find(kGenAcc, p.n_pairs - 4), q, n_tiles, stream);
     }
-    const int np = p.n_pairs <= 4 ? p.n_pairs : 0;
-    switch (np) {
-#define AW_CASE(NP) case NP: hipLaunchKernelGGL((aw_fused_ols_kernel<0, NP, false>), grid, block, kLdsBytes, stream, p, n_tiles); break;
-        AW_FOR_EACH_GEN(AW_CASE)
-#undef AW_CASE
-        default: break;
-    }
+    launch_tiles(find(kGen, p.n_pairs <= 4 ? p.n_pairs : 0), p, n_tiles, stream);
 }
+
+// Which windows of a call lie entirely inside its input.  Windows of `window` frames follow each other every `hop` frames, window 0
+// starts `start` frames before the input (in the history); [lo, hi) are those that start at frame >= 0 and end at least `slack`
+// frames before the input does, both clamped to `tiles`.  hi < lo when there is none: the caller says where the empty range sits.
+struct TileRange { long long lo, hi; };
+static TileRange interior_range(long long frames, int window, int hop, long long start, long long tiles, int slack) {
+    const long long last = frames - slack - window + start;         // latest start of such a window, counted from window 0's
+    TileRange r{(start + hop - 1) / hop, last >= 0 ? last / hop + 1 : 0};
+    if (r.hi > tiles) r.hi = tiles;
+    if (r.lo > tiles) r.lo = tiles;
+    return r;
+}
+// 8192-frame windows: layouts whose frames are not whole float4s read up to 3 floats past a frame (load_batch): one frame of slack
+static int frame_slack(int C) { return (C % 4 != 0 && C != 2) ? 1 : 0; }
+static bool fits_grid(long long n) { return n <= 0x7fffffffLL; }
 
 // Interior tiles (window entirely inside the call's input) and boundary tiles are separate launches.
 hipError_t launch_fused_ols(const TileParams &p_in, int n_streams, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
                             long long *dominant_tiles) {
     TileParams p = p_in;
     // tile i is interior iff  i*hop - hist_len >= 0  and  i*hop - hist_len + N <= frames
-    long long lo = (p.hist_len + p.hop - 1) / p.hop;
-    // layouts whose frames are not whole float4s read up to 3 floats past a frame: keep one frame of slack
-    const long long usable = p.frames - ((p.n_channels % 4 != 0 && p.n_channels != 2) ? 1 : 0);
-    long long hi = (usable - kN + p.hist_len) >= 0 ? (usable - kN + p.hist_len) / p.hop + 1 : 0;
-    if (hi > p.tiles_per_stream) hi = p.tiles_per_stream;
-    if (hi < lo) hi = lo;
-    if (lo > p.tiles_per_stream) { lo = p.tiles_per_stream; hi = lo; }
-    if (!has_fused_vec_variant(p.n_channels) || (p.wide_two_pass != 2 && p.n_channels > 8 && (p.n_channels & 1))) { lo = 0; hi = 0; }  // everything through the generic kernels
-    p.tile_lo = (int)lo; p.tile_hi = (int)hi;
-    const long long n_int = (long long)n_streams * (hi - lo);
-    const long long n_bnd = (long long)n_streams * (p.tiles_per_stream - (hi - lo));
-    if (n_int > 0x7fffffffLL || n_bnd > 0x7fffffffLL) return hipErrorInvalidValue;
+    TileRange r = interior_range(p.frames, kN, p.hop, p.hist_len, p.tiles_per_stream, frame_slack(p.n_channels));
+    if (r.hi < r.lo) r.hi = r.lo;
+    if (!has_fused_vec_variant(p.n_channels) || (p.wide_two_pass != 2 && p.n_channels > 8 && (p.n_channels & 1))) r = {0, 0};  // everything through the generic kernels
+    p.tile_lo = (int)r.lo; p.tile_hi = (int)r.hi;
+    const long long n_int = (long long)n_streams * (r.hi - r.lo);
+    const long long n_bnd = (long long)n_streams * (p.tiles_per_stream - (r.hi - r.lo));
+    if (!fits_grid(n_int) || !fits_grid(n_bnd)) return hipErrorInvalidValue;
     // the events bracket the DOMINANT launch only (interior tiles when the layout has a vector variant)
     const bool dom_int = n_int > 0;
     if (dominant_tiles) *dominant_tiles = dom_int ? n_int : n_bnd;
@@ -379,43 +321,29 @@ hipError_t launch_fused_ols(const TileParams &p_in, int n_streams, hipStream_t s
 hipError_t launch_fused_ols2(const TileParams &p_in, int n_streams, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
                              long long *dominant_tiles) {
     TileParams p = p_in;
-    long long lo = (p.hist_len + p.hop - 1) / p.hop;
     // the last batch of a pseudo-frame reads up to 2 floats past it (2C not a multiple of 4): keep that much input after the window
-    const long long usable = p.frames - (((2 * p.n_channels) % 4 != 0) ? (p.n_channels == 1 ? 2 : 1) : 0);
-    long long hi = (usable - kN2 + p.hist_len) >= 0 ? (usable - kN2 + p.hist_len) / p.hop + 1 : 0;
-    if (hi > p.tiles_per_stream) hi = p.tiles_per_stream;
-    if (hi < lo) hi = lo;
-    if (lo > p.tiles_per_stream) { lo = p.tiles_per_stream; hi = lo; }
-    if (!has_vec2_variant(p.n_channels)) { lo = 0; hi = 0; }
-    p.tile_lo = (int)lo; p.tile_hi = (int)hi;
-    const long long n_int = (long long)n_streams * (hi - lo);
-    const long long n_bnd = (long long)n_streams * (p.tiles_per_stream - (hi - lo));
-    if (n_int > 0x7fffffffLL || n_bnd > 0x7fffffffLL) return hipErrorInvalidValue;
+    const int slack = ((2 * p.n_channels) % 4 != 0) ? (p.n_channels == 1 ? 2 : 1) : 0;
+    TileRange r = interior_range(p.frames, kN2, p.hop, p.hist_len, p.tiles_per_stream, slack);
+    if (r.hi < r.lo) r.hi = r.lo;
+    const TileEntry *interior = find_ols2(p.n_channels, true);
+    if (!interior) r = {0, 0};
+    p.tile_lo = (int)r.lo; p.tile_hi = (int)r.hi;
+    const long long n_int = (long long)n_streams * (r.hi - r.lo);
+    const long long n_bnd = (long long)n_streams * (p.tiles_per_stream - (r.hi - r.lo));
+    if (!fits_grid(n_int) || !fits_grid(n_bnd)) return hipErrorInvalidValue;
     const bool dom_int = n_int > 0;
     if (dominant_tiles) *dominant_tiles = dom_int ? n_int : n_bnd;
     if (n_int > 0) {
-        const dim3 grid = persistent_grid(n_int, p), block(kThreads);
         if (ev0) (void)hipEventRecord(ev0, stream);
-        if (ols2_slp_layout(p.n_channels)) launch_ols2_even(p, true, n_int, grid, stream);
-        else switch (p.n_channels) {
-#define AW_CASE(CS, NB) case CS: hipLaunchKernelGGL((aw_fused_ols2_kernel<CS, NB, true>), grid, block, kLdsBytes, stream, p, n_int); break;
-            AW_FOR_EACH_VEC2(AW_CASE)
-#undef AW_CASE
-            default: break;
-        }
+        launch_tiles(interior, p, n_int, stream);
         if (ev1) (void)hipEventRecord(ev1, stream);
     }
     if (n_bnd > 0) {
         p.dbg = nullptr;                 // diagnostic stamps describe the interior launch only
         if (ev0 && !dom_int) (void)hipEventRecord(ev0, stream);
-        const dim3 grid = persistent_grid(n_bnd, p), block(kThreads);
-        if (ols2_slp_layout(p.n_channels)) launch_ols2_even(p, false, n_bnd, grid, stream);
-        else switch (p.n_channels) {      // compile-time channel and batch counts also for the boundary tiles (scalar loads)
-#define AW_CASE(CS, NB) case CS: hipLaunchKernelGGL((aw_fused_ols2_kernel<CS, NB, false>), grid, block, kLdsBytes, stream, p, n_bnd); break;
-            AW_FOR_EACH_VEC2(AW_CASE)
-#undef AW_CASE
-            default: hipLaunchKernelGGL((aw_fused_ols2_kernel<0, 0, false>), grid, block, kLdsBytes, stream, p, n_bnd); break;
-        }
+        // compile-time channel and batch counts also for the boundary tiles (scalar loads) of the layouts that have an interior kernel
+        const TileEntry *boundary = find_ols2(p.n_channels, false);
+        launch_tiles(boundary ? boundary : find(kBnd2, 0), p, n_bnd, stream);
         if (ev1 && !dom_int) (void)hipEventRecord(ev1, stream);
     }
     return hipGetLastError();
@@ -428,77 +356,27 @@ hipError_t launch_part_forward(const TileParams &p_in, int n_streams, hipStream_
     // window w covers frames [(w - P) B, (w - P) B + N): interior iff it starts at >= 0 and ends inside the input
     // (one frame of slack for layouts whose frames are not whole float4s, see load_batch); head iff it starts in the
     // history (which reaches back P B frames: every window does) and still ends inside the input
-    const long long usable = p.frames - ((p.n_channels % 4 != 0 && p.n_channels != 2) ? 1 : 0);
-    long long lo = p.partitions;
-    // windows [0, hi) end inside the input: (w - P) B + N <= usable  <=>  w <= floor((usable - N) / B) + P   (floor, not truncation:
-    // a call shorter than one window leaves only windows that lie entirely in the history)
-    const long long d = usable - kN;
-    long long hi = (d >= 0 ? d / p.hop : -((-d + p.hop - 1) / p.hop)) + p.partitions + 1;
-    long long head_lo = 0;
-    if (hi > n_windows) hi = n_windows;
-    if (lo > n_windows) lo = n_windows;
-    if (hi < lo) { lo = hi; }                   // short call: even some head windows run past the end
-    if (hi < 0) hi = 0;
-    if (lo < 0) lo = 0;
-    if (!has_vec_variant(p.n_channels)) { lo = 0; hi = 0; }
-    p.tile_lo = (int)lo; p.tile_hi = (int)hi;
-    const long long n_int = (long long)n_streams * (hi - lo), n_head = (long long)n_streams * (lo - head_lo);
-    const long long n_bnd = (long long)n_streams * (n_windows - (hi - head_lo));
-    if (n_int > 0x7fffffffLL || n_bnd > 0x7fffffffLL || n_head > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (p.fwd_one_pair) {             // one channel pair per workgroup, two workgroups per CU (the default)
-        const long long np = p.n_pairs;
-        if (n_int * np > 0x7fffffffLL || n_bnd * np > 0x7fffffffLL || n_head * np > 0x7fffffffLL) return hipErrorInvalidValue;
-        if (n_int > 0) {
-            if (tm) tm->begin();
-            switch (p.n_channels) {
-#define AW_CASE(CS, NP) case CS: hipLaunchKernelGGL((aw_part_forward1_kernel<CS, 1>), dim3((unsigned)(n_int * np)), dim3(kThreads), kInvLdsBytes, stream, p, n_int * np, (int)head_lo); break;
-                AW_FOR_EACH_VEC(AW_CASE)
-#undef AW_CASE
-                default: break;
-            }
-            if (tm) tm->end("aw_part_forward1_kernel<CS, interior>");
-        }
-        if (n_head > 0) {
-            if (tm) tm->begin();
-            switch (p.n_channels) {
-#define AW_CASE(CS, NP) case CS: hipLaunchKernelGGL((aw_part_forward1_kernel<CS, 2>), dim3((unsigned)(n_head * np)), dim3(kThreads), kInvLdsBytes, stream, p, n_head * np, (int)head_lo); break;
-                AW_FOR_EACH_VEC(AW_CASE)
-#undef AW_CASE
-                default: break;
-            }
-            if (tm) tm->end("aw_part_forward1_kernel<CS, head>");
-        }
-        if (n_bnd > 0) {
-            if (tm) tm->begin();
-            hipLaunchKernelGGL((aw_part_forward1_kernel<0, 0>), dim3((unsigned)(n_bnd * np)), dim3(kThreads), kInvLdsBytes, stream, p, n_bnd * np, (int)head_lo);
-            if (tm) tm->end("aw_part_forward1_kernel<generic>");
-        }
-        return hipGetLastError();
-    }
-    if (n_int > 0) {
+    TileRange r = interior_range(p.frames, kN, p.hop, (long long)p.partitions * p.hop, n_windows, frame_slack(p.n_channels));
+    const long long head_lo = 0;
+    if (r.hi < r.lo) r.lo = r.hi;                   // short call: even some head windows run past the end
+    if (!has_vec_variant(p.n_channels)) r = {0, 0};
+    p.tile_lo = (int)r.lo; p.tile_hi = (int)r.hi;
+    const long long n_int = (long long)n_streams * (r.hi - r.lo), n_head = (long long)n_streams * (r.lo - head_lo);
+    const long long n_bnd = (long long)n_streams * (n_windows - (r.hi - head_lo));
+    // one-pair form (the default): one channel pair per workgroup, two workgroups per CU; else persistent workgroups that walk all pairs
+    const long long per = p.fwd_one_pair ? p.n_pairs : 1;
+    if (!fits_grid(n_int) || !fits_grid(n_bnd) || !fits_grid(n_head)) return hipErrorInvalidValue;
+    if (!fits_grid(n_int * per) || !fits_grid(n_bnd * per) || !fits_grid(n_head * per)) return hipErrorInvalidValue;
+    // MODE 1 interior, 2 head, 0 the rest through the generic kernel
+    for (const int mode : {1, 2, 0}) {
+        const long long n = mode == 1 ? n_int : mode == 2 ? n_head : n_bnd;
+        if (n <= 0) continue;
+        const int key = mode ? 4 * p.n_channels + mode : 0;
+        const FwdEntry *k = p.fwd_one_pair ? find(kFwd1, key) : find(kFwd, key);
+        if (!k) return hipErrorInvalidValue;
         if (tm) tm->begin();
-        switch (p.n_channels) {
-#define AW_CASE(CS, NP) case CS: hipLaunchKernelGGL((aw_part_forward_kernel<CS, 1>), persistent_grid(n_int, p), dim3(kThreads), kLdsBytes, stream, p, n_int, (int)head_lo); break;
-            AW_FOR_EACH_VEC(AW_CASE)
-#undef AW_CASE
-            default: break;
-        }
-        if (tm) tm->end("aw_part_forward_kernel<CS, interior>");
-    }
-    if (n_head > 0) {
-        if (tm) tm->begin();
-        switch (p.n_channels) {
-#define AW_CASE(CS, NP) case CS: hipLaunchKernelGGL((aw_part_forward_kernel<CS, 2>), persistent_grid(n_head, p), dim3(kThreads), kLdsBytes, stream, p, n_head, (int)head_lo); break;
-            AW_FOR_EACH_VEC(AW_CASE)
-#undef AW_CASE
-            default: break;
-        }
-        if (tm) tm->end("aw_part_forward_kernel<CS, head>");
-    }
-    if (n_bnd > 0) {
-        if (tm) tm->begin();
-        hipLaunchKernelGGL((aw_part_forward_kernel<0, 0>), persistent_grid(n_bnd, p), dim3(kThreads), kLdsBytes, stream, p, n_bnd, (int)head_lo);
-        if (tm) tm->end("aw_part_forward_kernel<generic>");
+        launch(*k, p.fwd_one_pair ? dim3((unsigned)(n * per)) : persistent_grid(n, p), dim3(kThreads), stream, p, n * per, (int)head_lo);
+        if (tm) tm->end(k->name);
     }
     return hipGetLastError();
 }

@@ -9,6 +9,7 @@
 #include "tile_march.hpp"
 #include "tile_lw.hpp"
 #include "tile_lw16.hpp"
+#include "launch_table.hpp"
 
 namespace awk {
 
@@ -18,6 +19,9 @@ struct StageTimer {
     virtual void end(const char *name) = 0;
     virtual ~StageTimer() = default;
 };
+
+// A launch-table row (launch_table.hpp) of the persistent tile kernels: (params, tile count).
+using TileEntry = KernelEntry<TileParams, long long>;
 
 // Fused overlap-save spatializer: one workgroup per (stream, tile).  Returns hipSuccess or the
 // launch error.  `n_streams * p.tiles_per_stream` workgroups of kThreads.
@@ -73,8 +77,8 @@ hipError_t launch_lw_prep(const float *d_tracks, int n_tracks, int taps, int n_c
 // Measured-ceiling probe (probe_kernels.hip; aw_context_bandwidth_probe): what 0 read / 1 write / 2 copy over `bytes` of src / dst
 hipError_t launch_bw_probe(int what, bool nt, const void *src, void *dst, size_t bytes, int cus, float *sink, hipStream_t stream, size_t *bytes_moved);
 
-// Launch configuration of one context: device properties and tuning knobs, read ONCE at aw_context_create (never on a
-// process path, never process-global: contexts on different devices keep their own).
+// Launch configuration of one context: device properties and tuning knobs, read ONCE at aw_context_create by prepare_kernels()
+// (never on a process path, never process-global: contexts on different devices keep their own).
 struct LaunchCfg {
     int cus = 256;                // compute units of the context's device
     int persistent_wgs = 256;     // grid of the persistent tile kernels (AW_PERSISTENT_WGS; >= 8: the kernels deal tiles to 8 XCD groups)
@@ -91,6 +95,8 @@ struct LaunchCfg {
     int host_out_async = 1;       // host entry on pageable buffers: the copy OUT of a chunk runs on output copy threads beside the next copy IN (AW_HOST_OUT_ASYNC=0: on the driver thread, round 5's form)
     int host_chunk_mb = 96;       // host entry of a multi-stream batch: input megabytes per staged chunk of streams (AW_HOST_CHUNK_MB; a few ms of PCIe Gen5 = the pipeline's fill / drain)
 };
-hipError_t prepare_kernels(LaunchCfg *cfg);   // fills cfg from the current device + environment; sets the dynamic-LDS attribute on every tile kernel
+// fills cfg from the current device + the AW_* environment knobs, then sets the dynamic-LDS attribute on every tile kernel of kernels.hip
+// and ols2_even_kernels.hip (one launch table each, launch_table.hpp)
+hipError_t prepare_kernels(LaunchCfg *cfg);
 
 }  // namespace awk

@@ -5,6 +5,7 @@
 #include "tile_lw.hpp"
 #include "tile_lw16.hpp"
 #include "lw_split_inst.hpp"
+#include "launch_table.hpp"
 
 namespace awk {
 
@@ -57,41 +58,38 @@ template <int RA> constexpr int lw_merge_lds_bytes() { return lw_merge_lds_elems
 
 constexpr int kLwRows1LdsBytes = lw_rows_lds_elems<1>() * (int)sizeof(cf);
 
+// The launch tables (launch_table.hpp).  Rows kernels, three forms: key = 2 pairs + REAL_LAST; the two-pairs-per-batch form exists for
+// up to four pairs.  Merge kernels: key = RA.  Split kernels: two entry points per RA, their tables live in lw_split_a .. e.hip.
+using LwEntry = KernelEntry<LwParams, long long>;
+#define AW_ROW(KERNEL, LDS, NP) {2 * NP, &KERNEL<NP, false>, LDS, #KERNEL "<" #NP ", false>"}, {2 * NP + 1, &KERNEL<NP, true>, LDS, #KERNEL "<" #NP ", true>"},
+#define AW_ROWS4(KERNEL, LDS) AW_ROW(KERNEL, LDS, 1) AW_ROW(KERNEL, LDS, 2) AW_ROW(KERNEL, LDS, 3) AW_ROW(KERNEL, LDS, 4)
+#define AW_ROWS8(KERNEL, LDS) AW_ROWS4(KERNEL, LDS) AW_ROW(KERNEL, LDS, 5) AW_ROW(KERNEL, LDS, 6) AW_ROW(KERNEL, LDS, 7) AW_ROW(KERNEL, LDS, 8)
+static const LwEntry kLwRows[] = {AW_ROWS4(aw_lw_rows_kernel, kLdsBytes)};
+static const LwEntry kLwRows1[] = {AW_ROWS8(aw_lw_rows1_kernel, kLwRows1LdsBytes)};
+static const LwEntry kLwRows16[] = {AW_ROWS8(aw_lw_rows16_kernel, kR16LdsBytes)};
+#undef AW_ROWS8
+#undef AW_ROWS4
+#undef AW_ROW
+#define AW_ROW(RA) {RA, &aw_lw_merge_kernel<RA>, lw_merge_lds_bytes<RA>(), "aw_lw_merge_kernel<" #RA ">"},
+static const LwEntry kMerge[] = {AW_LW_FOR_RA(AW_ROW)};
+#undef AW_ROW
+struct LwSplitEntry {
+    int ra;
+    hipError_t (*prepare)();
+    hipError_t (*launch)(const LwParams &, bool, int, dim3, hipStream_t, long long);
+};
+#define AW_ROW(RA) {RA, &lw_split_prepare<RA>, &lw_split_launch<RA>},
+static const LwSplitEntry kSplit[] = {AW_LW_FOR_RA(AW_ROW)};
+#undef AW_ROW
+
 hipError_t prepare_lw_kernels() {
     hipError_t e = hipSuccess;
-#define AW_SET(RA) if (e == hipSuccess) e = lw_split_prepare<RA>();
-    AW_LW_FOR_RA(AW_SET)
-#undef AW_SET
-#define AW_SET(NP)                                                                                     \
-    if (e == hipSuccess)                                                                               \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_lw_rows_kernel<NP, false>),         \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);                \
-    if (e == hipSuccess)                                                                               \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_lw_rows_kernel<NP, true>),          \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    AW_SET(1) AW_SET(2) AW_SET(3) AW_SET(4)
-#undef AW_SET
-#define AW_SET(NP)                                                                                     \
-    if (e == hipSuccess)                                                                               \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_lw_rows1_kernel<NP, false>),        \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLwRows1LdsBytes);         \
-    if (e == hipSuccess)                                                                               \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_lw_rows1_kernel<NP, true>),         \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLwRows1LdsBytes);
-    AW_SET(1) AW_SET(2) AW_SET(3) AW_SET(4) AW_SET(5) AW_SET(6) AW_SET(7) AW_SET(8)
-#undef AW_SET
-#define AW_SET(NP)                                                                                     \
-    if (e == hipSuccess)                                                                               \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_lw_rows16_kernel<NP, false>),       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kR16LdsBytes);             \
-    if (e == hipSuccess)                                                                               \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_lw_rows16_kernel<NP, true>),        \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kR16LdsBytes);
-    AW_SET(1) AW_SET(2) AW_SET(3) AW_SET(4) AW_SET(5) AW_SET(6) AW_SET(7) AW_SET(8)
-#undef AW_SET
-#define AW_SET(RA) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_lw_merge_kernel<RA>), hipFuncAttributeMaxDynamicSharedMemorySize, lw_merge_lds_bytes<RA>());
-    AW_LW_FOR_RA(AW_SET)
-#undef AW_SET
+    for (const LwSplitEntry &k : kSplit)
+        if (e == hipSuccess) e = k.prepare();
+    if (e == hipSuccess) e = set_dynamic_lds(kLwRows);
+    if (e == hipSuccess) e = set_dynamic_lds(kLwRows1);
+    if (e == hipSuccess) e = set_dynamic_lds(kLwRows16);
+    if (e == hipSuccess) e = set_dynamic_lds(kMerge);
     return e;
 }
 
@@ -112,12 +110,8 @@ hipError_t launch_lw_split(const LwParams &p, int n_streams, hipStream_t stream,
     const dim3 grid(lw_grid(n_tiles, p, ra > 8 ? 1 : 2));
     if (tm) tm->begin();
     hipError_t e = hipErrorInvalidValue;
-    switch (ra) {
-#define AW_CASE(RA) case RA: e = lw_split_launch<RA>(p, wide, cs, grid, stream, n_tiles); break;
-        AW_LW_FOR_RA(AW_CASE)
-#undef AW_CASE
-        default: break;
-    }
+    for (const LwSplitEntry &k : kSplit)
+        if (k.ra == ra) e = k.launch(p, wide, cs, grid, stream, n_tiles);
     if (tm) tm->end(wide ? "aw_lw_split_wide_kernel" : "aw_lw_split_kernel");
     return e;
 }
@@ -127,52 +121,25 @@ hipError_t launch_lw_rows(const LwParams &p, int n_streams, hipStream_t stream, 
     const long long n_tiles = n_sw * (p.R / 2);
     if (n_tiles <= 0) return hipSuccess;
     if (n_tiles > 0x7fffffffLL) return hipErrorInvalidValue;
+    const int key = 2 * p.n_pairs + (p.real_last != 0 ? 1 : 0);
+    const LwEntry *k;
+    unsigned grid, threads = kThreads;
+    // 8 XCD groups: a grid that is a multiple of 8 (every group has the same number of workgroups), at least 8
     if (p.rows_form == 16) {
         if (!p.tab16 || !p.tw2) return hipErrorInvalidValue;
         const int per_cu = p.rows16_wgs >= 1 && p.rows16_wgs <= 4 ? p.rows16_wgs : 3;
-        unsigned grid16 = lw_grid((n_tiles + 7) / 8 * 8, p, per_cu) / 8 * 8;
-        if (grid16 < 8) grid16 = 8;
-        if (tm) tm->begin();
-        const bool real16 = p.real_last != 0;
-        switch (p.n_pairs) {
-#define AW_CASE(NP)                                                                                                       \
-        case NP:                                                                                                          \
-            if (real16) hipLaunchKernelGGL((aw_lw_rows16_kernel<NP, true>), dim3(grid16), dim3(kR16Threads), kR16LdsBytes, stream, p, n_sw);   \
-            else hipLaunchKernelGGL((aw_lw_rows16_kernel<NP, false>), dim3(grid16), dim3(kR16Threads), kR16LdsBytes, stream, p, n_sw);         \
-            break;
-        AW_CASE(1) AW_CASE(2) AW_CASE(3) AW_CASE(4) AW_CASE(5) AW_CASE(6) AW_CASE(7) AW_CASE(8)
-#undef AW_CASE
-        default: return hipErrorInvalidValue;
-        }
-        if (tm) tm->end("aw_lw_rows_kernel");
-        return hipGetLastError();
+        grid = lw_grid((n_tiles + 7) / 8 * 8, p, per_cu) / 8 * 8;
+        threads = kR16Threads;
+        k = find(kLwRows16, key);
+    } else {
+        const bool one = p.rows_pairs_per_batch == 1 || p.n_pairs > 4;          // the two-pairs-per-batch form exists for up to four pairs
+        grid = lw_grid((n_tiles + 7) / 8 * 8, p, one ? 2 : 1) / 8 * 8;
+        k = one ? find(kLwRows1, key) : find(kLwRows, key);
     }
-    // 8 XCD groups: a grid that is a multiple of 8 (every group has the same number of workgroups), at least 8
-    const bool one = p.rows_pairs_per_batch == 1 || p.n_pairs > 4;          // the two-pairs-per-batch form exists for up to four pairs
-    unsigned grid = lw_grid((n_tiles + 7) / 8 * 8, p, one ? 2 : 1) / 8 * 8;
+    if (!k) return hipErrorInvalidValue;
     if (grid < 8) grid = 8;
     if (tm) tm->begin();
-    const bool real = p.real_last != 0;
-    if (one) switch (p.n_pairs) {
-#define AW_CASE(NP)                                                                                                       \
-        case NP:                                                                                                          \
-            if (real) hipLaunchKernelGGL((aw_lw_rows1_kernel<NP, true>), dim3(grid), dim3(kThreads), kLwRows1LdsBytes, stream, p, n_sw);   \
-            else hipLaunchKernelGGL((aw_lw_rows1_kernel<NP, false>), dim3(grid), dim3(kThreads), kLwRows1LdsBytes, stream, p, n_sw);       \
-            break;
-        AW_CASE(1) AW_CASE(2) AW_CASE(3) AW_CASE(4) AW_CASE(5) AW_CASE(6) AW_CASE(7) AW_CASE(8)
-#undef AW_CASE
-        default: return hipErrorInvalidValue;
-    }
-    else switch (p.n_pairs) {
-#define AW_CASE(NP)                                                                                                       \
-        case NP:                                                                                                          \
-            if (real) hipLaunchKernelGGL((aw_lw_rows_kernel<NP, true>), dim3(grid), dim3(kThreads), kLdsBytes, stream, p, n_sw);   \
-            else hipLaunchKernelGGL((aw_lw_rows_kernel<NP, false>), dim3(grid), dim3(kThreads), kLdsBytes, stream, p, n_sw);       \
-            break;
-        AW_CASE(1) AW_CASE(2) AW_CASE(3) AW_CASE(4)
-#undef AW_CASE
-        default: return hipErrorInvalidValue;
-    }
+    launch(*k, dim3(grid), dim3(threads), stream, p, n_sw);
     if (tm) tm->end("aw_lw_rows_kernel");
     return hipGetLastError();
 }
@@ -181,13 +148,10 @@ hipError_t launch_lw_merge(const LwParams &p, int n_streams, hipStream_t stream,
     const long long n_tiles = (long long)n_streams * p.n_windows * kLwChunks;
     if (n_tiles <= 0) return hipSuccess;
     if (n_tiles > 0x7fffffffLL) return hipErrorInvalidValue;
+    const LwEntry *k = find(kMerge, p.R / 8);
+    if (!k) return hipErrorInvalidValue;
     if (tm) tm->begin();
-    switch (p.R / 8) {
-#define AW_CASE(RA) case RA: hipLaunchKernelGGL((aw_lw_merge_kernel<RA>), dim3(lw_grid(n_tiles, p, 2)), dim3(kThreads), lw_merge_lds_bytes<RA>(), stream, p, n_tiles); break;
-        AW_LW_FOR_RA(AW_CASE)
-#undef AW_CASE
-        default: return hipErrorInvalidValue;
-    }
+    launch(*k, dim3(lw_grid(n_tiles, p, 2)), dim3(kThreads), stream, p, n_tiles);
     if (tm) tm->end("aw_lw_merge_kernel");
     return hipGetLastError();
 }

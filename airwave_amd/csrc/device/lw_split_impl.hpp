@@ -3,6 +3,7 @@
 #include "kernels.hpp"
 #include "gpu_ctx.hpp"
 #include "tile_lw.hpp"
+#include "launch_table.hpp"
 
 namespace awk {
 
@@ -26,29 +27,21 @@ template <int RA> constexpr int lw_split_lds_bytes() { return lw_split_lds_elems
 
 #define AW_LW_FOR_CS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
 
-template <int RA> hipError_t lw_split_prepare() {
-    hipError_t e = hipSuccess;
-#define AW_SET(CS)                                                                                                       \
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_lw_split_kernel<RA, CS>),            \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lw_split_lds_bytes<RA>()); \
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_lw_split_wide_kernel<RA, CS>),       \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lw_split_lds_bytes<RA>());
-    AW_LW_FOR_CS(AW_SET)
-#undef AW_SET
-    return e;
-}
+// the launch table of one RA, key = 2 cs + wide
+template <int RA> struct LwSplitTable {
+#define AW_ROW(CS)                                                                                            \
+    {2 * CS, &aw_lw_split_kernel<RA, CS>, lw_split_lds_bytes<RA>(), "aw_lw_split_kernel"},                     \
+    {2 * CS + 1, &aw_lw_split_wide_kernel<RA, CS>, lw_split_lds_bytes<RA>(), "aw_lw_split_wide_kernel"},
+    static inline const KernelEntry<LwParams, long long> rows[] = {AW_LW_FOR_CS(AW_ROW)};
+#undef AW_ROW
+};
+
+template <int RA> hipError_t lw_split_prepare() { return set_dynamic_lds(LwSplitTable<RA>::rows); }
 
 template <int RA> hipError_t lw_split_launch(const LwParams &p, bool wide, int cs, dim3 grid, hipStream_t stream, long long n_tiles) {
-    switch (cs) {
-#define AW_CASE(CS)                                                                                                                          \
-        case CS:                                                                                                                             \
-            if (wide) hipLaunchKernelGGL((aw_lw_split_wide_kernel<RA, CS>), grid, dim3(kThreads), lw_split_lds_bytes<RA>(), stream, p, n_tiles); \
-            else hipLaunchKernelGGL((aw_lw_split_kernel<RA, CS>), grid, dim3(kThreads), lw_split_lds_bytes<RA>(), stream, p, n_tiles);           \
-            break;
-        AW_LW_FOR_CS(AW_CASE)
-#undef AW_CASE
-        default: return hipErrorInvalidValue;
-    }
+    const auto *k = find(LwSplitTable<RA>::rows, 2 * cs + (wide ? 1 : 0));
+    if (!k) return hipErrorInvalidValue;
+    launch(*k, grid, dim3(kThreads), stream, p, n_tiles);
     return hipGetLastError();
 }
 

@@ -16,6 +16,13 @@
 #define AW_OLA_LAYOUTS_F(X) AW_OLA_FOR_H(X, 9) AW_OLA_FOR_H(X, 11)
 
 namespace awk {
+// whether one of the units carries the (channels, H) kernel
+constexpr bool ola_has_kernel(int n_channels, int rows) {
+#define AW_ROW(CS, H) if (n_channels == CS && rows == H) return true;
+    AW_OLA_LAYOUTS_A(AW_ROW) AW_OLA_LAYOUTS_B(AW_ROW) AW_OLA_LAYOUTS_C(AW_ROW) AW_OLA_LAYOUTS_D(AW_ROW) AW_OLA_LAYOUTS_E(AW_ROW) AW_OLA_LAYOUTS_F(AW_ROW)
+#undef AW_ROW
+    return false;
+}
 // each returns false when the (channels, H) pair is not one of its unit's
 bool launch_ola_a(const TileParams &p, int H, dim3 grid, long long n_tiles, hipStream_t stream);
 bool launch_ola_b(const TileParams &p, int H, dim3 grid, long long n_tiles, hipStream_t stream);

@@ -11,11 +11,7 @@ int fused_ola_rows(int n_channels, int taps) {
     if (taps < 2) return 0;
     int H = (kN - (taps - 1)) / 512;
     if (H > 8) H = 8;
-    if (H < 6) return 0;
-    switch (n_channels) {
-        case 4: case 6: case 7: case 8: case 9: case 10: case 11: case 12: case 13: case 14: case 15: case 16: return H;
-        default: return 0;
-    }
+    return ola_has_kernel(n_channels, H) ? H : 0;
 }
 
 const char *fused_ola_kernel_name(int C, int H) {

@@ -4,26 +4,17 @@
 
 namespace awk {
 
-hipError_t AW_OLA_UNIT_PREPARE() {
-    hipError_t e = hipSuccess;
-#define AW_SET(CS, H)                                                                                               \
-    if (e == hipSuccess)                                                                                            \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_fused_ola_kernel<CS, (CS + 1) / 2, H>),          \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    AW_OLA_UNIT_LIST(AW_SET)
-#undef AW_SET
-    return e;
-}
+// the unit's launch table, key = 16 channels + H
+#define AW_ROW(CS, H) {16 * CS + H, &aw_fused_ola_kernel<CS, (CS + 1) / 2, H>, kLdsBytes, "aw_fused_ola_kernel<" #CS ", (" #CS " + 1) / 2, " #H ">"},
+static const TileEntry kOla[] = {AW_OLA_UNIT_LIST(AW_ROW)};
+#undef AW_ROW
+
+hipError_t AW_OLA_UNIT_PREPARE() { return set_dynamic_lds(kOla); }
 
 bool AW_OLA_UNIT_LAUNCH(const TileParams &p, int H, dim3 grid, long long n_tiles, hipStream_t stream) {
-#define AW_CASE(CS, HH)                                                                                                              \
-    if (p.n_channels == CS && H == HH) {                                                                                             \
-        hipLaunchKernelGGL((aw_fused_ola_kernel<CS, (CS + 1) / 2, HH>), grid, dim3(kThreads), kLdsBytes, stream, p, n_tiles);        \
-        return true;                                                                                                                 \
-    }
-    AW_OLA_UNIT_LIST(AW_CASE)
-#undef AW_CASE
-    return false;
+    const auto *k = find(kOla, 16 * p.n_channels + H);
+    if (k) launch(*k, grid, dim3(kThreads), stream, p, n_tiles);
+    return k != nullptr;
 }
 
 }  // namespace awk

@@ -7,37 +7,14 @@ namespace awk {
 
 #define AW_FOR_EACH_VEC2_EVEN(X) X(4, 2) X(6, 3) X(8, 4)
 
-hipError_t prepare_ols2_even() {
-    hipError_t e = hipSuccess;
-#define AW_SET(CS, NB)                                                                                \
-    if (e == hipSuccess)                                                                              \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_fused_ols2_kernel<CS, NB, true>),  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);               \
-    if (e == hipSuccess)                                                                              \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_fused_ols2_kernel<CS, NB, false>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    AW_FOR_EACH_VEC2_EVEN(AW_SET)
-#undef AW_SET
-    return e;
-}
+// key = 2 channels + INTERIOR
+#define AW_ROW(CS, NB)                                                                                                          \
+    {2 * CS + 1, &aw_fused_ols2_kernel<CS, NB, true>, kLdsBytes, "aw_fused_ols2_kernel<" #CS ", " #NB ", true>"},               \
+    {2 * CS, &aw_fused_ols2_kernel<CS, NB, false>, kLdsBytes, "aw_fused_ols2_kernel<" #CS ", " #NB ", false>"},
+static const TileEntry kEven[] = {AW_FOR_EACH_VEC2_EVEN(AW_ROW)};
+#undef AW_ROW
 
-void launch_ols2_even(const TileParams &p, bool interior, long long n_tiles, dim3 grid, hipStream_t stream) {
-    const dim3 block(kThreads);
-    if (interior) {
-        switch (p.n_channels) {
-#define AW_CASE(CS, NB) case CS: hipLaunchKernelGGL((aw_fused_ols2_kernel<CS, NB, true>), grid, block, kLdsBytes, stream, p, n_tiles); break;
-            AW_FOR_EACH_VEC2_EVEN(AW_CASE)
-#undef AW_CASE
-            default: break;
-        }
-    } else {
-        switch (p.n_channels) {
-#define AW_CASE(CS, NB) case CS: hipLaunchKernelGGL((aw_fused_ols2_kernel<CS, NB, false>), grid, block, kLdsBytes, stream, p, n_tiles); break;
-            AW_FOR_EACH_VEC2_EVEN(AW_CASE)
-#undef AW_CASE
-            default: break;
-        }
-    }
-}
+hipError_t prepare_ols2_even() { return set_dynamic_lds(kEven); }
+const TileEntry *find_ols2_even(int n_channels, bool interior) { return find(kEven, 2 * n_channels + (interior ? 1 : 0)); }
 
 }  // namespace awk

@@ -24,8 +24,8 @@ __global__ void __launch_bounds__(kThreads) aw_fused_ols2_kernel(TileParams p, l
     tiles_fused_ols2<GpuCtx, CS, NB, INTERIOR>(ctx, p, lo + slot, per_xcd_wg, hi);
 }
 
-// even channel counts (ols2_even_kernels.hip)
+// even channel counts (ols2_even_kernels.hip): nullptr for every other layout
 hipError_t prepare_ols2_even();
-void launch_ols2_even(const TileParams &p, bool interior, long long n_tiles, dim3 grid, hipStream_t stream);
+const TileEntry *find_ols2_even(int n_channels, bool interior);
 
 }  // namespace awk
