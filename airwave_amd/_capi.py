@@ -59,6 +59,10 @@ SIGNATURES = {
     "aw_spatializer_get_levels": (_I32, [_V, _I32, _I32, _V]),
     "aw_spatializer_reset_levels": (_I32, [_V]),
     "aw_spatializer_set_gain": (_I32, [_V, _I32, c_float_p, _I32, ctypes.c_float]),
+    "aw_spatializer_set_loudness": (_I32, [_V, _I32, _D]),
+    "aw_spatializer_get_loudness": (_I32, [_V, _I32, _I32, _V]),
+    "aw_spatializer_get_loudness_hops": (_I32, [_V, _I32, _I64, _I64, _V]),
+    "aw_loudness_gain": (_I32, [_D, _D, c_float_p]),
     "aw_spatializer_reset": (_I32, [_V]),
     "aw_spatializer_stream_count": (_I32, [_V]),
     "aw_spatializer_channel_count": (_I32, [_V]),
@@ -143,6 +147,13 @@ class StreamLevels(ctypes.Structure):
     """aw_stream_levels (56 bytes)."""
     _fields_ = [("peak", ctypes.c_float * 2), ("gain", ctypes.c_float), ("reserved", ctypes.c_uint32), ("energy", ctypes.c_double * 2),
                 ("frames", ctypes.c_uint64), ("clipped", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64)]
+
+
+class StreamLoudness(ctypes.Structure):
+    """aw_stream_loudness (56 bytes)."""
+    _fields_ = [("integrated_lufs", ctypes.c_double), ("relative_threshold_lufs", ctypes.c_double), ("blocks", ctypes.c_uint32),
+                ("blocks_above_absolute", ctypes.c_uint32), ("blocks_gated", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("frames", ctypes.c_uint64), ("frames_dropped", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64)]
 
 
 _lib = None

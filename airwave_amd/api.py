@@ -83,6 +83,21 @@ GAIN_MODES = {"none": 0, "fixed": 1, "peak_ceiling": 2}
 LEVELS_DTYPE = np.dtype([("peak", np.float32, (2,)), ("gain", np.float32), ("reserved", np.uint32), ("energy", np.float64, (2,)),
                          ("frames", np.uint64), ("clipped", np.uint64), ("nonfinite", np.uint64)], align=False)
 
+# aw_stream_loudness, byte for byte (Spatializer.loudness)
+LOUDNESS_DTYPE = np.dtype([("integrated_lufs", np.float64), ("relative_threshold_lufs", np.float64), ("blocks", np.uint32),
+                           ("blocks_above_absolute", np.uint32), ("blocks_gated", np.uint32), ("reserved", np.uint32),
+                           ("frames", np.uint64), ("frames_dropped", np.uint64), ("nonfinite", np.uint64)], align=False)
+
+
+def loudness_gain(lufs: float, target_lufs: float) -> float:
+    """aw_loudness_gain: 10^((target - lufs) / 20) as float32.  ValueError for a non-finite loudness (a silent stream) or target."""
+    lufs, target_lufs = float(lufs), float(target_lufs)
+    if not (np.isfinite(lufs) and np.isfinite(target_lufs)):
+        raise ValueError(f"loudness and target must be finite, got {lufs!r} and {target_lufs!r}")
+    g = ctypes.c_float(0.0)
+    _check(_capi.load().aw_loudness_gain(lufs, target_lufs, ctypes.byref(g)))
+    return float(g.value)
+
 
 def sample_format_bytes(fmt) -> int:
     """aw_sample_format_bytes: 4, 2, 3, 4 for f32, s16, s24, s32; 0 for an unknown format."""
@@ -434,7 +449,8 @@ class Spatializer:
                 "overlap_add_rows_policy": g(17),   # ... which this spatializer's calls do when they have enough blocks (0: never)
                 "position_frames": g(18),       # frames processed since creation / the last reset (the dither's frame position)
                 "metering": g(19),              # the level meter is on (set_metering)
-                "gain_mode": g(20)}             # aw_gain_mode of the batch entries (set_gain)
+                "gain_mode": g(20),             # aw_gain_mode of the batch entries (set_gain)
+                "loudness": g(21)}              # the loudness measurement is on (set_loudness)
 
     def process_device(self, in_ptr: int, out_ptr: int, frames: int) -> None:
         _check(self._lib.aw_spatializer_process(self._h, ctypes.c_void_p(in_ptr), ctypes.c_void_p(out_ptr), frames))
@@ -557,6 +573,33 @@ class Spatializer:
                 raise ValueError(f"peak_ceiling needs 0 < ceiling <= 1, got {ceiling!r}")
             c = float(ceiling)
         _check(self._lib.aw_spatializer_set_gain(self._h, mode, None if g is None else _fp(g), 0 if g is None else int(g.size), ctypes.c_float(c)))
+
+    def set_loudness(self, on: bool = True, max_seconds: float = 0.0) -> None:
+        """aw_spatializer_set_loudness: BS.1770 integrated loudness of every later batch call, per stream, measured before the gain.
+        Switching it on allocates the hop energies of max_seconds per stream here, not on the process path."""
+        if on and not (np.isfinite(max_seconds) and max_seconds > 0):
+            raise ValueError(f"max_seconds must be finite and positive, got {max_seconds!r}")
+        _check(self._lib.aw_spatializer_set_loudness(self._h, int(bool(on)), float(max_seconds)))
+
+    def loudness(self, first_stream: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """aw_spatializer_get_loudness: the gated loudness of n streams from first_stream on (default: all) as a structured array of
+        LOUDNESS_DTYPE.  Synchronises the context's stream."""
+        first_stream = int(first_stream)
+        n = self.n_streams - first_stream if n is None else int(n)
+        if first_stream < 0 or n < 0 or first_stream + n > self.n_streams:
+            raise ValueError(f"streams [{first_stream}, {first_stream + n}) outside [0, {self.n_streams})")
+        out = np.zeros(n, LOUDNESS_DTYPE)
+        _check(self._lib.aw_spatializer_get_loudness(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
+        return out
+
+    def loudness_hops(self, stream: int, first_hop: int, n: int) -> np.ndarray:
+        """aw_spatializer_get_loudness_hops: the raw 100 ms hop energies [first_hop, first_hop + n) of one stream (float64)."""
+        stream, first_hop, n = int(stream), int(first_hop), int(n)
+        if not 0 <= stream < self.n_streams or first_hop < 0 or n < 0:
+            raise ValueError(f"stream {stream}, hops [{first_hop}, {first_hop + n}) out of range")
+        out = np.zeros(n, np.float64)
+        _check(self._lib.aw_spatializer_get_loudness_hops(self._h, stream, first_hop, n, ctypes.c_void_p(out.ctypes.data)))
+        return out
 
     def reset(self) -> None:
         _check(self._lib.aw_spatializer_reset(self._h))

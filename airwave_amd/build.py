@@ -38,6 +38,7 @@ SOURCES = [
     "device/probe_kernels.hip",
     "device/prep_kernels.hip",
     "device/pcm_kernels.hip",
+    "device/loudness_kernels.hip",
     "runtime.cpp",
     "eq_runtime.cpp",
     "host/eq.cpp",

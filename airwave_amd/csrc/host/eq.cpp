@@ -307,6 +307,30 @@ static Mat2 mat2_mul(const Mat2 &a, const Mat2 &b) {
 }
 static void mat2_store(const Mat2 &a, double *dst) { for (int i = 0; i < 4; ++i) dst[i] = a.m[i].hi + a.m[i].lo; }
 
+void eq_section_tables(const Biquad &c, double *cf, double *plane) {
+    double *zir = cf + 5, *ppow = zir + awk::kEqChunk * 2;
+    cf[0] = c.b0; cf[1] = c.b1; cf[2] = c.b2; cf[3] = c.a1; cf[4] = c.a2;
+    // zero-input state matrix of the transposed direct form II section (x = 0 in :71-77):
+    //   z1' = -a1 z1 + z2,  z2' = -a2 z1,  y = z1
+    const Mat2 M{{{-c.a1, 0.0}, {1.0, 0.0}, {-c.a2, 0.0}, {0.0, 0.0}}};
+    Mat2 Mj{{{1.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {1.0, 0.0}}};
+    for (int j = 0; j < awk::kEqChunk; ++j) {
+        zir[j * 2] = Mj.m[0].hi + Mj.m[0].lo;
+        zir[j * 2 + 1] = Mj.m[1].hi + Mj.m[1].lo;
+        Mj = mat2_mul(M, Mj);
+    }
+    Mat2 P = Mj;                                  // M^chunk
+    Mat2 Pl{{{1.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {1.0, 0.0}}};
+    for (int l = 0; l < 64; ++l) {          // entry m holds P^(m+1)
+        Pl = mat2_mul(P, Pl);
+        mat2_store(Pl, &plane[(size_t)l * 4]);
+    }
+    for (int s = 0; s < awk::kEqScanSteps; ++s) {
+        mat2_store(P, &ppow[s * 4]);
+        P = mat2_mul(P, P);
+    }
+}
+
 int eq_prepare(const EqDefinition *def, double fs, EqPrepared &out, int *bad_index, int *bad_kind) {
     if (!std::isfinite(fs) || !(fs > 0)) return kEqPrepInvalidSampleRate;                 // :172-174
     const double preamp_db = def ? def->preamp_db : 0.0;
@@ -334,28 +358,7 @@ int eq_prepare(const EqDefinition *def, double fs, EqPrepared &out, int *bad_ind
             if (bad_kind) *bad_kind = kind;
             return kEqPrepInvalidFilter;
         }
-        double *cf = &out.tab[(size_t)k * awk::kEqTabDoubles];
-        double *zir = cf + 5, *ppow = zir + awk::kEqChunk * 2;
-        cf[0] = c.b0; cf[1] = c.b1; cf[2] = c.b2; cf[3] = c.a1; cf[4] = c.a2;
-        // zero-input state matrix of the transposed direct form II section (x = 0 in :71-77):
-        //   z1' = -a1 z1 + z2,  z2' = -a2 z1,  y = z1
-        const Mat2 M{{{-c.a1, 0.0}, {1.0, 0.0}, {-c.a2, 0.0}, {0.0, 0.0}}};
-        Mat2 Mj{{{1.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {1.0, 0.0}}};
-        for (int j = 0; j < awk::kEqChunk; ++j) {
-            zir[j * 2] = Mj.m[0].hi + Mj.m[0].lo;
-            zir[j * 2 + 1] = Mj.m[1].hi + Mj.m[1].lo;
-            Mj = mat2_mul(M, Mj);
-        }
-        Mat2 P = Mj;                                  // M^chunk
-        Mat2 Pl{{{1.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {1.0, 0.0}}};
-        for (int l = 0; l < 64; ++l) {          // entry m holds P^(m+1)
-            Pl = mat2_mul(P, Pl);
-            mat2_store(Pl, &out.plane[((size_t)k * 64 + l) * 4]);
-        }
-        for (int s = 0; s < awk::kEqScanSteps; ++s) {
-            mat2_store(P, &ppow[s * 4]);
-            P = mat2_mul(P, P);
-        }
+        eq_section_tables(c, &out.tab[(size_t)k * awk::kEqTabDoubles], &out.plane[(size_t)k * 64 * 4]);
     }
     return kEqPrepOk;
 }

@@ -47,6 +47,12 @@ enum { kEqPrepOk = 0, kEqPrepInvalidSampleRate = 1, kEqPrepInvalidFilter = 2, kE
 // *bad_kind = the BiquadCoefficientError kind; on kEqPrepTooManyFilters *bad_index = the count.
 int eq_prepare(const EqDefinition *def, double sample_rate, EqPrepared &out, int *bad_index, int *bad_kind);
 
+// The kernel tables of ONE section (eq_prepare's builder; the loudness meter's two K-weighting sections use it too): tab receives the
+// EqTables::tab entry (coefficients, zero-input rows, scan powers: awk::kEqTabDoubles doubles), plane the [64][4] per-lane powers.  The
+// powers are formed in double-double and rounded once.
+void eq_section_tables(const Biquad &c, double *tab, double *plane);
+constexpr int kEqSectionPlaneDoubles = 64 * 4;
+
 // The equalizer FOLDED INTO THE IMPULSE RESPONSES (round 6).  Between two setTarget calls the reference's equalizer is a linear
 // time-invariant filter (preamp x cascade of biquads, ParametricEqualizerProcessor.swift:58-91) that follows the spatializer in the graph
 // (AudioEffectGraph.swift:195-211), so  EQ(x * h) = x * (h * g)  with g its impulse response: a batch host that knows the definition

@@ -14,8 +14,10 @@
 #include <thread>
 
 #include "device/eq_kernels.hpp"
+#include "device/loudness_kernels.hpp"
 #include "device/pcm.hpp"
 #include "device/pcm_kernels.hpp"
+#include "host/eq.hpp"
 #include "host/tables.hpp"
 
 // Default fused window: 8192 frames; 16384 (tile_ols2.hpp) where measurements favour it.
@@ -233,6 +235,7 @@ static aw_status context_create_impl(int32_t device, void *ext_stream, bool use_
     if (e == hipSuccess) e = awk::prepare_ola_kernels();
     if (e == hipSuccess) e = awk::prepare_lw_kernels();
     if (e == hipSuccess) e = awk::prepare_eq_kernels();
+    if (e == hipSuccess) e = awk::prepare_loudness_kernels();
     if (e == hipSuccess) e = awk::prepare_prep_kernels();
     awh::Twiddles tw;
     awh::build_twiddles(tw);
@@ -557,6 +560,7 @@ aw_status aw_spatializer_create(aw_context *ctx, const aw_hrir *hrir, int32_t n_
     if (!sp) return fail(AW_ERR_OUT_OF_MEMORY, "spatializer");
     sp->ctx = ctx; sp->n_channels = n_in; sp->n_pairs = (n_in + 1) / 2; sp->n_streams = n_streams;
     sp->taps = hrir->taps;
+    sp->sample_rate = hrir->sample_rate;
     const int N = awk::kN;
     // Path choice.  AW_WINDOW=8192|16384 forces the fused window, 4096 the partitioned path (tuning / A-B); default: see below.
     int window = 0;
@@ -733,6 +737,7 @@ void aw_spatializer_destroy(aw_spatializer *sp) {
     if (sp->d_pcm_out) (void)hipFree(sp->d_pcm_out);
     if (sp->d_clip) (void)hipFree(sp->d_clip);
     if (sp->d_levels) (void)hipFree(sp->d_levels);
+    if (sp->d_loud) (void)hipFree(sp->d_loud);
     if (sp->k0) (void)hipEventDestroy(sp->k0);
     if (sp->k1) (void)hipEventDestroy(sp->k1);
     for (auto &pr : sp->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -767,6 +772,7 @@ int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what) {
         case 18: return (int64_t)sp->position;    // frames processed since create / the last reset (the dither's frame position)
         case 19: return sp->metering ? 1 : 0;     // the level meter is on (aw_spatializer_set_metering)
         case 20: return sp->gain_mode;            // aw_gain_mode of the batch entries (aw_spatializer_set_gain)
+        case 21: return sp->loudness ? 1 : 0;     // the loudness measurement is on (aw_spatializer_set_loudness)
         default: return -1;
     }
 }
@@ -1498,6 +1504,40 @@ static float lv_host_call(aw_spatializer *sp, const float *y, size_t n) {
     return g;
 }
 
+/* ---- integrated loudness of the batch entries (aw_spatializer_set_loudness; rules: device/loudness.hpp, kernels: device/loudness_scan.hpp) -- */
+static_assert(sizeof(aw_stream_loudness) == 56, "aw_stream_loudness");
+static double *ld_state(const aw_spatializer *sp) { return reinterpret_cast<double *>(sp->d_loud); }
+static unsigned long long *ld_nonfinite(const aw_spatializer *sp) { return reinterpret_cast<unsigned long long *>(ld_state(sp) + (size_t)sp->n_streams * awk::kLdFilters * 4); }
+static double *ld_hops(const aw_spatializer *sp) { return reinterpret_cast<double *>(ld_nonfinite(sp) + sp->n_streams); }
+static size_t ld_record_bytes(const aw_spatializer *sp) { return (size_t)sp->n_streams * (awk::kLdFilters * 4 + 1 + (size_t)sp->loud_cap) * 8; }
+static double *ld_tables(const aw_spatializer *sp) { return reinterpret_cast<double *>(sp->d_loud + ld_record_bytes(sp)); }
+constexpr size_t kLdTabDoubles = (size_t)awk::kLdFilters * awk::kEqTabDoubles, kLdPlaneDoubles = (size_t)awk::kLdFilters * awh::kEqSectionPlaneDoubles;
+
+// The float32 output y of the streams [s0, s0 + ns) of a call (dense: `frames` apart), before any gain; frame0: frames measured before
+// this call.  Chunks of streams are independent (one workgroup owns a stream), so chunking changes no bit.
+static aw_status ld_measure(aw_spatializer *sp, const float *y, int64_t s0, int ns, int64_t frames, uint64_t frame0) {
+    SpStageTimer tm(sp);
+    if (sp->profiling) tm.begin();
+    awk::LoudnessParams p{};
+    p.in = y;
+    p.z = ld_state(sp) + (size_t)s0 * awk::kLdFilters * 4;
+    p.hops = ld_hops(sp) + (size_t)s0 * (size_t)sp->loud_cap;
+    p.nonfinite = ld_nonfinite(sp) + s0;
+    p.tab = ld_tables(sp); p.plane = ld_tables(sp) + kLdTabDoubles;
+    p.frames = frames; p.stride_frames = frames; p.frame0 = (long long)frame0;
+    p.hop = sp->loud_hop; p.cap_hops = sp->loud_cap;
+    AW_HIP_TRY(awk::launch_loudness(p, ns, sp->ctx->stream));
+    if (sp->profiling) tm.end("aw_loudness_kernel");
+    return AW_OK;
+}
+
+// the records start over (the setting and the capacity stay)
+static aw_status ld_reset(aw_spatializer *sp) {
+    sp->loud_frames = 0;
+    if (sp->d_loud) AW_HIP_TRY(hipMemsetAsync(sp->d_loud, 0, ld_record_bytes(sp), sp->ctx->stream));
+    return AW_OK;
+}
+
 /* ---- host entry ------------------------------------------------------------------------------------
  * The reference's callers hand over host buffers (AudioPipeline.swift:3-11: the four planar pointers of a render callback); an offline
  * batch host does too.  A multi-stream batch crosses PCIe in CHUNKS OF STREAMS (streams are independent: state is per stream), double
@@ -1631,6 +1671,7 @@ struct BatchCall {
     uint64_t pos0;                          // position of the call's first frame: every encode of the call keys its dither on it
     unsigned long long *clip;               // NULL, or the device counter this call's encodes add their clipped samples to
     bool metered;                           // metered and gained as the handle is set (the planar entry's inner call is not)
+    uint64_t loud0;                         // loudness: frames measured before this call (the hop index of its first frame)
 };
 
 // s0: the handle's index of the first of the ns streams encoded.  No dither and neither gain nor meter: the plain encode kernel, as ever.
@@ -1679,6 +1720,8 @@ static aw_status batch_begin(aw_spatializer *sp, BatchCall *call, unsigned long 
     if (metered) {
         const aw_status st = lv_begin_call(sp, call->frames, true);
         if (st != AW_OK) return st;
+        call->loud0 = sp->loud_frames;
+        if (sp->loudness) sp->loud_frames += (uint64_t)call->frames;
     }
     if (zero_clip) AW_HIP_TRY(hipMemsetAsync(clip, 0, sizeof(unsigned long long), sp->ctx->stream));
     return AW_OK;
@@ -1694,6 +1737,7 @@ static aw_status batch_chunk(aw_spatializer *sp, const BatchCall &call, int64_t 
     const float *x = call.dec ? f_in : static_cast<const float *>(pcm_src);
     float *y = call.enc ? f_out : static_cast<float *>(pcm_dst);
     if (st == AW_OK) st = sp_run_streams(sp, call.lw, (int)s0, ns, x, y, call.frames);
+    if (st == AW_OK && call.metered && sp->loudness) st = ld_measure(sp, y, s0, ns, call.frames, call.loud0);      // (before the gain)
     if (st == AW_OK && call.metered) st = lv_after_run(sp, y, s0, ns, call.frames, !call.enc);
     if (st == AW_OK && call.enc) st = pcm_encode(sp, call, y, pcm_dst, s0, ns);
     return st;
@@ -1705,6 +1749,10 @@ static aw_status batch_run_pinned(aw_spatializer *sp, int64_t frames, bool meter
     const LwCallPlan lw = sp_begin_call(sp, frames, pos0);
     aw_status st = metered ? lv_begin_call(sp, frames, false) : AW_OK;
     if (st == AW_OK) st = sp_run_streams(sp, lw, 0, 1, sp->h_pin_in, sp->h_pin_out, frames);
+    if (st == AW_OK && metered && sp->loudness) {        // the loudness kernels read the page-locked output as the convolution kernels wrote it
+        st = ld_measure(sp, sp->h_pin_out, 0, 1, frames, sp->loud_frames);
+        sp->loud_frames += (uint64_t)frames;
+    }
     if (st != AW_OK) return st;
     batch_end(sp);
     AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
@@ -1959,7 +2007,7 @@ static aw_status lv_reset(aw_spatializer *sp) {
     sp->metered_frames = 0;
     sp->applied_mode = AW_GAIN_NONE;
     if (sp->d_levels) AW_HIP_TRY(hipMemsetAsync(sp->d_levels, 0, (size_t)sp->n_streams * (sizeof(awl::Record) + sizeof(uint32_t)), sp->ctx->stream));
-    return AW_OK;
+    return ld_reset(sp);
 }
 
 aw_status aw_spatializer_reset(aw_spatializer *sp) try {
@@ -2023,6 +2071,87 @@ aw_status aw_spatializer_get_levels(aw_spatializer *sp, int32_t first_stream, in
         o.clipped = r.clipped;
         o.nonfinite = r.nonfinite;
     }
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+// Checks first, then the one allocation and the table upload (here, never on the process path).  A capacity other than the one held
+// makes new, empty records.
+aw_status aw_spatializer_set_loudness(aw_spatializer *sp, int32_t on, double max_seconds) try {
+    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    if (!on) { sp->loudness = false; return AW_OK; }
+    if (!std::isfinite(max_seconds) || !(max_seconds > 0.0) || max_seconds > 1e9) return fail(AW_ERR_INVALID_ARGUMENT, "max_seconds must be finite and positive");
+    const long long hop = awlo::hop_frames(sp->sample_rate);
+    if (hop <= 0) return fail(AW_ERR_INVALID_ARGUMENT, "loudness needs an HRIR sample rate that is a finite positive multiple of 10 Hz");
+    const int64_t cap = (int64_t)std::ceil((double)awlo::kHopsPerSecond * max_seconds);
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    if (!sp->d_loud || cap != sp->loud_cap) {
+        double kw[awlo::kFilters][5];
+        awlo::k_weighting(sp->sample_rate, kw);
+        std::vector<double> tables(kLdTabDoubles + kLdPlaneDoubles);
+        for (int k = 0; k < awlo::kFilters; ++k)
+            awh::eq_section_tables(awh::Biquad{kw[k][0], kw[k][1], kw[k][2], kw[k][3], kw[k][4]}, &tables[(size_t)k * awk::kEqTabDoubles],
+                                   &tables[kLdTabDoubles + (size_t)k * awh::kEqSectionPlaneDoubles]);
+        AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));            // whatever still reads the old records
+        if (sp->d_loud) { (void)hipFree(sp->d_loud); sp->d_loud = nullptr; sp->loudness = false; }
+        sp->loud_hop = hop; sp->loud_cap = cap; sp->loud_frames = 0;
+        const size_t rec = ld_record_bytes(sp);
+        AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sp->d_loud), rec + tables.size() * sizeof(double)));
+        sp->ctx->device_allocs += 1;
+        AW_HIP_TRY(hipMemsetAsync(sp->d_loud, 0, rec, sp->ctx->stream));
+        AW_HIP_TRY(hipMemcpyAsync(ld_tables(sp), tables.data(), tables.size() * sizeof(double), hipMemcpyHostToDevice, sp->ctx->stream));
+        AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));            // (the upload reads `tables`)
+    }
+    sp->loudness = true;
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_spatializer_get_loudness(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_loudness *out) try {
+    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    if (first_stream < 0 || n < 0 || (int64_t)first_stream + n > sp->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "streams out of range");
+    if (n == 0) return AW_OK;
+    if (!out) return fail(AW_ERR_INVALID_ARGUMENT, "out_host is NULL");
+    if (!sp->d_loud) return fail(AW_ERR_INVALID_ARGUMENT, "no loudness: aw_spatializer_set_loudness has not been called");
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
+    const uint64_t cap_frames = (uint64_t)sp->loud_cap * (uint64_t)sp->loud_hop;
+    const int64_t n_hops = (int64_t)(std::min(sp->loud_frames, cap_frames) / (uint64_t)sp->loud_hop);     // complete hops only
+    std::vector<double> e((size_t)n * (size_t)std::max<int64_t>(n_hops, 1));
+    std::vector<unsigned long long> nf((size_t)n);
+    if (n_hops > 0)
+        AW_HIP_TRY(hipMemcpy2D(e.data(), (size_t)n_hops * 8, ld_hops(sp) + (size_t)first_stream * (size_t)sp->loud_cap, (size_t)sp->loud_cap * 8, (size_t)n_hops * 8,
+                               (size_t)n, hipMemcpyDeviceToHost));
+    AW_HIP_TRY(hipMemcpy(nf.data(), ld_nonfinite(sp) + first_stream, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int32_t i = 0; i < n; ++i) {
+        const awlo::Gated g = awlo::gate(e.data() + (size_t)i * (size_t)n_hops, n_hops, sp->loud_hop);
+        aw_stream_loudness &o = out[i];
+        o.integrated_lufs = g.integrated_lufs; o.relative_threshold_lufs = g.relative_threshold_lufs;
+        o.blocks = g.blocks; o.blocks_above_absolute = g.blocks_above_absolute; o.blocks_gated = g.blocks_gated;
+        o.reserved = 0;
+        o.frames = sp->loud_frames;
+        o.frames_dropped = sp->loud_frames > cap_frames ? sp->loud_frames - cap_frames : 0;
+        o.nonfinite = nf[(size_t)i];
+    }
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_spatializer_get_loudness_hops(aw_spatializer *sp, int32_t stream, int64_t first_hop, int64_t n, double *out) try {
+    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    if (stream < 0 || stream >= sp->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "stream out of range");
+    if (first_hop < 0 || n < 0 || first_hop > sp->loud_cap || n > sp->loud_cap - first_hop) return fail(AW_ERR_INVALID_ARGUMENT, "hops out of range");
+    if (n == 0) return AW_OK;
+    if (!out) return fail(AW_ERR_INVALID_ARGUMENT, "out_host is NULL");
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
+    AW_HIP_TRY(hipMemcpy(out, ld_hops(sp) + (size_t)stream * (size_t)sp->loud_cap + (size_t)first_hop, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_loudness_gain(double lufs, double target_lufs, float *gain) try {
+    if (!gain) return fail(AW_ERR_INVALID_ARGUMENT, "gain is NULL");
+    if (!awlo::gain_to_target(lufs, target_lufs, gain)) return fail(AW_ERR_INVALID_ARGUMENT, "loudness and target must be finite (a silent stream has no gain)");
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 

@@ -138,6 +138,14 @@ struct aw_spatializer {
     float applied_ceiling = 1.0f, applied_host_gain = 1.0f;
     bool applied_on_host = false;                 // PEAK_CEILING: the single-stream path computed it (applied_host_gain), else the call-local peaks hold it
     std::vector<float> applied_gains;
+    // integrated loudness of the four batch entries (aw_spatializer_set_loudness; rules: device/loudness.hpp).  One device allocation, made
+    // by set_loudness(1, max_seconds): [n_streams][2][4] double filter state, [n_streams] uint64 non-finite counts, [n_streams][loud_cap]
+    // double hop energies (those three are what a reset zeroes), then the two K-weighting sections' kernel tables.
+    bool loudness = false;
+    double sample_rate = 0.0;                     // the HRIR's
+    int64_t loud_hop = 0, loud_cap = 0;           // frames per hop (rate / 10), hops recorded per stream
+    uint64_t loud_frames = 0;                     // frames measured since the last reset (the same for every stream): fixes the hop index
+    unsigned char *d_loud = nullptr;
     int64_t host_chunk_streams = 0;               // streams per staged chunk of the last host call (0: the whole batch in one piece, serial)
     int64_t host_chunk_reserved = 0, host_reserved_frames = 0;   // aw_spatializer_reserve_host: the chunking its buffers were sized for, and up to which call length
     // what the last aw_spatializer_reserve spent where (microseconds): float64 table build on host threads, table upload (hipMalloc +

@@ -222,8 +222,8 @@ AW_API aw_status aw_spatializer_set_dither(aw_spatializer *sp, aw_dither mode, u
  *  - levels accumulate over every later batch call until aw_spatializer_reset_levels or aw_spatializer_reset.  Chunking a batch by
  *    streams (AW_HOST_CHUNK_MB), sharding it over handles, pinned or pageable, aligned or unaligned buffers change no output bit and
  *    no field but energy's summation order; splitting calls in time changes none either under AW_GAIN_NONE and AW_GAIN_FIXED.
- *  - peak and energy are raw material: loudness in LUFS (K-weighting), true-peak oversampling, limiters and compressors are a host's
- *    business and are not provided. */
+ *  - peak and energy are raw material.  Integrated loudness in LUFS (K-weighting and gating, ITU-R BS.1770) is provided:
+ *    aw_spatializer_set_loudness below.  True-peak oversampling, limiters and compressors are a host's business and are not provided. */
 typedef struct aw_stream_levels {
     float    peak[2];      /* max |y| per ear (left, right) over finite samples, before gain */
     float    gain;         /* the gain the last call applied to this stream (1 if none) */
@@ -253,6 +253,51 @@ AW_API aw_status aw_spatializer_reset_levels(aw_spatializer *sp);
  * ignored.  A NULL handle, an unknown mode, a bad n, a NaN / inf gain or a bad ceiling returns AW_ERR_INVALID_ARGUMENT before any HIP
  * call, and the previous setting stays. */
 AW_API aw_status aw_spatializer_set_gain(aw_spatializer *sp, aw_gain_mode mode, const float *gains_host, int32_t n, float ceiling);
+/* Per-stream integrated loudness (ITU-R BS.1770-4) of the four batch entries, measured on the device from the float32 output y BEFORE
+ * the gain — the level meter's tap — so that a host can bring every stream to a target such as -16 or -23 LUFS without moving float32
+ * output over PCIe: pass one measures, aw_loudness_gain gives the AW_GAIN_FIXED gains, pass two writes the file
+ * (examples/offline_batch_loudness.c).  Off by default; while it is off every entry launches the kernels and writes the bytes it always
+ * has.  The planar entry and the engine / realtime adapters are not measured.
+ *  - K-weighting: per ear, the shelf and the high-pass biquad in Float64, their coefficients derived for the HRIR's sample rate
+ *    (aw_hrir_sample_rate) from the analog prototypes behind the standard's 48 kHz table (shelf f0 = 1681.974450955533 Hz,
+ *    G = 3.999843853973347 dB, Q = 0.7071752369554196, band gain exponent 0.4996667741545416; high-pass f0 = 38.13547087602444 Hz,
+ *    Q = 0.5003270373238773, numerator 1, -2, 1; bilinear transform with K = tan(pi f0 / fs)).  At 48 kHz these are the table values.
+ *    A NaN or +-inf y enters the filters as 0 and counts in nonfinite.
+ *  - hop energies: a hop is rate / 10 frames (100 ms); E[s][h] = the sum of (k_L^2 + k_R^2) over the frames of hop h of stream s, k the
+ *    K-weighted output, both ears with channel weight 1.  The device keeps [stream][ceil(10 max_seconds)] doubles; frames past that
+ *    capacity are not measured and are reported in frames_dropped.  aw_spatializer_get_loudness_hops returns them raw: momentary and
+ *    short-term loudness and LRA are sums over them that a host can form.
+ *  - gating, on the host at read-out, over complete hops only: block j covers hops j .. j+3 (400 ms, 75 % overlap),
+ *    z_j = (E[j] + .. + E[j+3]) / (4 hop), l_j = -0.691 + 10 log10 z_j; the absolute gate keeps l_j > -70; the relative threshold is
+ *    -0.691 + 10 log10(mean of z over those blocks) - 10; integrated_lufs is -0.691 + 10 log10(mean of z over the blocks above both).
+ *    With no such block it is -INFINITY (and so is the threshold with no block above the absolute gate).
+ *  - chunking a batch by streams (AW_HOST_CHUNK_MB), pinned or pageable buffers and sharding over handles change no bit of any hop
+ *    energy; splitting calls in time changes them by Float64 summation order only, and a given split gives the same bits every time.
+ *  - aw_spatializer_reset and aw_spatializer_reset_levels zero the hop energies, the filter state and the frame count. */
+typedef struct aw_stream_loudness {
+    double   integrated_lufs;           /* gated loudness, LUFS; -INFINITY when no block passes the gates */
+    double   relative_threshold_lufs;   /* the relative gate, LUFS */
+    uint32_t blocks;                    /* complete 400 ms blocks */
+    uint32_t blocks_above_absolute;     /* ... above -70 LUFS */
+    uint32_t blocks_gated;              /* ... above both gates: what integrated_lufs averages */
+    uint32_t reserved;                  /* 0 */
+    uint64_t frames;                    /* frames of the measured calls since the last reset */
+    uint64_t frames_dropped;            /* of those, frames past the capacity: not measured */
+    uint64_t nonfinite;                 /* NaN / inf samples, both ears, that entered the filters as 0 */
+} aw_stream_loudness;                   /* 56 bytes */
+/* on != 0: allocates the filter state and the hop energies of max_seconds per stream at once (never on the process path; a capacity
+ * other than the one held makes new, empty records) and measures every later batch call; 0: stops measuring, the records stay readable
+ * and max_seconds is ignored.  A NULL handle, an HRIR sample rate that is not a finite positive multiple of 10 Hz, or a max_seconds that
+ * is <= 0 or not finite returns AW_ERR_INVALID_ARGUMENT before any HIP call.  Do not call it while a process call on the same handle is
+ * running. */
+AW_API aw_status aw_spatializer_set_loudness(aw_spatializer *sp, int32_t on, double max_seconds);
+/* Synchronises the context's stream, copies the hop energies of streams [first_stream, first_stream + n) and gates them on the host. */
+AW_API aw_status aw_spatializer_get_loudness(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_loudness *out_host);
+/* The raw hop energies [first_hop, first_hop + n) of one stream (the hop in progress included); the range must lie in the capacity. */
+AW_API aw_status aw_spatializer_get_loudness_hops(aw_spatializer *sp, int32_t stream, int64_t first_hop, int64_t n, double *out_host);
+/* *gain = 10^((target_lufs - lufs) / 20) as float32.  A NULL gain, a non-finite loudness (a silent stream measures -INFINITY) or target,
+ * or a gain that is no finite float32 returns AW_ERR_INVALID_ARGUMENT and leaves *gain alone. */
+AW_API aw_status aw_loudness_gain(double lufs, double target_lufs, float *gain);
 /* StereoAudioProcessing.process shape (AudioPipeline.swift:3-11) for a 1-stream, 2-channel
  * spatializer: planar HOST buffers, input_right may be NULL (mono duplication). Zero latency. */
 AW_API aw_status aw_spatializer_process_planar(aw_spatializer *sp, const float *input_left, const float *input_right,
@@ -276,7 +321,8 @@ AW_API int32_t aw_spatializer_channel_count(const aw_spatializer *sp);
  *   growing the context's scratch pool, 13 device or page-locked allocations and 14 blocking table uploads made so far on behalf
  *   of the context's handles (a reserved process path makes neither), 15 streams per staged chunk of the last host-entry call,
  * 18 frames processed since create / the last aw_spatializer_reset (the dither's frame position, aw_spatializer_set_dither),
- * 19 the level meter is on (aw_spatializer_set_metering), 20 the aw_gain_mode of the batch entries (aw_spatializer_set_gain). */
+ * 19 the level meter is on (aw_spatializer_set_metering), 20 the aw_gain_mode of the batch entries (aw_spatializer_set_gain),
+ * 21 the loudness measurement is on (aw_spatializer_set_loudness). */
 AW_API int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what);
 /* Average device time of the dominant kernel over the launches since the last call (HIP events
  * on the context stream); used for bench.py's roofline object.  Returns launches counted. */

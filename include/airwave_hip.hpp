@@ -120,6 +120,19 @@ class Spatializer {
     void setGainNone() { check(aw_spatializer_set_gain(h_, AW_GAIN_NONE, nullptr, 0, 0.0f)); }
     void setGainFixed(const std::vector<float> &gains) { check(aw_spatializer_set_gain(h_, AW_GAIN_FIXED, gains.data(), (int32_t)gains.size(), 0.0f)); }
     void setGainPeakCeiling(float ceiling) { check(aw_spatializer_set_gain(h_, AW_GAIN_PEAK_CEILING, nullptr, 0, ceiling)); }
+    // per-stream BS.1770 integrated loudness of the batch entries (aw_stream_loudness)
+    void setLoudness(bool on, double maxSeconds = 0.0) { check(aw_spatializer_set_loudness(h_, on ? 1 : 0, maxSeconds)); }
+    std::vector<aw_stream_loudness> loudness() {
+        std::vector<aw_stream_loudness> out((size_t)aw_spatializer_stream_count(h_));
+        check(aw_spatializer_get_loudness(h_, 0, (int32_t)out.size(), out.data()));
+        return out;
+    }
+    std::vector<double> loudnessHops(int32_t stream, int64_t firstHop, int64_t count) {
+        std::vector<double> out((size_t)count);
+        check(aw_spatializer_get_loudness_hops(h_, stream, firstHop, count, out.data()));
+        return out;
+    }
+    static float loudnessGain(double lufs, double targetLufs) { float g = 1.0f; check(aw_loudness_gain(lufs, targetLufs, &g)); return g; }
     int64_t info(int32_t what) const { return aw_spatializer_info(h_, what); }
     void reset() { check(aw_spatializer_reset(h_)); }
     aw_spatializer *get() const { return h_; }

@@ -123,6 +123,37 @@ public final class BatchSpatializer {
         guard st == AW_OK else { throw BatchSpatializer.error(st) }
     }
 
+    /// BS.1770 integrated loudness of every later batch call (`aw_spatializer_set_loudness`), measured per stream before the gain;
+    /// switching it on allocates the hop energies of `maxSeconds` per stream here, not on the process path.
+    public func setLoudness(_ on: Bool, maxSeconds: Double = 0) throws {
+        let st = aw_spatializer_set_loudness(handle, on ? 1 : 0, maxSeconds)
+        guard st == AW_OK else { throw BatchSpatializer.error(st) }
+    }
+
+    /// The gated loudness of every stream (`aw_spatializer_get_loudness`): integrated LUFS, the relative threshold, block counts, frames
+    /// measured and dropped, non-finite samples.  Synchronises the context's stream.
+    public func loudness() throws -> [aw_stream_loudness] {
+        let n = aw_spatializer_stream_count(handle)
+        var out = [aw_stream_loudness](repeating: aw_stream_loudness(), count: Int(n))
+        let st = out.withUnsafeMutableBufferPointer { aw_spatializer_get_loudness(handle, 0, n, $0.baseAddress) }
+        guard st == AW_OK else { throw BatchSpatializer.error(st) }
+        return out
+    }
+
+    /// The raw 100 ms hop energies of one stream (`aw_spatializer_get_loudness_hops`): material for momentary / short-term loudness.
+    public func loudnessHops(stream: Int32, firstHop: Int64, count: Int64) throws -> [Double] {
+        var out = [Double](repeating: 0, count: Int(count))
+        let st = out.withUnsafeMutableBufferPointer { aw_spatializer_get_loudness_hops(handle, stream, firstHop, count, $0.baseAddress) }
+        guard st == AW_OK else { throw BatchSpatializer.error(st) }
+        return out
+    }
+
+    /// The gain that brings a measured loudness to a target (`aw_loudness_gain`); nil for a silent stream (-infinity LUFS).
+    public static func loudnessGain(lufs: Double, target: Double) -> Float? {
+        var g: Float = 1
+        return aw_loudness_gain(lufs, target, &g) == AW_OK ? g : nil
+    }
+
     /// `reserve` plus the host entry's device-side staging: `process(hostInput:…)` never allocates afterwards either.
     public func reserveHost(maxFrames: Int64) throws {
         let st = aw_spatializer_reserve_host(handle, maxFrames)
