@@ -63,6 +63,9 @@ SIGNATURES = {
     "aw_spatializer_get_loudness": (_I32, [_V, _I32, _I32, _V]),
     "aw_spatializer_get_loudness_hops": (_I32, [_V, _I32, _I64, _I64, _V]),
     "aw_loudness_gain": (_I32, [_D, _D, c_float_p]),
+    "aw_spatializer_set_true_peak": (_I32, [_V, _I32]),
+    "aw_spatializer_get_true_peak": (_I32, [_V, _I32, _I32, _V]),
+    "aw_true_peak_filter": (_I32, [c_float_p]),
     "aw_spatializer_reset": (_I32, [_V]),
     "aw_spatializer_stream_count": (_I32, [_V]),
     "aw_spatializer_channel_count": (_I32, [_V]),
@@ -154,6 +157,12 @@ class StreamLoudness(ctypes.Structure):
     _fields_ = [("integrated_lufs", ctypes.c_double), ("relative_threshold_lufs", ctypes.c_double), ("blocks", ctypes.c_uint32),
                 ("blocks_above_absolute", ctypes.c_uint32), ("blocks_gated", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
                 ("frames", ctypes.c_uint64), ("frames_dropped", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64)]
+
+
+class StreamTruePeak(ctypes.Structure):
+    """aw_stream_true_peak (32 bytes)."""
+    _fields_ = [("true_peak", ctypes.c_float * 2), ("call_true_peak", ctypes.c_float), ("reserved", ctypes.c_uint32),
+                ("frames", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64)]
 
 
 _lib = None

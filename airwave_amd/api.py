@@ -78,7 +78,7 @@ _FORMAT_DTYPE = {0: np.dtype(np.float32), 1: np.dtype(np.int16), 2: np.dtype(np.
 # aw_dither (include/airwave_hip.h): dither of the s16 / s24 encode (Spatializer.set_dither)
 DITHER_MODES = {"none": 0, "tpdf": 1, "tpdf_hp": 2}
 # aw_gain_mode: output gain of the batch entries (Spatializer.set_gain)
-GAIN_MODES = {"none": 0, "fixed": 1, "peak_ceiling": 2}
+GAIN_MODES = {"none": 0, "fixed": 1, "peak_ceiling": 2, "true_peak_ceiling": 3}
 # aw_stream_levels, byte for byte (Spatializer.levels)
 LEVELS_DTYPE = np.dtype([("peak", np.float32, (2,)), ("gain", np.float32), ("reserved", np.uint32), ("energy", np.float64, (2,)),
                          ("frames", np.uint64), ("clipped", np.uint64), ("nonfinite", np.uint64)], align=False)
@@ -87,6 +87,17 @@ LEVELS_DTYPE = np.dtype([("peak", np.float32, (2,)), ("gain", np.float32), ("res
 LOUDNESS_DTYPE = np.dtype([("integrated_lufs", np.float64), ("relative_threshold_lufs", np.float64), ("blocks", np.uint32),
                            ("blocks_above_absolute", np.uint32), ("blocks_gated", np.uint32), ("reserved", np.uint32),
                            ("frames", np.uint64), ("frames_dropped", np.uint64), ("nonfinite", np.uint64)], align=False)
+
+# aw_stream_true_peak, byte for byte (Spatializer.true_peak)
+TRUE_PEAK_DTYPE = np.dtype([("true_peak", np.float32, (2,)), ("call_true_peak", np.float32), ("reserved", np.uint32), ("frames", np.uint64),
+                            ("nonfinite", np.uint64)], align=False)
+
+
+def true_peak_filter() -> np.ndarray:
+    """aw_true_peak_filter: the interpolator's float32 coefficients c[p][k], p = 1 .. 3, as a [3][12] array."""
+    c = np.zeros(36, np.float32)
+    _check(_capi.load().aw_true_peak_filter(_fp(c)))
+    return c.reshape(3, 12)
 
 
 def loudness_gain(lufs: float, target_lufs: float) -> float:
@@ -450,7 +461,8 @@ class Spatializer:
                 "position_frames": g(18),       # frames processed since creation / the last reset (the dither's frame position)
                 "metering": g(19),              # the level meter is on (set_metering)
                 "gain_mode": g(20),             # aw_gain_mode of the batch entries (set_gain)
-                "loudness": g(21)}              # the loudness measurement is on (set_loudness)
+                "loudness": g(21),              # the loudness measurement is on (set_loudness)
+                "true_peak": g(22)}             # the true-peak measurement is on (set_true_peak)
 
     def process_device(self, in_ptr: int, out_ptr: int, frames: int) -> None:
         _check(self._lib.aw_spatializer_process(self._h, ctypes.c_void_p(in_ptr), ctypes.c_void_p(out_ptr), frames))
@@ -551,7 +563,8 @@ class Spatializer:
 
     def set_gain(self, mode, gains=None, ceiling: Optional[float] = None) -> None:
         """aw_spatializer_set_gain: 'none'; 'fixed' with one gain (every stream) or one per stream; 'peak_ceiling' with 0 < ceiling <= 1,
-        which scales every stream of every call down to the ceiling where that call's peak exceeds it (or the aw_gain_mode code)."""
+        which scales every stream of every call down to the ceiling where that call's peak exceeds it; 'true_peak_ceiling' likewise over
+        the call's true peak (or the aw_gain_mode code)."""
         if isinstance(mode, str):
             if mode not in GAIN_MODES:
                 raise ValueError(f"unknown gain mode {mode!r} (one of {', '.join(GAIN_MODES)})")
@@ -568,9 +581,9 @@ class Spatializer:
                 raise ValueError(f"gains must be 1 or {self.n_streams} values, got shape {g.shape}")
             if not np.all(np.isfinite(g)):
                 raise ValueError("gains must be finite")
-        elif mode == GAIN_MODES["peak_ceiling"]:
+        elif mode in (GAIN_MODES["peak_ceiling"], GAIN_MODES["true_peak_ceiling"]):
             if ceiling is None or not (0.0 < float(np.float32(ceiling)) <= 1.0):
-                raise ValueError(f"peak_ceiling needs 0 < ceiling <= 1, got {ceiling!r}")
+                raise ValueError(f"a ceiling gain needs 0 < ceiling <= 1, got {ceiling!r}")
             c = float(ceiling)
         _check(self._lib.aw_spatializer_set_gain(self._h, mode, None if g is None else _fp(g), 0 if g is None else int(g.size), ctypes.c_float(c)))
 
@@ -599,6 +612,22 @@ class Spatializer:
             raise ValueError(f"stream {stream}, hops [{first_hop}, {first_hop + n}) out of range")
         out = np.zeros(n, np.float64)
         _check(self._lib.aw_spatializer_get_loudness_hops(self._h, stream, first_hop, n, ctypes.c_void_p(out.ctypes.data)))
+        return out
+
+    def set_true_peak(self, on: bool = True) -> None:
+        """aw_spatializer_set_true_peak: the true peak (4x oversampled) of every later batch call, per stream, measured before the gain.
+        Switching it on allocates the records here, not on the process path."""
+        _check(self._lib.aw_spatializer_set_true_peak(self._h, int(bool(on))))
+
+    def true_peak(self, first_stream: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """aw_spatializer_get_true_peak: the records of n streams from first_stream on (default: all) as a structured array of
+        TRUE_PEAK_DTYPE.  Synchronises the context's stream."""
+        first_stream = int(first_stream)
+        n = self.n_streams - first_stream if n is None else int(n)
+        if first_stream < 0 or n < 0 or first_stream + n > self.n_streams:
+            raise ValueError(f"streams [{first_stream}, {first_stream + n}) outside [0, {self.n_streams})")
+        out = np.zeros(n, TRUE_PEAK_DTYPE)
+        _check(self._lib.aw_spatializer_get_true_peak(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
         return out
 
     def reset(self) -> None:

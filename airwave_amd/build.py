@@ -39,6 +39,7 @@ SOURCES = [
     "device/prep_kernels.hip",
     "device/pcm_kernels.hip",
     "device/loudness_kernels.hip",
+    "device/truepeak_kernels.hip",
     "runtime.cpp",
     "eq_runtime.cpp",
     "host/eq.cpp",

@@ -1,0 +1,74 @@
+// truepeak_kernels.hip — gfx950 kernel of the per-stream true peak (device code in truepeak_tile.hpp).
+#include "truepeak_kernels.hpp"
+
+namespace awk {
+
+namespace {
+
+struct TpGpuCtx {
+    float *lds_;
+    __device__ __forceinline__ int tid() const { return (int)threadIdx.x; }
+    __device__ __forceinline__ float *lds() const { return lds_; }
+    __device__ __forceinline__ void barrier() const { __syncthreads(); }
+    __device__ __forceinline__ void ld16(const float *g, float (&x)[4]) const {
+        const float4 v = *reinterpret_cast<const float4 *>(g);
+        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+    }
+    __device__ __forceinline__ void st16(float *l, const float (&x)[4]) const { *reinterpret_cast<float4 *>(l) = make_float4(x[0], x[1], x[2], x[3]); }
+    __device__ __forceinline__ void ld_lds16(const float *l, float *x) const {
+        const float4 v = *reinterpret_cast<const float4 *>(l);
+        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+    }
+    __device__ __forceinline__ void ld_lds8(const float *l, float *x) const {
+        const float2 v = *reinterpret_cast<const float2 *>(l);
+        x[0] = v.x; x[1] = v.y;
+    }
+    // every wave is launched whole and keeps its lanes together up to here, so the shuffles see all 64 lanes
+    __device__ __forceinline__ uint32_t wave_max(uint32_t v) const {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) { const uint32_t o = __shfl_xor(v, m); v = o > v ? o : v; }
+        return v;
+    }
+    __device__ __forceinline__ unsigned wave_sum(unsigned v) const {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+        return v;
+    }
+    __device__ __forceinline__ void atomic_max(uint32_t *a, uint32_t v) const { atomicMax(a, v); }
+    __device__ __forceinline__ void atomic_add(unsigned long long *a, unsigned long long v) const { atomicAdd(a, v); }
+};
+
+}  // namespace
+
+// grid: (tiles of a stream, streams)
+__global__ void __launch_bounds__(kTpThreads) aw_true_peak_kernel(TruePeakParams p) {
+    __shared__ __align__(16) float tp_lds[kTpLdsFloats];
+    TpGpuCtx ctx{tp_lds};
+    truepeak_tile<TpGpuCtx>(ctx, p, (long long)blockIdx.y, (long long)blockIdx.x);
+}
+
+hipError_t prepare_truepeak_kernels() { return hipSuccess; }      // static LDS under 64 KB: nothing to set
+
+hipError_t launch_truepeak(const TruePeakParams &p, hipStream_t stream) {
+    if (p.n_streams <= 0 || p.frames <= 0) return hipSuccess;
+    if (!p.in || !p.hist_in || !p.hist_out || p.hist_in == p.hist_out || !p.call_tp || (p.tp_bits && !p.nonfinite) ||
+        (reinterpret_cast<uintptr_t>(p.in) & 3u))
+        return hipErrorInvalidValue;
+    const long long tiles = (p.frames + kTpTile - 1) / kTpTile;
+    if (tiles > 0x7FFFFFFFll) return hipErrorInvalidValue;
+    // the y dimension of a grid holds 65,535 workgroups: more streams go in slices
+    for (int s0 = 0; s0 < p.n_streams; s0 += 65535) {
+        TruePeakParams q = p;
+        const int ns = p.n_streams - s0 < 65535 ? p.n_streams - s0 : 65535;
+        q.in = p.in + (long long)s0 * p.frames * 2; q.n_streams = ns;
+        q.hist_in = p.hist_in + (size_t)s0 * 2 * awtp::kHistory; q.hist_out = p.hist_out + (size_t)s0 * 2 * awtp::kHistory;
+        if (p.tp_bits) { q.tp_bits = p.tp_bits + 2 * (size_t)s0; q.nonfinite = p.nonfinite + s0; }
+        q.call_tp = p.call_tp + s0;
+        hipLaunchKernelGGL(aw_true_peak_kernel, dim3((unsigned)tiles, (unsigned)ns), dim3(kTpThreads), 0, stream, q);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace awk

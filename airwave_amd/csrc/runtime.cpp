@@ -17,6 +17,7 @@
 #include "device/loudness_kernels.hpp"
 #include "device/pcm.hpp"
 #include "device/pcm_kernels.hpp"
+#include "device/truepeak_kernels.hpp"
 #include "host/eq.hpp"
 #include "host/tables.hpp"
 
@@ -236,6 +237,7 @@ static aw_status context_create_impl(int32_t device, void *ext_stream, bool use_
     if (e == hipSuccess) e = awk::prepare_lw_kernels();
     if (e == hipSuccess) e = awk::prepare_eq_kernels();
     if (e == hipSuccess) e = awk::prepare_loudness_kernels();
+    if (e == hipSuccess) e = awk::prepare_truepeak_kernels();
     if (e == hipSuccess) e = awk::prepare_prep_kernels();
     awh::Twiddles tw;
     awh::build_twiddles(tw);
@@ -738,6 +740,7 @@ void aw_spatializer_destroy(aw_spatializer *sp) {
     if (sp->d_clip) (void)hipFree(sp->d_clip);
     if (sp->d_levels) (void)hipFree(sp->d_levels);
     if (sp->d_loud) (void)hipFree(sp->d_loud);
+    if (sp->d_tp) (void)hipFree(sp->d_tp);
     if (sp->k0) (void)hipEventDestroy(sp->k0);
     if (sp->k1) (void)hipEventDestroy(sp->k1);
     for (auto &pr : sp->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -773,6 +776,7 @@ int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what) {
         case 19: return sp->metering ? 1 : 0;     // the level meter is on (aw_spatializer_set_metering)
         case 20: return sp->gain_mode;            // aw_gain_mode of the batch entries (aw_spatializer_set_gain)
         case 21: return sp->loudness ? 1 : 0;     // the loudness measurement is on (aw_spatializer_set_loudness)
+        case 22: return sp->true_peak ? 1 : 0;    // the true-peak measurement is on (aw_spatializer_set_true_peak)
         default: return -1;
     }
 }
@@ -1428,6 +1432,7 @@ static LwCallPlan sp_begin_call(aw_spatializer *sp, int64_t frames, uint64_t *po
 
 /* ---- level meter and output gain of the batch entries (aw_spatializer_set_metering / _set_gain; rules: device/levels.hpp) ------------- */
 static_assert(AW_GAIN_NONE == awl::kGainNone && AW_GAIN_FIXED == awl::kGainFixed && AW_GAIN_PEAK_CEILING == awl::kGainPeakCeiling, "aw_gain_mode");
+static_assert(AW_GAIN_TRUE_PEAK_CEILING == 3, "aw_gain_mode");
 static_assert(sizeof(aw_stream_levels) == 56 && sizeof(awl::Record) == 40, "aw_stream_levels");
 static awl::Record *lv_records(const aw_spatializer *sp) { return reinterpret_cast<awl::Record *>(sp->d_levels); }
 static uint32_t *lv_call_peaks(const aw_spatializer *sp) { return reinterpret_cast<uint32_t *>(sp->d_levels + (size_t)sp->n_streams * sizeof(awl::Record)); }
@@ -1460,8 +1465,15 @@ static aw_status lv_begin_call(aw_spatializer *sp, int64_t frames, bool device) 
     return AW_OK;
 }
 
+// the true-peak kernel runs (below): the measurement is on, or the gain wants the call's true peaks
+static bool tp_runs(const aw_spatializer *sp) { return sp->true_peak || sp->gain_mode == AW_GAIN_TRUE_PEAK_CEILING; }
+static uint32_t *tp_call_peaks(const aw_spatializer *sp);
+
+// AW_GAIN_TRUE_PEAK_CEILING is the kernels' peak-ceiling gain over the call-local TRUE peaks
 static awk::PcmGain lv_gain_launch(const aw_spatializer *sp, int64_t s0) {
-    return awk::PcmGain{sp->gain_mode, sp->gain_ceiling, lv_gains(sp) + s0, lv_call_peaks(sp) + s0, sp->metering ? lv_records(sp) + s0 : nullptr};
+    awl::Record *rec = sp->metering ? lv_records(sp) + s0 : nullptr;
+    if (sp->gain_mode == AW_GAIN_TRUE_PEAK_CEILING) return awk::PcmGain{awl::kGainPeakCeiling, sp->gain_ceiling, lv_gains(sp) + s0, tp_call_peaks(sp) + s0, rec};
+    return awk::PcmGain{sp->gain_mode, sp->gain_ceiling, lv_gains(sp) + s0, lv_call_peaks(sp) + s0, rec};
 }
 
 // After the kernels of the streams [s0, s0 + ns) have written their float32 output to f_out: meter it, and — float32 output with a gain
@@ -1500,6 +1512,7 @@ static float lv_host_call(aw_spatializer *sp, const float *y, size_t n) {
     float g = 1.0f;
     if (sp->gain_mode == AW_GAIN_FIXED) g = sp->gains[0];
     else if (sp->gain_mode == AW_GAIN_PEAK_CEILING) g = awl::auto_gain(awl::bits_float(std::max(pk[0], pk[1])), sp->gain_ceiling);
+    else if (sp->gain_mode == AW_GAIN_TRUE_PEAK_CEILING) g = awl::auto_gain(awl::bits_float(sp->tp_pinned_call_bits), sp->gain_ceiling);
     sp->applied_host_gain = g;
     return g;
 }
@@ -1535,6 +1548,68 @@ static aw_status ld_measure(aw_spatializer *sp, const float *y, int64_t s0, int 
 static aw_status ld_reset(aw_spatializer *sp) {
     sp->loud_frames = 0;
     if (sp->d_loud) AW_HIP_TRY(hipMemsetAsync(sp->d_loud, 0, ld_record_bytes(sp), sp->ctx->stream));
+    return AW_OK;
+}
+
+/* ---- true peak of the batch entries (aw_spatializer_set_true_peak, AW_GAIN_TRUE_PEAK_CEILING; rules: device/truepeak.hpp, kernel:
+ * device/truepeak_tile.hpp) ---- */
+static_assert(sizeof(aw_stream_true_peak) == 32, "aw_stream_true_peak");
+constexpr size_t kTpHistFloats = 2 * (size_t)awtp::kHistory;
+static unsigned long long *tp_nonfinite(const aw_spatializer *sp) { return reinterpret_cast<unsigned long long *>(sp->d_tp); }
+static uint32_t *tp_peaks(const aw_spatializer *sp) { return reinterpret_cast<uint32_t *>(tp_nonfinite(sp) + sp->n_streams); }
+static uint32_t *tp_call_peaks(const aw_spatializer *sp) { return tp_peaks(sp) + 2 * (size_t)sp->n_streams; }
+static float *tp_history(const aw_spatializer *sp, int slot) {
+    return reinterpret_cast<float *>(tp_call_peaks(sp) + sp->n_streams) + (size_t)slot * (size_t)sp->n_streams * kTpHistFloats;
+}
+static size_t tp_record_bytes(const aw_spatializer *sp) { return (size_t)sp->n_streams * (8 + 3 * 4); }
+static size_t tp_bytes(const aw_spatializer *sp) { return tp_record_bytes(sp) + 2 * (size_t)sp->n_streams * kTpHistFloats * sizeof(float); }
+
+// the one allocation (the setters make it: never the process path), zeroed, and the coefficients
+static aw_status tp_buffers(aw_spatializer *sp) {
+    if (sp->d_tp) return AW_OK;
+    awtp::filter(sp->tp_filter);
+    AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sp->d_tp), tp_bytes(sp)));
+    sp->ctx->device_allocs += 1;
+    AW_HIP_TRY(hipMemsetAsync(sp->d_tp, 0, tp_bytes(sp), sp->ctx->stream));
+    return AW_OK;
+}
+
+// frames of unmeasured calls are not predecessors: the kernel starts (again) behind silence
+static aw_status tp_zero_history(aw_spatializer *sp) {
+    AW_HIP_TRY(hipMemsetAsync(tp_history(sp, 0), 0, 2 * (size_t)sp->n_streams * kTpHistFloats * sizeof(float), sp->ctx->stream));
+    return AW_OK;
+}
+
+// once per call that runs the kernel, before its first launch
+static aw_status tp_begin_call(aw_spatializer *sp, int64_t frames) {
+    if (sp->true_peak) sp->tp_frames += (uint64_t)frames;
+    AW_HIP_TRY(hipMemsetAsync(tp_call_peaks(sp), 0, (size_t)sp->n_streams * sizeof(uint32_t), sp->ctx->stream));
+    return AW_OK;
+}
+
+// The float32 output y of the streams [s0, s0 + ns) of a call (dense: `frames` apart), before any gain.  A workgroup's tile lies in one
+// stream and the history is per stream, so chunks of streams are independent.
+static aw_status tp_measure(aw_spatializer *sp, const float *y, int64_t s0, int ns, int64_t frames) {
+    SpStageTimer tm(sp);
+    if (sp->profiling) tm.begin();
+    awk::TruePeakParams p{};
+    p.in = y; p.frames = frames; p.n_streams = ns;
+    p.hist_in = tp_history(sp, sp->tp_cur) + (size_t)s0 * kTpHistFloats;
+    p.hist_out = tp_history(sp, sp->tp_cur ^ 1) + (size_t)s0 * kTpHistFloats;
+    if (sp->true_peak) { p.tp_bits = tp_peaks(sp) + 2 * (size_t)s0; p.nonfinite = tp_nonfinite(sp) + s0; }
+    p.call_tp = tp_call_peaks(sp) + s0;
+    std::memcpy(p.c, sp->tp_filter, sizeof(p.c));
+    AW_HIP_TRY(awk::launch_truepeak(p, sp->ctx->stream));
+    sp->tp_ran = true;
+    if (sp->profiling) tm.end("aw_true_peak_kernel");
+    return AW_OK;
+}
+
+// the records and the history start over (the setting stays)
+static aw_status tp_reset(aw_spatializer *sp) {
+    sp->tp_frames = 0;
+    sp->tp_pinned_call_bits = 0;
+    if (sp->d_tp) AW_HIP_TRY(hipMemsetAsync(sp->d_tp, 0, tp_bytes(sp), sp->ctx->stream));
     return AW_OK;
 }
 
@@ -1718,16 +1793,21 @@ static aw_status batch_begin(aw_spatializer *sp, BatchCall *call, unsigned long 
     call->clip = clip;
     call->metered = metered;
     if (metered) {
-        const aw_status st = lv_begin_call(sp, call->frames, true);
+        aw_status st = lv_begin_call(sp, call->frames, true);
         if (st != AW_OK) return st;
         call->loud0 = sp->loud_frames;
         if (sp->loudness) sp->loud_frames += (uint64_t)call->frames;
+        if (tp_runs(sp) && (st = tp_begin_call(sp, call->frames)) != AW_OK) return st;
     }
     if (zero_clip) AW_HIP_TRY(hipMemsetAsync(clip, 0, sizeof(unsigned long long), sp->ctx->stream));
     return AW_OK;
 }
 
-static void batch_end(aw_spatializer *sp) { sp->hist_cur ^= 1; }      // every chunk's kernels are queued: the history they wrote is the next call's
+// every chunk's kernels are queued: the history they wrote is the next call's
+static void batch_end(aw_spatializer *sp) {
+    sp->hist_cur ^= 1;
+    if (sp->tp_ran) { sp->tp_cur ^= 1; sp->tp_ran = false; }
+}
 
 // The streams [s0, s0 + ns) of a call, on the context's stream: pcm_src -> decode into f_in -> kernels -> meter / gain -> encode of f_out
 // into pcm_dst.  A float32 side has no conversion and no staging: the kernels read pcm_src / write pcm_dst, f_in / f_out is not looked at.
@@ -1738,6 +1818,7 @@ static aw_status batch_chunk(aw_spatializer *sp, const BatchCall &call, int64_t 
     float *y = call.enc ? f_out : static_cast<float *>(pcm_dst);
     if (st == AW_OK) st = sp_run_streams(sp, call.lw, (int)s0, ns, x, y, call.frames);
     if (st == AW_OK && call.metered && sp->loudness) st = ld_measure(sp, y, s0, ns, call.frames, call.loud0);      // (before the gain)
+    if (st == AW_OK && call.metered && tp_runs(sp)) st = tp_measure(sp, y, s0, ns, call.frames);                   // (the gain may read its result)
     if (st == AW_OK && call.metered) st = lv_after_run(sp, y, s0, ns, call.frames, !call.enc);
     if (st == AW_OK && call.enc) st = pcm_encode(sp, call, y, pcm_dst, s0, ns);
     return st;
@@ -1753,9 +1834,14 @@ static aw_status batch_run_pinned(aw_spatializer *sp, int64_t frames, bool meter
         st = ld_measure(sp, sp->h_pin_out, 0, 1, frames, sp->loud_frames);
         sp->loud_frames += (uint64_t)frames;
     }
-    if (st != AW_OK) return st;
+    const bool tp = metered && tp_runs(sp);
+    if (st == AW_OK && tp) st = tp_begin_call(sp, frames);
+    if (st == AW_OK && tp) st = tp_measure(sp, sp->h_pin_out, 0, 1, frames);
+    if (st != AW_OK) { sp->tp_ran = false; return st; }
     batch_end(sp);
     AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
+    if (tp && sp->gain_mode == AW_GAIN_TRUE_PEAK_CEILING)       // the CPU gains this call: it needs the call's true peak
+        AW_HIP_TRY(hipMemcpy(&sp->tp_pinned_call_bits, tp_call_peaks(sp), sizeof(uint32_t), hipMemcpyDeviceToHost));
     return AW_OK;
 }
 
@@ -2007,7 +2093,8 @@ static aw_status lv_reset(aw_spatializer *sp) {
     sp->metered_frames = 0;
     sp->applied_mode = AW_GAIN_NONE;
     if (sp->d_levels) AW_HIP_TRY(hipMemsetAsync(sp->d_levels, 0, (size_t)sp->n_streams * (sizeof(awl::Record) + sizeof(uint32_t)), sp->ctx->stream));
-    return ld_reset(sp);
+    const aw_status st = ld_reset(sp);
+    return st == AW_OK ? tp_reset(sp) : st;
 }
 
 aw_status aw_spatializer_reset(aw_spatializer *sp) try {
@@ -2050,7 +2137,8 @@ aw_status aw_spatializer_get_levels(aw_spatializer *sp, int32_t first_stream, in
     std::vector<awl::Record> rec((size_t)n);
     std::vector<uint32_t> peaks((size_t)n);
     AW_HIP_TRY(hipMemcpy(rec.data(), lv_records(sp) + first_stream, (size_t)n * sizeof(awl::Record), hipMemcpyDeviceToHost));
-    AW_HIP_TRY(hipMemcpy(peaks.data(), lv_call_peaks(sp) + first_stream, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const uint32_t *call_peaks = sp->applied_mode == AW_GAIN_TRUE_PEAK_CEILING && sp->d_tp ? tp_call_peaks(sp) : lv_call_peaks(sp);
+    AW_HIP_TRY(hipMemcpy(peaks.data(), call_peaks + first_stream, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (int32_t i = 0; i < n; ++i) {
         awl::Record r = rec[(size_t)i];
         const int32_t s = first_stream + i;
@@ -2063,7 +2151,7 @@ aw_status aw_spatializer_get_levels(aw_spatializer *sp, int32_t first_stream, in
         o.peak[0] = awl::bits_float(r.peak_bits[0]); o.peak[1] = awl::bits_float(r.peak_bits[1]);
         o.gain = 1.0f;
         if (sp->applied_mode == AW_GAIN_FIXED && (size_t)s < sp->applied_gains.size()) o.gain = sp->applied_gains[(size_t)s];
-        else if (sp->applied_mode == AW_GAIN_PEAK_CEILING)
+        else if (sp->applied_mode == AW_GAIN_PEAK_CEILING || sp->applied_mode == AW_GAIN_TRUE_PEAK_CEILING)
             o.gain = sp->applied_on_host ? sp->applied_host_gain : awl::auto_gain(awl::bits_float(peaks[(size_t)i]), sp->applied_ceiling);
         o.reserved = 0;
         o.energy[0] = r.energy[0]; o.energy[1] = r.energy[1];
@@ -2155,22 +2243,76 @@ aw_status aw_loudness_gain(double lufs, double target_lufs, float *gain) try {
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 
+// The one allocation is made here, never on the process path.  Off -> on: the history is zeroed, the peaks stay.
+aw_status aw_spatializer_set_true_peak(aw_spatializer *sp, int32_t on) try {
+    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    if (!on) { sp->true_peak = false; return AW_OK; }
+    if (sp->true_peak) return AW_OK;
+    if (!sp->ctx || sp->n_streams < 1) return fail(AW_ERR_INVALID_ARGUMENT, "the handle has no streams");
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    aw_status st = tp_buffers(sp);
+    if (st == AW_OK) st = tp_zero_history(sp);
+    if (st != AW_OK) return st;
+    sp->true_peak = true;
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_spatializer_get_true_peak(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_true_peak *out) try {
+    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    if (first_stream < 0 || n < 0 || (int64_t)first_stream + n > sp->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "streams out of range");
+    if (n == 0) return AW_OK;
+    if (!out) return fail(AW_ERR_INVALID_ARGUMENT, "out_host is NULL");
+    if (!sp->d_tp) return fail(AW_ERR_INVALID_ARGUMENT, "no true peak: neither aw_spatializer_set_true_peak nor AW_GAIN_TRUE_PEAK_CEILING has been used");
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
+    std::vector<unsigned long long> nf((size_t)n);
+    std::vector<uint32_t> pk(2 * (size_t)n), call((size_t)n);
+    AW_HIP_TRY(hipMemcpy(nf.data(), tp_nonfinite(sp) + first_stream, nf.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    AW_HIP_TRY(hipMemcpy(pk.data(), tp_peaks(sp) + 2 * (size_t)first_stream, pk.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    AW_HIP_TRY(hipMemcpy(call.data(), tp_call_peaks(sp) + first_stream, call.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int32_t i = 0; i < n; ++i) {
+        aw_stream_true_peak &o = out[i];
+        o.true_peak[0] = awtp::bits_float(pk[2 * (size_t)i]); o.true_peak[1] = awtp::bits_float(pk[2 * (size_t)i + 1]);
+        o.call_true_peak = awtp::bits_float(call[(size_t)i]);
+        o.reserved = 0;
+        o.frames = sp->tp_frames;
+        o.nonfinite = nf[(size_t)i];
+    }
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_true_peak_filter(float *out36) try {
+    if (!out36) return fail(AW_ERR_INVALID_ARGUMENT, "out36 is NULL");
+    float c[awtp::kCoefficients];
+    awtp::filter(c);
+    std::memcpy(out36, c, sizeof(c));
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
 // Checks first, then the allocation and the upload (here, never on the process path); the setting changes only when all of it worked.
 aw_status aw_spatializer_set_gain(aw_spatializer *sp, aw_gain_mode mode, const float *gains_host, int32_t n, float ceiling) try {
     if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
-    if (mode != AW_GAIN_NONE && mode != AW_GAIN_FIXED && mode != AW_GAIN_PEAK_CEILING) return fail(AW_ERR_INVALID_ARGUMENT, "unknown gain mode");
+    if (mode != AW_GAIN_NONE && mode != AW_GAIN_FIXED && mode != AW_GAIN_PEAK_CEILING && mode != AW_GAIN_TRUE_PEAK_CEILING)
+        return fail(AW_ERR_INVALID_ARGUMENT, "unknown gain mode");
     if (mode == AW_GAIN_FIXED) {
         if (!gains_host) return fail(AW_ERR_INVALID_ARGUMENT, "gains_host is NULL");
         if (n != 1 && n != sp->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "n must be 1 or the stream count");
         for (int32_t i = 0; i < n; ++i)
             if (!std::isfinite(gains_host[i])) return fail(AW_ERR_INVALID_ARGUMENT, "gains must be finite");
     }
-    if (mode == AW_GAIN_PEAK_CEILING && !(ceiling > 0.0f && ceiling <= 1.0f)) return fail(AW_ERR_INVALID_ARGUMENT, "ceiling must lie in (0, 1]");
+    if ((mode == AW_GAIN_PEAK_CEILING || mode == AW_GAIN_TRUE_PEAK_CEILING) && !(ceiling > 0.0f && ceiling <= 1.0f)) return fail(AW_ERR_INVALID_ARGUMENT, "ceiling must lie in (0, 1]");
     if (mode == AW_GAIN_NONE) { sp->gain_mode = AW_GAIN_NONE; return AW_OK; }
+    // the per-stream records below are sized by the stream count: a handle without streams or context has nothing to gain
+    if (!sp->ctx || sp->n_streams < 1) return fail(AW_ERR_INVALID_ARGUMENT, "the handle has no streams");
     AW_HIP_TRY(hipSetDevice(sp->ctx->device));
     std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
-    const aw_status st = lv_buffers(sp);
+    aw_status st = lv_buffers(sp);
     if (st != AW_OK) return st;
+    if (mode == AW_GAIN_TRUE_PEAK_CEILING && !tp_runs(sp)) {      // the true-peak kernel starts here, behind silence
+        if ((st = tp_buffers(sp)) != AW_OK || (st = tp_zero_history(sp)) != AW_OK) return st;
+    }
     if (mode == AW_GAIN_FIXED) {
         std::vector<float> g((size_t)sp->n_streams);
         for (int32_t s = 0; s < sp->n_streams; ++s) g[(size_t)s] = gains_host[n == 1 ? 0 : s];

@@ -146,6 +146,17 @@ struct aw_spatializer {
     int64_t loud_hop = 0, loud_cap = 0;           // frames per hop (rate / 10), hops recorded per stream
     uint64_t loud_frames = 0;                     // frames measured since the last reset (the same for every stream): fixes the hop index
     unsigned char *d_loud = nullptr;
+    // true peak of the four batch entries (aw_spatializer_set_true_peak, AW_GAIN_TRUE_PEAK_CEILING; rules: device/truepeak.hpp).  One
+    // device allocation, made by set_true_peak(1) or set_gain(AW_GAIN_TRUE_PEAK_CEILING): [n_streams] uint64 non-finite counts,
+    // [n_streams][2] uint32 peaks, [n_streams] uint32 call-local peaks (zeroed at the start of every call that runs the kernel), then two
+    // slots of [n_streams][11][2] float history: a call reads slot tp_cur and writes the other; batch_end flips after a call that ran.
+    bool true_peak = false;
+    int tp_cur = 0;
+    bool tp_ran = false;                          // this call queued the true-peak kernel: its history slot is the next call's
+    uint64_t tp_frames = 0;                       // frames measured since the last reset (the same for every stream)
+    float tp_filter[36] = {};                     // c[p][k], built once by the setter
+    uint32_t tp_pinned_call_bits = 0;             // the single-stream page-locked path under AW_GAIN_TRUE_PEAK_CEILING: the call's true peak, read back
+    unsigned char *d_tp = nullptr;
     int64_t host_chunk_streams = 0;               // streams per staged chunk of the last host call (0: the whole batch in one piece, serial)
     int64_t host_chunk_reserved = 0, host_reserved_frames = 0;   // aw_spatializer_reserve_host: the chunking its buffers were sized for, and up to which call length
     // what the last aw_spatializer_reserve spent where (microseconds): float64 table build on host threads, table upload (hipMalloc +

@@ -223,7 +223,8 @@ AW_API aw_status aw_spatializer_set_dither(aw_spatializer *sp, aw_dither mode, u
  *    streams (AW_HOST_CHUNK_MB), sharding it over handles, pinned or pageable, aligned or unaligned buffers change no output bit and
  *    no field but energy's summation order; splitting calls in time changes none either under AW_GAIN_NONE and AW_GAIN_FIXED.
  *  - peak and energy are raw material.  Integrated loudness in LUFS (K-weighting and gating, ITU-R BS.1770) is provided:
- *    aw_spatializer_set_loudness below.  True-peak oversampling, limiters and compressors are a host's business and are not provided. */
+ *    aw_spatializer_set_loudness below; so is the true peak (4x oversampling): aw_spatializer_set_true_peak, and the gain that holds a
+ *    true-peak ceiling, AW_GAIN_TRUE_PEAK_CEILING.  Limiters and compressors are a host's business and are not provided. */
 typedef struct aw_stream_levels {
     float    peak[2];      /* max |y| per ear (left, right) over finite samples, before gain */
     float    gain;         /* the gain the last call applied to this stream (1 if none) */
@@ -237,7 +238,8 @@ typedef int32_t aw_gain_mode;
 enum {
     AW_GAIN_NONE = 0,          /* no gain (the default) */
     AW_GAIN_FIXED = 1,         /* one gain per stream, given by the host */
-    AW_GAIN_PEAK_CEILING = 2   /* per stream and call: scale down to the ceiling where the call's peak exceeds it */
+    AW_GAIN_PEAK_CEILING = 2,  /* per stream and call: scale down to the ceiling where the call's peak exceeds it */
+    AW_GAIN_TRUE_PEAK_CEILING = 3   /* the same over the call's TRUE peak: g = tp > c ? c / tp : 1 (aw_stream_true_peak, below) */
 };
 /* on != 0: allocates the per-stream records at once (a later aw_spatializer_reserve / _reserve_pcm still means "no allocation on the
  * process path") and meters every later batch call; 0: stops metering, the records stay readable.  Do not call these four setters while
@@ -249,9 +251,9 @@ AW_API aw_status aw_spatializer_get_levels(aw_spatializer *sp, int32_t first_str
 /* Zeroes every record (asynchronous on the context's stream); the meter and gain settings stay. */
 AW_API aw_status aw_spatializer_reset_levels(aw_spatializer *sp);
 /* AW_GAIN_NONE: gains_host, n and ceiling are ignored.  AW_GAIN_FIXED: n finite gains, n == 1 (every stream) or n == the stream count,
- * uploaded by this call (never on the process path); ceiling is ignored.  AW_GAIN_PEAK_CEILING: 0 < ceiling <= 1; gains_host and n are
- * ignored.  A NULL handle, an unknown mode, a bad n, a NaN / inf gain or a bad ceiling returns AW_ERR_INVALID_ARGUMENT before any HIP
- * call, and the previous setting stays. */
+ * uploaded by this call (never on the process path); ceiling is ignored.  AW_GAIN_PEAK_CEILING and AW_GAIN_TRUE_PEAK_CEILING:
+ * 0 < ceiling <= 1; gains_host and n are ignored.  A NULL handle, an unknown mode, a bad n, a NaN / inf gain, a bad ceiling or (for a mode
+ * other than AW_GAIN_NONE) a handle without streams returns AW_ERR_INVALID_ARGUMENT before any HIP call, and the previous setting stays. */
 AW_API aw_status aw_spatializer_set_gain(aw_spatializer *sp, aw_gain_mode mode, const float *gains_host, int32_t n, float ceiling);
 /* Per-stream integrated loudness (ITU-R BS.1770-4) of the four batch entries, measured on the device from the float32 output y BEFORE
  * the gain — the level meter's tap — so that a host can bring every stream to a target such as -16 or -23 LUFS without moving float32
@@ -298,6 +300,46 @@ AW_API aw_status aw_spatializer_get_loudness_hops(aw_spatializer *sp, int32_t st
 /* *gain = 10^((target_lufs - lufs) / 20) as float32.  A NULL gain, a non-finite loudness (a silent stream measures -INFINITY) or target,
  * or a gain that is no finite float32 returns AW_ERR_INVALID_ARGUMENT and leaves *gain alone. */
 AW_API aw_status aw_loudness_gain(double lufs, double target_lufs, float *gain);
+/* Per-stream true peak (ITU-R BS.1770-4 Annex 2; dBTP = 20 log10 of it) of the four batch entries, measured on the device from the float32
+ * output y BEFORE the gain — the level meter's tap — the figure every loudness delivery specification sets beside its LUFS target
+ * (usually -1 dBTP).  The sample peak of aw_stream_levels under-reads it by up to 3 dB: a sine at a quarter of the sample rate, sampled at
+ * 45 degrees, reads -3.01 dB.  examples/offline_batch_true_peak.c brings every stream to -16 LUFS and -1 dBTP.  Off by default; while it is
+ * off and the gain is not AW_GAIN_TRUE_PEAK_CEILING every entry launches the kernels and writes the bytes it always has.  The planar
+ * entry and the engine / realtime adapters are not measured.
+ *  - the interpolator: 4x oversampling at every sample rate by a 49-tap Hann-windowed sinc,
+ *    h[j] = sinc((j - 24) / 4) * (0.5 - 0.5 cos(2 pi j / 48)), j = 0 .. 48, formed in double and rounded once to float32 (the libebur128
+ *    construction; BS.1770's own table is an example — EBU Tech 3341's +0.2 / -0.4 dB is the measure).  Phase 0 is the identity; the
+ *    phases p = 1, 2, 3 have twelve taps c[p][k] = h[p + 4k], which aw_true_peak_filter returns.
+ *  - per ear and frame n, with v[i] = y[i] where finite, else 0 (counted in nonfinite), and v[i] before the first measured frame 0:
+ *    t_p[n] = fmaf(c[p][11], v[n-11], .. fmaf(c[p][1], v[n-1], c[p][0] * v[n]) ..) in float32, and the true peak is the largest of
+ *    |v[n]|, |t_1[n]|, |t_2[n]|, |t_3[n]| over the frames: never below aw_stream_levels.peak.  The filter's six frames of lookahead are
+ *    not flushed: the last frames of a call contribute their windows when the next call brings later frames.
+ *  - every field is a pure function of the stream's samples since the last reset: chunking a batch by streams (AW_HOST_CHUNK_MB), sample
+ *    formats, pinned or pageable buffers, sharding over handles AND splitting calls in time change no bit.
+ *  - AW_GAIN_TRUE_PEAK_CEILING (aw_spatializer_set_gain, 0 < ceiling <= 1) gives every stream, in every call, g = tp > c ? c / tp : 1
+ *    with tp the stream's call_true_peak, and runs the measurement kernel in every call whether or not set_true_peak is on.  Like
+ *    AW_GAIN_PEAK_CEILING it is per call: a host that splits a file over calls in time should measure first (pass one), then set
+ *    AW_GAIN_FIXED gains of c / true_peak (pass two).  The first 11 windows of a call look back at the UNGAINED frames of the call
+ *    before.  Dither and the rounding of the integer encode come after the gain and can exceed the ceiling by the order of one LSB.
+ *  - aw_spatializer_reset and aw_spatializer_reset_levels zero the peaks, the counts and the carried frames. */
+typedef struct aw_stream_true_peak {
+    float    true_peak[2];   /* per ear, linear full scale, since the last reset; >= aw_stream_levels.peak */
+    float    call_true_peak; /* larger ear over the last measured call */
+    uint32_t reserved;       /* 0 */
+    uint64_t frames;         /* frames measured */
+    uint64_t nonfinite;      /* NaN / inf samples that entered as 0 */
+} aw_stream_true_peak;       /* 32 bytes */
+/* on != 0: allocates the per-stream records at once (never on the process path) and measures every later batch call; switching it on
+ * from off zeroes the carried frames — frames of unmeasured calls are not predecessors — while the peaks stay until a reset.  0: stops
+ * measuring, the records stay readable.  A NULL handle or a handle without streams returns AW_ERR_INVALID_ARGUMENT before any HIP call.  Do not call it while a
+ * process call on the same handle is running. */
+AW_API aw_status aw_spatializer_set_true_peak(aw_spatializer *sp, int32_t on);
+/* Synchronises the context's stream and copies the records of streams [first_stream, first_stream + n) to out_host.  A range outside the
+ * handle's streams returns AW_ERR_INVALID_ARGUMENT, as does a handle on which neither set_true_peak nor AW_GAIN_TRUE_PEAK_CEILING was
+ * ever used. */
+AW_API aw_status aw_spatializer_get_true_peak(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_true_peak *out_host);
+/* The coefficients the library uses: out36[(p - 1) * 12 + k] = c[p][k], p = 1 .. 3. */
+AW_API aw_status aw_true_peak_filter(float out36[36]);
 /* StereoAudioProcessing.process shape (AudioPipeline.swift:3-11) for a 1-stream, 2-channel
  * spatializer: planar HOST buffers, input_right may be NULL (mono duplication). Zero latency. */
 AW_API aw_status aw_spatializer_process_planar(aw_spatializer *sp, const float *input_left, const float *input_right,
@@ -322,7 +364,7 @@ AW_API int32_t aw_spatializer_channel_count(const aw_spatializer *sp);
  *   of the context's handles (a reserved process path makes neither), 15 streams per staged chunk of the last host-entry call,
  * 18 frames processed since create / the last aw_spatializer_reset (the dither's frame position, aw_spatializer_set_dither),
  * 19 the level meter is on (aw_spatializer_set_metering), 20 the aw_gain_mode of the batch entries (aw_spatializer_set_gain),
- * 21 the loudness measurement is on (aw_spatializer_set_loudness). */
+ * 21 the loudness measurement is on (aw_spatializer_set_loudness), 22 the true-peak measurement is on (aw_spatializer_set_true_peak). */
 AW_API int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what);
 /* Average device time of the dominant kernel over the launches since the last call (HIP events
  * on the context stream); used for bench.py's roofline object.  Returns launches counted. */

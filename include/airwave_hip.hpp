@@ -133,6 +133,14 @@ class Spatializer {
         return out;
     }
     static float loudnessGain(double lufs, double targetLufs) { float g = 1.0f; check(aw_loudness_gain(lufs, targetLufs, &g)); return g; }
+    // per-stream true peak of the batch entries (aw_stream_true_peak); the gain that holds a true-peak ceiling
+    void setTruePeak(bool on) { check(aw_spatializer_set_true_peak(h_, on ? 1 : 0)); }
+    std::vector<aw_stream_true_peak> truePeak() {
+        std::vector<aw_stream_true_peak> out((size_t)aw_spatializer_stream_count(h_));
+        check(aw_spatializer_get_true_peak(h_, 0, (int32_t)out.size(), out.data()));
+        return out;
+    }
+    void setGainTruePeakCeiling(float ceiling) { check(aw_spatializer_set_gain(h_, AW_GAIN_TRUE_PEAK_CEILING, nullptr, 0, ceiling)); }
     int64_t info(int32_t what) const { return aw_spatializer_info(h_, what); }
     void reset() { check(aw_spatializer_reset(h_)); }
     aw_spatializer *get() const { return h_; }
