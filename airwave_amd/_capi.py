@@ -66,6 +66,8 @@ SIGNATURES = {
     "aw_spatializer_set_true_peak": (_I32, [_V, _I32]),
     "aw_spatializer_get_true_peak": (_I32, [_V, _I32, _I32, _V]),
     "aw_true_peak_filter": (_I32, [c_float_p]),
+    "aw_spatializer_set_limiter": (_I32, [_V, _I32, ctypes.c_float, _I32, _I32]),
+    "aw_spatializer_get_limiter": (_I32, [_V, _I32, _I32, _V]),
     "aw_spatializer_reset": (_I32, [_V]),
     "aw_spatializer_stream_count": (_I32, [_V]),
     "aw_spatializer_channel_count": (_I32, [_V]),
@@ -163,6 +165,12 @@ class StreamTruePeak(ctypes.Structure):
     """aw_stream_true_peak (32 bytes)."""
     _fields_ = [("true_peak", ctypes.c_float * 2), ("call_true_peak", ctypes.c_float), ("reserved", ctypes.c_uint32),
                 ("frames", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64)]
+
+
+class StreamLimiter(ctypes.Structure):
+    """aw_stream_limiter (32 bytes)."""
+    _fields_ = [("min_gain", ctypes.c_float), ("reserved", ctypes.c_uint32), ("frames", ctypes.c_uint64),
+                ("limited_frames", ctypes.c_uint64), ("nonfinite", ctypes.c_uint64)]
 
 
 _lib = None

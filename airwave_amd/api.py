@@ -92,6 +92,10 @@ LOUDNESS_DTYPE = np.dtype([("integrated_lufs", np.float64), ("relative_threshold
 TRUE_PEAK_DTYPE = np.dtype([("true_peak", np.float32, (2,)), ("call_true_peak", np.float32), ("reserved", np.uint32), ("frames", np.uint64),
                             ("nonfinite", np.uint64)], align=False)
 
+# aw_stream_limiter, byte for byte (Spatializer.limiter)
+LIMITER_DTYPE = np.dtype([("min_gain", np.float32), ("reserved", np.uint32), ("frames", np.uint64), ("limited_frames", np.uint64),
+                          ("nonfinite", np.uint64)], align=False)
+
 
 def true_peak_filter() -> np.ndarray:
     """aw_true_peak_filter: the interpolator's float32 coefficients c[p][k], p = 1 .. 3, as a [3][12] array."""
@@ -462,7 +466,9 @@ class Spatializer:
                 "metering": g(19),              # the level meter is on (set_metering)
                 "gain_mode": g(20),             # aw_gain_mode of the batch entries (set_gain)
                 "loudness": g(21),              # the loudness measurement is on (set_loudness)
-                "true_peak": g(22)}             # the true-peak measurement is on (set_true_peak)
+                "true_peak": g(22),             # the true-peak measurement is on (set_true_peak)
+                "limiter": g(23),               # the limiter is on (set_limiter)
+                "limiter_latency": g(24)}       # its latency in frames (0 while it is off)
 
     def process_device(self, in_ptr: int, out_ptr: int, frames: int) -> None:
         _check(self._lib.aw_spatializer_process(self._h, ctypes.c_void_p(in_ptr), ctypes.c_void_p(out_ptr), frames))
@@ -628,6 +634,23 @@ class Spatializer:
             raise ValueError(f"streams [{first_stream}, {first_stream + n}) outside [0, {self.n_streams})")
         out = np.zeros(n, TRUE_PEAK_DTYPE)
         _check(self._lib.aw_spatializer_get_true_peak(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
+        return out
+
+    def set_limiter(self, on: bool = True, ceiling: float = 1.0, attack_frames: int = 64, hold_frames: int = 128) -> None:
+        """aw_spatializer_set_limiter: a look-ahead true-peak limiter on the output of every later batch call, behind the fixed gain;
+        0 < ceiling <= 1, 16 <= attack_frames <= 512, 0 <= hold_frames <= 1024.  The output is attack_frames + 11 frames late
+        (info()['limiter_latency']).  Switching it on allocates here, not on the process path."""
+        _check(self._lib.aw_spatializer_set_limiter(self._h, int(bool(on)), ctypes.c_float(ceiling), int(attack_frames), int(hold_frames)))
+
+    def limiter(self, first_stream: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """aw_spatializer_get_limiter: the records of n streams from first_stream on (default: all) as a structured array of
+        LIMITER_DTYPE.  Synchronises the context's stream."""
+        first_stream = int(first_stream)
+        n = self.n_streams - first_stream if n is None else int(n)
+        if first_stream < 0 or n < 0 or first_stream + n > self.n_streams:
+            raise ValueError(f"streams [{first_stream}, {first_stream + n}) outside [0, {self.n_streams})")
+        out = np.zeros(n, LIMITER_DTYPE)
+        _check(self._lib.aw_spatializer_get_limiter(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
         return out
 
     def reset(self) -> None:

@@ -40,6 +40,7 @@ SOURCES = [
     "device/pcm_kernels.hip",
     "device/loudness_kernels.hip",
     "device/truepeak_kernels.hip",
+    "device/limiter_kernels.hip",
     "runtime.cpp",
     "eq_runtime.cpp",
     "host/eq.cpp",

@@ -14,6 +14,7 @@
 #include <thread>
 
 #include "device/eq_kernels.hpp"
+#include "device/limiter_kernels.hpp"
 #include "device/loudness_kernels.hpp"
 #include "device/pcm.hpp"
 #include "device/pcm_kernels.hpp"
@@ -238,6 +239,7 @@ static aw_status context_create_impl(int32_t device, void *ext_stream, bool use_
     if (e == hipSuccess) e = awk::prepare_eq_kernels();
     if (e == hipSuccess) e = awk::prepare_loudness_kernels();
     if (e == hipSuccess) e = awk::prepare_truepeak_kernels();
+    if (e == hipSuccess) e = awk::prepare_limiter_kernels();
     if (e == hipSuccess) e = awk::prepare_prep_kernels();
     awh::Twiddles tw;
     awh::build_twiddles(tw);
@@ -741,6 +743,8 @@ void aw_spatializer_destroy(aw_spatializer *sp) {
     if (sp->d_levels) (void)hipFree(sp->d_levels);
     if (sp->d_loud) (void)hipFree(sp->d_loud);
     if (sp->d_tp) (void)hipFree(sp->d_tp);
+    if (sp->d_lim) (void)hipFree(sp->d_lim);
+    if (sp->d_lim_y) (void)hipFree(sp->d_lim_y);
     if (sp->k0) (void)hipEventDestroy(sp->k0);
     if (sp->k1) (void)hipEventDestroy(sp->k1);
     for (auto &pr : sp->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -763,7 +767,7 @@ int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what) {
         case 7: return sp->last_lw_R;         // long-window path: rows R of the last call's windows (N = R x 4096); 0 = the partitioned kernels ran
         case 8: return sp->last_lw_R2;        // rows of the last call's remainder window when it ran as two groups of windows (0: one group)
         case 9: return (int64_t)sp->lw_plans.size();   // long-window table sets built so far (one per window length; reserve builds those of its plan)
-        case 6: return (int64_t)(sp->ctx->pool_capacity * sizeof(awk::cf) + (sp->stage_in_cap + sp->stage_out_cap) * sizeof(float) + sp->pcm_in_cap + sp->pcm_out_cap);   // grow-only device buffers, bytes (the context's scratch pool + this handle's staging)
+        case 6: return (int64_t)(sp->ctx->pool_capacity * sizeof(awk::cf) + (sp->stage_in_cap + sp->stage_out_cap + sp->lim_y_cap) * sizeof(float) + sp->pcm_in_cap + sp->pcm_out_cap);   // grow-only device buffers, bytes (the context's scratch pool + this handle's staging)
         case 10: return sp->reserve_tables_us;    // last aw_spatializer_reserve: float64 table build on host threads, microseconds
         case 11: return sp->reserve_upload_us;    //   table upload (hipMalloc + hipMemcpy)
         case 12: return sp->reserve_scratch_us;   //   scratch pool growth (hipMalloc)
@@ -777,6 +781,8 @@ int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what) {
         case 20: return sp->gain_mode;            // aw_gain_mode of the batch entries (aw_spatializer_set_gain)
         case 21: return sp->loudness ? 1 : 0;     // the loudness measurement is on (aw_spatializer_set_loudness)
         case 22: return sp->true_peak ? 1 : 0;    // the true-peak measurement is on (aw_spatializer_set_true_peak)
+        case 23: return sp->limiter ? 1 : 0;      // the limiter is on (aw_spatializer_set_limiter)
+        case 24: return sp->limiter ? awlim::delay(sp->lim_attack) : 0;      // its latency in frames
         default: return -1;
     }
 }
@@ -1386,6 +1392,10 @@ aw_status aw_spatializer_reserve(aw_spatializer *sp, int64_t max_frames) try {
         if (st != AW_OK) return st;
     }
     sp->reserved_frames = std::max<int64_t>(sp->reserved_frames, max_frames);
+    if (sp->limiter) {              // the float32 staging in front of the limiter: every stream of the longest call
+        const aw_status st = sp_grow(sp, &sp->d_lim_y, &sp->lim_y_cap, (size_t)sp->n_streams * (size_t)max_frames * 2);
+        if (st != AW_OK) return st;
+    }
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 
@@ -1472,6 +1482,7 @@ static uint32_t *tp_call_peaks(const aw_spatializer *sp);
 // AW_GAIN_TRUE_PEAK_CEILING is the kernels' peak-ceiling gain over the call-local TRUE peaks
 static awk::PcmGain lv_gain_launch(const aw_spatializer *sp, int64_t s0) {
     awl::Record *rec = sp->metering ? lv_records(sp) + s0 : nullptr;
+    if (sp->limiter) return awk::PcmGain{awl::kGainNone, 0.0f, lv_gains(sp) + s0, lv_call_peaks(sp) + s0, rec};      // (the limiter has applied the fixed gain)
     if (sp->gain_mode == AW_GAIN_TRUE_PEAK_CEILING) return awk::PcmGain{awl::kGainPeakCeiling, sp->gain_ceiling, lv_gains(sp) + s0, tp_call_peaks(sp) + s0, rec};
     return awk::PcmGain{sp->gain_mode, sp->gain_ceiling, lv_gains(sp) + s0, lv_call_peaks(sp) + s0, rec};
 }
@@ -1610,6 +1621,85 @@ static aw_status tp_reset(aw_spatializer *sp) {
     sp->tp_frames = 0;
     sp->tp_pinned_call_bits = 0;
     if (sp->d_tp) AW_HIP_TRY(hipMemsetAsync(sp->d_tp, 0, tp_bytes(sp), sp->ctx->stream));
+    return AW_OK;
+}
+
+/* ---- look-ahead true-peak limiter of the batch entries (aw_spatializer_set_limiter; rules: device/limiter.hpp, kernel:
+ * device/limiter_tile.hpp) ---- */
+static_assert(sizeof(aw_stream_limiter) == 32, "aw_stream_limiter");
+static size_t lim_hist_floats(const aw_spatializer *sp) { return 2 * (size_t)awlim::halo(sp->lim_attack, sp->lim_hold); }
+static unsigned long long *lim_limited(const aw_spatializer *sp) { return reinterpret_cast<unsigned long long *>(sp->d_lim); }
+static unsigned long long *lim_nonfinite(const aw_spatializer *sp) { return lim_limited(sp) + sp->n_streams; }
+static uint32_t *lim_min_gain(const aw_spatializer *sp) { return reinterpret_cast<uint32_t *>(lim_nonfinite(sp) + sp->n_streams); }
+static float *lim_history(const aw_spatializer *sp, int slot) {
+    return reinterpret_cast<float *>(lim_min_gain(sp) + sp->n_streams) + (size_t)slot * (size_t)sp->n_streams * lim_hist_floats(sp);
+}
+static size_t lim_bytes_for(int n_streams, int attack, int hold) {
+    return (size_t)n_streams * (8 + 8 + 4 + 2 * 2 * (size_t)awlim::halo(attack, hold) * sizeof(float));
+}
+
+// the history starts over behind silence (off -> on; a reset), on the device and for the single-stream path
+static aw_status lim_zero_history(aw_spatializer *sp) {
+    AW_HIP_TRY(hipMemsetAsync(lim_history(sp, 0), 0, 2 * (size_t)sp->n_streams * lim_hist_floats(sp) * sizeof(float), sp->ctx->stream));
+    sp->h_lim_hist.assign(lim_hist_floats(sp), 0.0f);
+    sp->lim_hist_on_host = false;
+    return AW_OK;
+}
+
+// the records start over: no frame limited, a lowest gain of 1
+static aw_status lim_zero_records(aw_spatializer *sp) {
+    sp->lim_frames = 0;
+    sp->h_lim = awlim::Record{};
+    AW_HIP_TRY(hipMemsetAsync(sp->d_lim, 0, (size_t)sp->n_streams * 16, sp->ctx->stream));
+    AW_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lim_min_gain(sp)), (int)awlim::kOneBits, (size_t)sp->n_streams, sp->ctx->stream));
+    return AW_OK;
+}
+
+static aw_status lim_reset(aw_spatializer *sp) {
+    if (!sp->d_lim) return AW_OK;
+    const aw_status st = lim_zero_records(sp);
+    return st == AW_OK ? lim_zero_history(sp) : st;
+}
+
+// once per call that runs the kernel, before its first launch: where the single-stream path ran last, its history is the newer one
+static aw_status lim_begin_call(aw_spatializer *sp, int64_t frames) {
+    sp->lim_frames += (uint64_t)frames;
+    if (sp->lim_hist_on_host) {
+        AW_HIP_TRY(hipMemcpyAsync(lim_history(sp, sp->lim_cur), sp->h_lim_hist.data(), lim_hist_floats(sp) * sizeof(float), hipMemcpyHostToDevice, sp->ctx->stream));
+        AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
+        sp->lim_hist_on_host = false;
+    }
+    return AW_OK;
+}
+
+// y -> z for the streams [s0, s0 + ns) of a call (dense: `frames` apart; two buffers).  The AW_GAIN_FIXED gain is applied here, in
+// front of the detector.  A workgroup's tile lies in one stream and the history is per stream, so chunks of streams are independent.
+static aw_status lim_run(aw_spatializer *sp, const float *y, float *z, int64_t s0, int ns, int64_t frames) {
+    SpStageTimer tm(sp);
+    if (sp->profiling) tm.begin();
+    awk::LimiterParams p{};
+    p.in = y; p.out = z; p.frames = frames; p.n_streams = ns;
+    p.gain = sp->gain_mode == AW_GAIN_FIXED ? lv_gains(sp) + s0 : nullptr;
+    p.hist_in = lim_history(sp, sp->lim_cur) + (size_t)s0 * lim_hist_floats(sp);
+    p.hist_out = lim_history(sp, sp->lim_cur ^ 1) + (size_t)s0 * lim_hist_floats(sp);
+    p.min_gain = lim_min_gain(sp) + s0; p.limited = lim_limited(sp) + s0; p.nonfinite = lim_nonfinite(sp) + s0;
+    p.L = sp->lim_attack; p.H = sp->lim_hold; p.ceiling = sp->lim_ceiling;
+    std::memcpy(p.c, sp->tp_filter, sizeof(p.c));
+    AW_HIP_TRY(awk::launch_limiter(p, sp->ctx->stream));
+    sp->lim_ran = true;
+    if (sp->profiling) tm.end("aw_limiter_kernel");
+    return AW_OK;
+}
+
+// The single-stream page-locked path: the rule itself on the CPU, in place over the n = 2 * frames output samples y (the context's
+// stream is idle).  gain: what lv_host_call returned.
+static aw_status lim_host_call(aw_spatializer *sp, float *y, int64_t frames, float gain) {
+    if (!sp->lim_hist_on_host) {
+        AW_HIP_TRY(hipMemcpy(sp->h_lim_hist.data(), lim_history(sp, sp->lim_cur), lim_hist_floats(sp) * sizeof(float), hipMemcpyDeviceToHost));
+        sp->lim_hist_on_host = true;
+    }
+    sp->lim_frames += (uint64_t)frames;
+    awlim::sequential(sp->tp_filter, sp->lim_attack, sp->lim_hold, sp->lim_ceiling, gain, y, frames, sp->h_lim_hist.data(), y, sp->h_lim);
     return AW_OK;
 }
 
@@ -1798,6 +1888,7 @@ static aw_status batch_begin(aw_spatializer *sp, BatchCall *call, unsigned long 
         call->loud0 = sp->loud_frames;
         if (sp->loudness) sp->loud_frames += (uint64_t)call->frames;
         if (tp_runs(sp) && (st = tp_begin_call(sp, call->frames)) != AW_OK) return st;
+        if (sp->limiter && (st = lim_begin_call(sp, call->frames)) != AW_OK) return st;
     }
     if (zero_clip) AW_HIP_TRY(hipMemsetAsync(clip, 0, sizeof(unsigned long long), sp->ctx->stream));
     return AW_OK;
@@ -1807,20 +1898,27 @@ static aw_status batch_begin(aw_spatializer *sp, BatchCall *call, unsigned long 
 static void batch_end(aw_spatializer *sp) {
     sp->hist_cur ^= 1;
     if (sp->tp_ran) { sp->tp_cur ^= 1; sp->tp_ran = false; }
+    if (sp->lim_ran) { sp->lim_cur ^= 1; sp->lim_ran = false; }
 }
 
 // The streams [s0, s0 + ns) of a call, on the context's stream: pcm_src -> decode into f_in -> kernels -> meter / gain -> encode of f_out
 // into pcm_dst.  A float32 side has no conversion and no staging: the kernels read pcm_src / write pcm_dst, f_in / f_out is not looked at.
+// With the limiter on the kernels write y into the limiter's staging instead, the meters tap it there, and the limiter (which applies
+// the fixed gain) writes z where y would have gone.
 static aw_status batch_chunk(aw_spatializer *sp, const BatchCall &call, int64_t s0, int ns, const void *pcm_src, float *f_in, float *f_out, void *pcm_dst) {
     aw_status st = AW_OK;
     if (call.dec) st = pcm_decode(sp, call.in_fmt, pcm_src, f_in, (int64_t)ns * call.in_ps);
     const float *x = call.dec ? f_in : static_cast<const float *>(pcm_src);
-    float *y = call.enc ? f_out : static_cast<float *>(pcm_dst);
+    float *dst = call.enc ? f_out : static_cast<float *>(pcm_dst);
+    const bool lim = call.metered && sp->limiter;
+    if (st == AW_OK && lim) st = sp_grow(sp, &sp->d_lim_y, &sp->lim_y_cap, (size_t)ns * call.out_ps);      // (reserved for: nothing happens)
+    float *y = lim ? sp->d_lim_y : dst;
     if (st == AW_OK) st = sp_run_streams(sp, call.lw, (int)s0, ns, x, y, call.frames);
     if (st == AW_OK && call.metered && sp->loudness) st = ld_measure(sp, y, s0, ns, call.frames, call.loud0);      // (before the gain)
     if (st == AW_OK && call.metered && tp_runs(sp)) st = tp_measure(sp, y, s0, ns, call.frames);                   // (the gain may read its result)
-    if (st == AW_OK && call.metered) st = lv_after_run(sp, y, s0, ns, call.frames, !call.enc);
-    if (st == AW_OK && call.enc) st = pcm_encode(sp, call, y, pcm_dst, s0, ns);
+    if (st == AW_OK && call.metered) st = lv_after_run(sp, y, s0, ns, call.frames, !call.enc && !lim);
+    if (st == AW_OK && lim) st = lim_run(sp, y, dst, s0, ns, call.frames);
+    if (st == AW_OK && call.enc) st = pcm_encode(sp, call, dst, pcm_dst, s0, ns);
     return st;
 }
 
@@ -1872,7 +1970,12 @@ static aw_status host_process_pinned(aw_spatializer *sp, const BatchCall &call, 
     const aw_status st = batch_run_pinned(sp, call.frames, true, &pos0);
     if (st != AW_OK) return st;
     const bool lv = lv_active(sp);
-    const float gain = lv ? lv_host_call(sp, sp->h_pin_out, out_ps) : 1.0f;
+    float gain = lv ? lv_host_call(sp, sp->h_pin_out, out_ps) : 1.0f;
+    if (sp->limiter) {                   // z replaces y in the staging; the fixed gain went in with it
+        const aw_status sl = lim_host_call(sp, sp->h_pin_out, call.frames, gain);
+        if (sl != AW_OK) return sl;
+        gain = 1.0f;
+    }
     if (call.enc) {
         uint64_t n_clip = 0;
         const int mode = sp_dithers(sp, out_fmt) ? sp->dither : awp::kDitherNone;
@@ -2093,8 +2196,9 @@ static aw_status lv_reset(aw_spatializer *sp) {
     sp->metered_frames = 0;
     sp->applied_mode = AW_GAIN_NONE;
     if (sp->d_levels) AW_HIP_TRY(hipMemsetAsync(sp->d_levels, 0, (size_t)sp->n_streams * (sizeof(awl::Record) + sizeof(uint32_t)), sp->ctx->stream));
-    const aw_status st = ld_reset(sp);
-    return st == AW_OK ? tp_reset(sp) : st;
+    aw_status st = ld_reset(sp);
+    if (st == AW_OK) st = tp_reset(sp);
+    return st == AW_OK ? lim_reset(sp) : st;
 }
 
 aw_status aw_spatializer_reset(aw_spatializer *sp) try {
@@ -2291,6 +2395,74 @@ aw_status aw_true_peak_filter(float *out36) try {
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 
+// Checks first, then every allocation (here, never on the process path); the setting changes only when all of it worked.  Off -> on
+// and a change of attack or hold start from empty history; the records stay until a reset unless the allocation is made anew.
+aw_status aw_spatializer_set_limiter(aw_spatializer *sp, int32_t on, float ceiling, int32_t attack_frames, int32_t hold_frames) try {
+    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    if (!on) { sp->limiter = false; return AW_OK; }
+    if (!sp->ctx || sp->n_streams < 1) return fail(AW_ERR_INVALID_ARGUMENT, "the handle has no streams");
+    if (!(ceiling > 0.0f && ceiling <= 1.0f)) return fail(AW_ERR_INVALID_ARGUMENT, "ceiling must lie in (0, 1]");
+    if (attack_frames < awlim::kMinAttack || attack_frames > awlim::kMaxAttack) return fail(AW_ERR_INVALID_ARGUMENT, "attack_frames must lie in [16, 512]");
+    if (hold_frames < 0 || hold_frames > awlim::kMaxHold) return fail(AW_ERR_INVALID_ARGUMENT, "hold_frames must lie in [0, 1024]");
+    if (sp->gain_mode == AW_GAIN_PEAK_CEILING || sp->gain_mode == AW_GAIN_TRUE_PEAK_CEILING)
+        return fail(AW_ERR_INVALID_ARGUMENT, "a per-call ceiling gain cannot feed the limiter: set AW_GAIN_NONE or AW_GAIN_FIXED first");
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    const bool same_shape = sp->d_lim && sp->lim_attack == attack_frames && sp->lim_hold == hold_frames;
+    if (sp->limiter && same_shape) { sp->lim_ceiling = ceiling; return AW_OK; }
+    aw_status st = AW_OK;
+    const int64_t longest = std::max(sp->reserved_frames, sp->host_reserved_frames);
+    if (longest > 0 && (st = sp_grow(sp, &sp->d_lim_y, &sp->lim_y_cap, (size_t)sp->n_streams * (size_t)longest * 2)) != AW_OK) return st;
+    if (!same_shape) {
+        const size_t bytes = lim_bytes_for(sp->n_streams, attack_frames, hold_frames);
+        unsigned char *d = nullptr;
+        AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), bytes));
+        sp->ctx->device_allocs += 1;
+        if (sp->d_lim) {
+            AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
+            (void)hipFree(sp->d_lim);
+        }
+        sp->d_lim = d;
+        sp->lim_attack = attack_frames; sp->lim_hold = hold_frames;
+        sp->lim_cur = 0;
+        if ((st = lim_zero_records(sp)) != AW_OK) return st;
+    }
+    if ((st = lim_zero_history(sp)) != AW_OK) return st;
+    awtp::filter(sp->tp_filter);
+    sp->lim_ceiling = ceiling;
+    sp->limiter = true;
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_spatializer_get_limiter(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_limiter *out) try {
+    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    if (first_stream < 0 || n < 0 || (int64_t)first_stream + n > sp->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "streams out of range");
+    if (n == 0) return AW_OK;
+    if (!out) return fail(AW_ERR_INVALID_ARGUMENT, "out_host is NULL");
+    if (!sp->d_lim) return fail(AW_ERR_INVALID_ARGUMENT, "no limiter: aw_spatializer_set_limiter has not been called");
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
+    std::vector<unsigned long long> lim((size_t)n), nf((size_t)n);
+    std::vector<uint32_t> mg((size_t)n);
+    AW_HIP_TRY(hipMemcpy(lim.data(), lim_limited(sp) + first_stream, lim.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    AW_HIP_TRY(hipMemcpy(nf.data(), lim_nonfinite(sp) + first_stream, nf.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    AW_HIP_TRY(hipMemcpy(mg.data(), lim_min_gain(sp) + first_stream, mg.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int32_t i = 0; i < n; ++i) {
+        if (first_stream + i == 0) {     // the single-stream path's share (a handle of one stream)
+            mg[(size_t)i] = std::min(mg[(size_t)i], sp->h_lim.min_gain_bits);
+            lim[(size_t)i] += sp->h_lim.limited_frames; nf[(size_t)i] += sp->h_lim.nonfinite;
+        }
+        aw_stream_limiter &o = out[i];
+        o.min_gain = awl::bits_float(mg[(size_t)i]);
+        o.reserved = 0;
+        o.frames = sp->lim_frames;
+        o.limited_frames = lim[(size_t)i];
+        o.nonfinite = nf[(size_t)i];
+    }
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
 // Checks first, then the allocation and the upload (here, never on the process path); the setting changes only when all of it worked.
 aw_status aw_spatializer_set_gain(aw_spatializer *sp, aw_gain_mode mode, const float *gains_host, int32_t n, float ceiling) try {
     if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
@@ -2303,6 +2475,8 @@ aw_status aw_spatializer_set_gain(aw_spatializer *sp, aw_gain_mode mode, const f
             if (!std::isfinite(gains_host[i])) return fail(AW_ERR_INVALID_ARGUMENT, "gains must be finite");
     }
     if ((mode == AW_GAIN_PEAK_CEILING || mode == AW_GAIN_TRUE_PEAK_CEILING) && !(ceiling > 0.0f && ceiling <= 1.0f)) return fail(AW_ERR_INVALID_ARGUMENT, "ceiling must lie in (0, 1]");
+    if ((mode == AW_GAIN_PEAK_CEILING || mode == AW_GAIN_TRUE_PEAK_CEILING) && sp->limiter)
+        return fail(AW_ERR_INVALID_ARGUMENT, "a per-call ceiling gain cannot feed the limiter: switch the limiter off first");
     if (mode == AW_GAIN_NONE) { sp->gain_mode = AW_GAIN_NONE; return AW_OK; }
     // the per-stream records below are sized by the stream count: a handle without streams or context has nothing to gain
     if (!sp->ctx || sp->n_streams < 1) return fail(AW_ERR_INVALID_ARGUMENT, "the handle has no streams");

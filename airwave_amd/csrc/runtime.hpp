@@ -12,6 +12,7 @@
 #include "../../include/airwave_hip.h"
 #include "device/kernels.hpp"
 #include "device/levels.hpp"
+#include "device/limiter.hpp"
 
 namespace awr {
 
@@ -157,6 +158,24 @@ struct aw_spatializer {
     float tp_filter[36] = {};                     // c[p][k], built once by the setter
     uint32_t tp_pinned_call_bits = 0;             // the single-stream page-locked path under AW_GAIN_TRUE_PEAK_CEILING: the call's true peak, read back
     unsigned char *d_tp = nullptr;
+    // look-ahead true-peak limiter of the four batch entries (aw_spatializer_set_limiter; rules: device/limiter.hpp).  One device
+    // allocation, made by set_limiter(on): [n_streams] uint64 limited frames, [n_streams] uint64 non-finite counts, [n_streams] uint32
+    // bits of the lowest gain, then two slots of [n_streams][halo][2] float history (raw u): a call reads slot lim_cur and writes the
+    // other; batch_end flips after a call that ran.  d_lim_y is the float32 staging the convolution kernels write y into while the
+    // limiter is on (the kernel is out of place): one chunk of streams, grow-only like the other staging.
+    bool limiter = false;
+    int lim_attack = 0, lim_hold = 0;
+    float lim_ceiling = 0.0f;
+    int lim_cur = 0;
+    bool lim_ran = false;                         // this call queued the limiter kernel: its history slot is the next call's
+    uint64_t lim_frames = 0;                      // frames limited since the last reset (the same for every stream)
+    unsigned char *d_lim = nullptr;               // (made anew when attack or hold change the halo)
+    float *d_lim_y = nullptr;
+    size_t lim_y_cap = 0;
+    // the single-stream page-locked path limits on the CPU: its share of stream 0's record, and the history while it is the newer one
+    awlim::Record h_lim;
+    std::vector<float> h_lim_hist;
+    bool lim_hist_on_host = false;
     int64_t host_chunk_streams = 0;               // streams per staged chunk of the last host call (0: the whole batch in one piece, serial)
     int64_t host_chunk_reserved = 0, host_reserved_frames = 0;   // aw_spatializer_reserve_host: the chunking its buffers were sized for, and up to which call length
     // what the last aw_spatializer_reserve spent where (microseconds): float64 table build on host threads, table upload (hipMalloc +

@@ -224,7 +224,8 @@ AW_API aw_status aw_spatializer_set_dither(aw_spatializer *sp, aw_dither mode, u
  *    no field but energy's summation order; splitting calls in time changes none either under AW_GAIN_NONE and AW_GAIN_FIXED.
  *  - peak and energy are raw material.  Integrated loudness in LUFS (K-weighting and gating, ITU-R BS.1770) is provided:
  *    aw_spatializer_set_loudness below; so is the true peak (4x oversampling): aw_spatializer_set_true_peak, and the gain that holds a
- *    true-peak ceiling, AW_GAIN_TRUE_PEAK_CEILING.  Limiters and compressors are a host's business and are not provided. */
+ *    true-peak ceiling, AW_GAIN_TRUE_PEAK_CEILING.  A look-ahead true-peak limiter is provided too: aw_spatializer_set_limiter
+ *    below; compressors and multiband dynamics are a host's business and are not provided. */
 typedef struct aw_stream_levels {
     float    peak[2];      /* max |y| per ear (left, right) over finite samples, before gain */
     float    gain;         /* the gain the last call applied to this stream (1 if none) */
@@ -340,6 +341,49 @@ AW_API aw_status aw_spatializer_set_true_peak(aw_spatializer *sp, int32_t on);
 AW_API aw_status aw_spatializer_get_true_peak(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_true_peak *out_host);
 /* The coefficients the library uses: out36[(p - 1) * 12 + k] = c[p][k], p = 1 .. 3. */
 AW_API aw_status aw_true_peak_filter(float out36[36]);
+/* Look-ahead true-peak limiter on the output of the four batch entries, on the device: a stream can be brought to its loudness target
+ * (AW_GAIN_FIXED) AND held under a true-peak ceiling without moving float32 output over PCIe (examples/offline_batch_limiter.c).  Off by
+ * default; while it is off every entry launches the kernels and writes the bytes it always has.  The planar entry and the engine /
+ * realtime adapters are not limited.  Per stream, stereo-linked, with n the frame index since the last reset, c the ceiling,
+ * L = attack_frames (attack = release), H = hold_frames, g_s the stream's AW_GAIN_FIXED gain (1 under AW_GAIN_NONE), W = L + 12 + H and
+ * D = L + 11:
+ *  - u[n][e] = (float)(y[n][e] * g_s) — the gain's one float32 product, made inside the limiter: the scale / encode kernels then run
+ *    without gain, and aw_stream_levels.gain stays the fixed gain.  The meter, the loudness and the true peak keep tapping y.
+ *  - p[n]: the larger ear of the true-peak detector above over v = u where finite, else 0 (counted in nonfinite); the same
+ *    coefficients and fmaf order as aw_stream_true_peak.
+ *  - r[n] = p[n] > c ? c / p[n] correctly rounded : 1 (1 before the first frame); q[n] = floor(r[n] * 2^30) as uint32.
+ *  - m[n] = min(q[n] .. q[n - (W - 1)]); S[n] = m[n] + .. + m[n - (L - 1)] in uint64 (exact in any order);
+ *    g[n] = (float)((double)S[n] / ((double)L * 2^30)).
+ *  - z[n][e] = (float)(u[n - D][e] * g[n]), u = 0 before the stream's first frame.  z goes where y went: float32 output, or the
+ *    integer encode with its dither; clipped counts what the encode of z clipped.  A non-finite y comes out non-finite, D frames later.
+ *  - g[n] <= r[k] for every detector frame k in [n - D - H, n - D + 11]: no sample of z exceeds c by more than the rounding of c / p
+ *    and of the product, and the gain is flat across the twelve frames of an isolated peak's window, whose true peak lands at c up to
+ *    float32 rounding.  Dense material can overshoot c slightly between such windows while the gain moves: measured on noise at 2.5
+ *    times full scale, 1.4e-3 of c at attack 16 / hold 0, 4e-5 at 64 / 128, 7e-6 and less from 256 / 256 on (DESIGN.md has the table).
+ *  - latency: D frames (aw_spatializer_info 24).  The last D frames of a file come out when the host feeds D more frames of zeros.
+ *  - every bit of z and every field is a pure function of the stream's samples since the last reset: chunking a batch by streams
+ *    (AW_HOST_CHUNK_MB), sample formats, pinned or pageable buffers, sharding over handles AND splitting calls in time change none.
+ *    This is why the per-call gains AW_GAIN_PEAK_CEILING and AW_GAIN_TRUE_PEAK_CEILING cannot be combined with it.
+ *  - aw_spatializer_reset and aw_spatializer_reset_levels zero the records and the carried frames. */
+typedef struct aw_stream_limiter {
+    float    min_gain;        /* lowest g applied since the last reset (1 if never limited) */
+    uint32_t reserved;        /* 0 */
+    uint64_t frames;          /* frames that went through the limiter */
+    uint64_t limited_frames;  /* of those, output frames with g < 1 */
+    uint64_t nonfinite;       /* NaN / inf samples that entered the detector as 0 */
+} aw_stream_limiter;          /* 32 bytes */
+/* on != 0: 0 < ceiling <= 1, 16 <= attack_frames <= 512, 0 <= hold_frames <= 1024.  Allocates the records, the carried frames (the last
+ * W + L + 9 frames of u per stream, in two slots) and the float32 staging the convolution kernels write into while the limiter is on
+ * (sized for what aw_spatializer_reserve / _reserve_pcm / _reserve_host have reserved so far; a reserve made afterwards sizes it too), so
+ * that a reserved process path still does not allocate.  Switching it on from off, or changing attack or hold, starts from empty
+ * history.  0: switches it off; the other arguments are ignored and the records stay readable.  A NULL handle, a handle without streams,
+ * a ceiling outside (0, 1] or not finite, attack_frames or hold_frames out of range, or a gain mode of AW_GAIN_PEAK_CEILING /
+ * AW_GAIN_TRUE_PEAK_CEILING returns AW_ERR_INVALID_ARGUMENT before any HIP call and leaves the previous setting; while the limiter is
+ * on, aw_spatializer_set_gain refuses those two modes likewise.  Do not call it while a process call on the same handle is running. */
+AW_API aw_status aw_spatializer_set_limiter(aw_spatializer *sp, int32_t on, float ceiling, int32_t attack_frames, int32_t hold_frames);
+/* Synchronises the context's stream and copies the records of streams [first_stream, first_stream + n) to out_host.  A range outside the
+ * handle's streams returns AW_ERR_INVALID_ARGUMENT, as does a handle on which set_limiter was never switched on. */
+AW_API aw_status aw_spatializer_get_limiter(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_limiter *out_host);
 /* StereoAudioProcessing.process shape (AudioPipeline.swift:3-11) for a 1-stream, 2-channel
  * spatializer: planar HOST buffers, input_right may be NULL (mono duplication). Zero latency. */
 AW_API aw_status aw_spatializer_process_planar(aw_spatializer *sp, const float *input_left, const float *input_right,
@@ -364,7 +408,8 @@ AW_API int32_t aw_spatializer_channel_count(const aw_spatializer *sp);
  *   of the context's handles (a reserved process path makes neither), 15 streams per staged chunk of the last host-entry call,
  * 18 frames processed since create / the last aw_spatializer_reset (the dither's frame position, aw_spatializer_set_dither),
  * 19 the level meter is on (aw_spatializer_set_metering), 20 the aw_gain_mode of the batch entries (aw_spatializer_set_gain),
- * 21 the loudness measurement is on (aw_spatializer_set_loudness), 22 the true-peak measurement is on (aw_spatializer_set_true_peak). */
+ * 21 the loudness measurement is on (aw_spatializer_set_loudness), 22 the true-peak measurement is on (aw_spatializer_set_true_peak),
+ * 23 the limiter is on (aw_spatializer_set_limiter), 24 its latency D in frames (0 while it is off). */
 AW_API int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what);
 /* Average device time of the dominant kernel over the launches since the last call (HIP events
  * on the context stream); used for bench.py's roofline object.  Returns launches counted. */

@@ -141,6 +141,15 @@ class Spatializer {
         return out;
     }
     void setGainTruePeakCeiling(float ceiling) { check(aw_spatializer_set_gain(h_, AW_GAIN_TRUE_PEAK_CEILING, nullptr, 0, ceiling)); }
+    // look-ahead true-peak limiter of the batch entries (aw_stream_limiter); latency: info(24) frames
+    void setLimiter(bool on, float ceiling = 1.0f, int32_t attackFrames = 64, int32_t holdFrames = 128) {
+        check(aw_spatializer_set_limiter(h_, on ? 1 : 0, ceiling, attackFrames, holdFrames));
+    }
+    std::vector<aw_stream_limiter> limiter() {
+        std::vector<aw_stream_limiter> out((size_t)aw_spatializer_stream_count(h_));
+        check(aw_spatializer_get_limiter(h_, 0, (int32_t)out.size(), out.data()));
+        return out;
+    }
     int64_t info(int32_t what) const { return aw_spatializer_info(h_, what); }
     void reset() { check(aw_spatializer_reset(h_)); }
     aw_spatializer *get() const { return h_; }

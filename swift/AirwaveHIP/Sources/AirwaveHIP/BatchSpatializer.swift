@@ -154,6 +154,27 @@ public final class BatchSpatializer {
         return aw_loudness_gain(lufs, target, &g) == AW_OK ? g : nil
     }
 
+    /// Look-ahead true-peak limiter on the output of every later batch call (`aw_spatializer_set_limiter`), behind the `AW_GAIN_FIXED`
+    /// gain: 0 < ceiling <= 1, 16 <= attackFrames <= 512, 0 <= holdFrames <= 1024.  The output is `limiterLatency` frames late; feed that
+    /// many frames of zeros to flush a file.  Switching it on allocates here, not on the process path.
+    public func setLimiter(_ on: Bool, ceiling: Float = 1, attackFrames: Int32 = 64, holdFrames: Int32 = 128) throws {
+        let st = aw_spatializer_set_limiter(handle, on ? 1 : 0, ceiling, attackFrames, holdFrames)
+        guard st == AW_OK else { throw BatchSpatializer.error(st) }
+    }
+
+    /// The limiter's latency in frames (`aw_spatializer_info` 24); 0 while it is off.
+    public var limiterLatency: Int64 { aw_spatializer_info(handle, 24) }
+
+    /// The limiter's records of every stream (`aw_spatializer_get_limiter`): the lowest gain applied, frames, limited frames and
+    /// non-finite samples.  Synchronises the context's stream.
+    public func limiter() throws -> [aw_stream_limiter] {
+        let n = aw_spatializer_stream_count(handle)
+        var out = [aw_stream_limiter](repeating: aw_stream_limiter(), count: Int(n))
+        let st = out.withUnsafeMutableBufferPointer { aw_spatializer_get_limiter(handle, 0, n, $0.baseAddress) }
+        guard st == AW_OK else { throw BatchSpatializer.error(st) }
+        return out
+    }
+
     /// `reserve` plus the host entry's device-side staging: `process(hostInput:…)` never allocates afterwards either.
     public func reserveHost(maxFrames: Int64) throws {
         let st = aw_spatializer_reserve_host(handle, maxFrames)
