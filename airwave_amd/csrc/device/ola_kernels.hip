@@ -6,13 +6,7 @@
 
 namespace awk {
 
-// rows H of the block a layout's HRIR length maps to (0: no kernel): the largest H <= 8 whose window still holds the tail
-int fused_ola_rows(int n_channels, int taps) {
-    if (taps < 2) return 0;
-    int H = (kN - (taps - 1)) / 512;
-    if (H > 8) H = 8;
-    return ola_has_kernel(n_channels, H) ? H : 0;
-}
+int fused_ola_rows(int n_channels, int taps) { return ola_rows_carried(n_channels, taps); }
 
 const char *fused_ola_kernel_name(int C, int H) {
     static thread_local char name[64];

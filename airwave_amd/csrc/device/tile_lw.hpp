@@ -1,5 +1,5 @@
 // tile_lw.hpp — the LONG-WINDOW path for long calls (cfg 3's 32 768-tap HRIRs; past a measured HRIR length every layout,
-// runtime.cpp lw_choose): single-partition overlap-save on windows of N = R x 4096 frames (R = 32, 64, 128: N = 131 072 ...
+// host/path_policy.hpp lw_choose): single-partition overlap-save on windows of N = R x 4096 frames (R = 32, 64, 128: N = 131 072 ...
 // 524 288), the transform run as a four-step FFT through HBM scratch.
 //
 // Replaces, for a whole window of one stream at once, what ConvolutionEngine.process does per 512-frame block with a

@@ -20,14 +20,10 @@
 #include "device/pcm_kernels.hpp"
 #include "device/truepeak_kernels.hpp"
 #include "host/eq.hpp"
+#include "host/path_policy.hpp"
 #include "host/tables.hpp"
 
-// Default fused window: 8192 frames; 16384 (tile_ols2.hpp) where measurements favour it.
-#ifndef AW_DEFAULT_WINDOW
-#define AW_DEFAULT_WINDOW 8192
-#endif
-
-// table sets a spatializer can hold: one per long-window length (kLwRowChoices below); lw_plans reserves this many at create
+// table sets a spatializer can hold: one per long-window length (awp::kLwRowChoices); lw_plans reserves this many at create
 static constexpr size_t kLwPlanSlots = 16;
 
 // Host threads that copy slices of ONE buffer at a time: the multi-stream host entry bounces pageable caller memory through page-locked
@@ -479,62 +475,19 @@ static aw_status sp_alloc_hist(aw_spatializer *sp) {
     return AW_OK;
 }
 
-// Tiles start on 64-frame boundaries of the timeline: a shorter hop costs < 2 % more tiles and makes every tile's
-// loads and stores start line-aligned (measured cfg 2: 1.555 -> 1.530 ms per call).  AW_HOP_ALIGN (read at aw_context_create) overrides (1 = off).
-// Overlap-add tile or overlap-save tile for a path-0 spatializer?  Returns the block rows H (0: overlap-save).  `hist_len` = rows of the
-// history buffer the spatializer will keep (N - the aligned overlap-save hop >= taps - 1): the block's tail must fit behind its hop.
-// The overlap-add block is cheaper per transform (whole frames in registers, every input line read once, no boundary launch) but
-// shorter than the overlap-save hop (512 H against 8193 - taps rounded down to 64), so it wins from a layout-specific ratio of the two
-// on — measured, profiles/round6_v1/ola_sweep.txt (128 streams x 10 s, G frames/s overlap-save / overlap-add / long-window):
-//   4 ch   3585 taps 92.2 / 87.3, 3969: 86.3 / 86.6, 4320: 79.5 / 79.5, 4609: 74.6 / 79.2            -> from hop_ola >= 0.94 hop_ols
-//   6 ch   3585: 64.7 / 64.4, 3969: 60.9 / 65.2, 4098: 58.4 / 58.0, 4320: 56.5 / 57.8                 -> 0.90
-//   7 ch   3000: 58.7 / 54.5, 3585: 53.3 / 54.2, 4320: 46.0 / 48.8, 4609: 42.9 (16384-frame tile) / 48.7   -> 0.875
-//   8 ch   3585: 53.5 / 53.4, 3969: 49.4 / 53.3, 4320: 46.7 / 47.7, 5121: 34.6 / 41.7 / 39.0          -> 0.89
-//   10 ch  2048: 45.6 / 42.7, 3000: 40.7 / 42.7, 4320: 32.4 / 38.7 / 30.0                             -> 0.74
-//   12 ch  3000: 36.7 / 36.4, 3585: 34.1 / 36.2, 4320: 29.8 / 32.9 / 25.7                             -> 0.80
-//   14 ch  3000: 29.7 / 27.5, 3585: 27.5 / 27.6, 4320: 23.5 / 27.7 / 23.8, 5121: 20.1 / 25.4 / 23.7   -> 0.89
-//   16 ch  2048: 24.1 / 24.5, 4320: 17.6 / 22.7 / 20.6, 5121: 14.9 / 21.3 / 20.4                      -> 0.66
-// odd wide layouts (profiles/round6_v5/ola_sweep_odd.txt): 9 ch 3000: 42.5 / 43.1, 4320: 33.9 / 38.8 / 31.6; 11 ch 4320: 29.3 / 33.4 / 28.1;
-//   13 ch 4320: 24.1 / 28.6 / 24.9 -> 0.78 each; 15 ch 2048: 24.6 / 26.7, 4320: 17.7 / 24.2 / 21.7 -> 0.62; 5 channels: the 16384-frame
-//   tile stays faster at every length (64.5 against 57.4 at 4320 taps): no kernel
-// (tools/ola_sweep.py regenerates the table).  AW_OLA=0 never, AW_OLA=1 wherever a kernel exists.
-static int ola_policy(int n_channels, int taps, int hist_len) {
-    int mode = -1;
-    if (const char *e = getenv("AW_OLA")) mode = atoi(e);
-    if (mode == 0) return 0;
-    int H = awk::fused_ola_rows(n_channels, taps);
-    while (H >= 6 && hist_len > awk::kN - 512 * H) --H;          // (the aligned history may be a few rows longer than taps - 1)
-    if (H < 6) return 0;
-    if (mode > 0) return H;
-    const int hop_ols = awk::kN - hist_len;
-    double need;
-    switch (n_channels) {
-        case 4: need = 0.94; break;
-        case 6: need = 0.90; break;
-        case 7: need = 0.875; break;
-        case 8: need = 0.89; break;
-        case 9: need = 0.78; break;
-        case 10: need = 0.74; break;
-        case 11: need = 0.78; break;
-        case 12: need = 0.80; break;
-        case 13: need = 0.78; break;
-        case 14: need = 0.89; break;
-        case 15: need = 0.62; break;
-        default: need = 0.66; break;      // 16 channels
-    }
-    return 512.0 * H >= need * hop_ols ? H : 0;
+// The kernel-path decisions of a spatializer are pure functions of its layout and knobs (host/path_policy.hpp); this file reads the knobs,
+// calls them and keeps the side effects.
+static awp::Layout sp_layout(const aw_spatializer *sp) { return awp::Layout{sp->n_channels, sp->taps, sp->n_streams}; }
+static awp::CreatePlan sp_plan(const aw_spatializer *sp) {          // what plan_create() decided, as aw_spatializer_create copied it into sp
+    awp::CreatePlan p;
+    p.path = sp->path; p.fused2 = sp->fused2; p.hop = sp->hop; p.hist_len = sp->hist_len; p.partitions = sp->partitions; p.n_pairs = sp->n_pairs;
+    p.ola_h = sp->ola_h; p.cmac_group = sp->cmac_group; p.fwd_one_pair = sp->fwd_one_pair; p.herm_ok = sp->herm_ok; p.lw_mode = sp->lw_mode;
+    return p;
 }
-// Blocks per persistent workgroup from which a call runs the overlap-add tile: every run pays ceil(hist / hop) <= 2 warm-up blocks, which
-// must stay below what the tile gains over the overlap-save tile — 2 - 10 % for layouts of up to eight channels, 10 - 40 % for wider ones.
-static int ola_min_blocks(const aw_spatializer *sp) {
-    const int forced = sp->ctx->cfg.ola_min_blocks_per_wg;       // AW_OLA_MIN_BLOCKS (read at context creation); < 0: per layout
-    if (forced >= 0) return forced;
-    return sp->n_channels <= 8 ? 48 : 16;
-}
-
-static int align_hop(const aw_context *ctx, int hop) {
-    const int al = ctx->cfg.hop_align;          // read once at aw_context_create (LaunchCfg), like every other knob
-    return (al > 1 && hop > 16 * al) ? hop - hop % al : hop;
+static awp::Knob env_knob(const char *name) {
+    awp::Knob k;
+    if (const char *e = getenv(name)) { k.set = true; k.value = atoi(e); }
+    return k;
 }
 
 aw_status aw_spatializer_create(aw_context *ctx, const aw_hrir *hrir, int32_t n_in, const int32_t *left_track,
@@ -565,95 +518,26 @@ aw_status aw_spatializer_create(aw_context *ctx, const aw_hrir *hrir, int32_t n_
     sp->ctx = ctx; sp->n_channels = n_in; sp->n_pairs = (n_in + 1) / 2; sp->n_streams = n_streams;
     sp->taps = hrir->taps;
     sp->sample_rate = hrir->sample_rate;
-    const int N = awk::kN;
-    // Path choice.  AW_WINDOW=8192|16384 forces the fused window, 4096 the partitioned path (tuning / A-B); default: see below.
-    int window = 0;
-    if (const char *e = getenv("AW_WINDOW")) window = atoi(e);
-    const int hist2 = awh::poly_history_frames(hrir->taps);          // 16384-frame windows (tile_ols2.hpp)
-    const bool fits1 = hrir->taps - 1 <= N - 2048, fits2 = hist2 <= awk::kN2 - 4096;
-    // Path / window policy.  Every threshold below is a measured crossover (G stereo frames/s, 128 streams x 4 s unless stated) and
-    // is regenerated in one command: `bash tools/regen_policy.sh` (round 2, after the marched partitioned path, the two-pass
-    // wide kernels and the per-layout SLP choice moved most of them).
-    // (1) Long end of the 16384-frame windows against the partitioned path (the hop shrinks to 4096 frames at 12 289 taps):
-    //     1, 3 and 5 channels stay fused to the window's limit (mono 12 289 taps: 79 / 49), stereo too (12 289: 53 / 51);
-    //     7 channels up to ~11 800 (11 000: 19.7 / 18.8; 12 289: 16.7 / 18.3); the even layouts leave early, their 16384-frame
-    //     kernels carry ~100 spilled VGPRs: 4 channels up to ~7000 (6146: 36.8 / 35.1; 8000: 30.7 / 35.4), 6 up to ~8500
-    //     (8000: 23.5 / 21.8; 9000: 20.2 / 21.1), 8 up to ~7800 (6146: 20.6 / 17.6; 8000: 18.2 / 18.2).  9+ channels have no
-    //     16384-frame vector kernels: partitioned as soon as one 8192-frame window cannot hold the HRIR.
-    //     Round 4, the 16384-frame kernels on the half-wave row transform (no spills, 4 / 6 / 8 channels +12 / +27 / +11 %), re-measured
-    //     (profiles/round4_v2/policy_sweeps_final.txt, 16384 / partitioned): 4 channels up to ~10 500 (10 000: 36.7 / 33.2; 11 000: 32.7 / 35.8),
-    //     6 to the window's limit (12 289: 21.0 / 20.7), 7 up to ~11 500 (11 000: 21.1 / 19.1; 11 800: 18.2 / 19.0), 8 up to ~11 200
-    //     (11 000: 17.4 / 17.2; 11 800: 15.5 / 17.3).
-    const int upto = (n_in <= 3 || n_in == 5 || n_in == 6) ? 12289 : n_in == 4 ? 10500 : n_in == 8 ? 11200 : n_in == 7 ? 11500 : 0;
-    const bool fused2_ok = fits2 && hrir->taps <= upto;
-    // (0) Round 6: the overlap-add form of the 8192-frame tile (device/tile_ola.hpp) where the library carries a kernel for the layout and
-    //     the HRIR length (blocks of 512 H frames, H = 5 .. 8: 3585 .. 5633 taps and shorter ones on H = 8).  It reads every input line
-    //     once and holds whole frames of every layout, so it is measured against BOTH overlap-save windows (ola_policy()); the choice is
-    //     per call: calls with too few blocks per workgroup to amortise a run's warm-up blocks stay on the overlap-save tile.
-    //     AW_OLA=0 never, AW_OLA=1 wherever a kernel exists.
-    const int ola_h = (window == 0 || window == N) ? ola_policy(n_in, hrir->taps, N - align_hop(ctx, N - (hrir->taps - 1))) : 0;
-    // batches of fewer than 48 streams keep the window policy below: their calls rarely have the blocks per workgroup the overlap-add tile
-    // needs (ola_min_blocks), and then run the overlap-save tile of the window chosen here
-    if (ola_h && window == 0 && n_streams >= 48) window = N;
-    if (window == 0) {
-        // (2) 8192- against 16384-frame windows where both can hold the HRIR (8192 / 16384): mono always 16384 (4320 taps 93 / 202),
-        //     stereo from ~2000 taps (2048: 157 / 160; 4320: 105 / 143), 3 channels from ~1800 (1024: 120 / 113; 2048: 107 / 111;
-        //     4320: 67 / 101), 5 from ~3200 (3000: 57.6 / 56.2; 3600: 52.4 / 56.9; 4320: 43 / 55) — both with the 8192-frame vector
-        //     variants <3,2> and <5,3> of the end of round 2 (generic kernels before: crossovers at ~1000 / ~2000) —, 7 from ~4400 (4320: 35.9 / 35.6; 5000: 29.7 / 33.2); 4, 6 and 8 channels only at the very
-        //     end of the 8192-frame window's range (6 and 8 from ~6100: 26.4 / 27.5 and 21.1 / 21.2 at 6145; 4 never: 38.2 / 36.9).
-        //     Odd counts cross early: the 8192-frame kernels pad them to whole pairs, the polyphase view has 2C pseudo-channels.
-        const int c = n_in;
-        //     Round 4: both fused kernels moved to the half-wave row transform (tile_ols.hpp; the 16384-frame kernels with their tables in
-        //     parts of four bins and all of them without SLP), re-measured (profiles/round4_v2/policy_sweeps_final.txt, 128 streams x 4 s):
-        //     stereo from ~1800 (1500: 180 / 171; 1800: 171 / 172), 3 channels from ~1800 (1500: 123 / 119; 1800: 117 / 119), 5 from ~3400
-        //     (3200: 63.7 / 60.5; 3500: 59.9 / 61.4), 7 from ~4400 (4320: 38.9 / 38.8; 4500: 36.4 / 36.8), 4 from ~5300 (5000: 59.9 / 58.5;
-        //     5300: 57.9 / 58.0), 6 from ~4700 (4320: 47.2 / 45.9; 5000: 39.4 / 44.9), 8 from ~5500 (5300: 30.1 / 29.0; 5600: 27.4 / 28.4).
-        const int from = c == 1 ? 0 : c == 2 ? 1800 : c == 3 ? 1800 : c == 5 ? 3400 : c == 7 ? 4400 : c == 4 ? 5300 : c == 6 ? 4700 : c == 8 ? 5500 : (1 << 30);
-        window = (hrir->taps >= from && fused2_ok) ? awk::kN2 : AW_DEFAULT_WINDOW;
-        // (3) small batches cannot fill 256 CUs with 16384-frame tiles (a 10 s stream is 40 of them): the 8192-frame kernels give
-        //     three times the tiles.  Crossover in streams (tools/small_batch_sweep.py, 4320 taps, 10 s per stream): mono 8
-        //     (4 streams 67 / 55, 8: 79 / 81), stereo 24 (16: 88 / 86, 24: 92 / 107), 3 channels 12, 5 channels 24; 16 elsewhere
-        const int min_streams = c == 1 ? 8 : c == 2 ? 24 : c == 3 ? 12 : c == 5 ? 24 : 16;
-        if (window == awk::kN2 && n_streams < min_streams && fits1) window = awk::kN;
-    }
-    // (4) 9+ channels near the end of the 8192-frame window's range (hop down to 2048 frames) against the partitioned path
-    //     (8192 / partitioned, G frames/s at 6145 taps, tools/path_sweep.py): with the one-pass vector kernels of round 2 the fused
-    //     kernels win to the end for 9-15 channels (9: 16.3 / 13.4, 12: 14.3 / 11.6, 14: 11.3 / 10.2, 15: 9.2 / 8.9); 16 channels
-    //     cross at ~6000 taps (5800: 10.1 / 9.5; 6145: 9.1 / 9.4)
-    const bool prefer_partitioned = getenv("AW_WINDOW") == nullptr && n_in >= 16 && hrir->taps >= 6000;
-    const bool force_partitioned = window == 4096 || prefer_partitioned;       // AW_WINDOW=4096: the partitioned path (A/B)
-    if (!force_partitioned && ((window == awk::kN2 && fits2) || (!fits1 && fused2_ok))) {
-        sp->path = 0; sp->fused2 = true;
-        sp->hop = align_hop(ctx, awk::kN2 - hist2);
-        sp->hist_len = awk::kN2 - sp->hop;                           // even, >= 2 * floor(taps / 2)
-        sp->partitions = 1;
-        sp->n_pairs = (2 * n_in + 1) / 2;                            // pseudo-pairs of the half-rate 2C-channel view
-    } else if (fits1 && !force_partitioned) {
-        sp->path = 0;
-        sp->hop = align_hop(ctx, N - (hrir->taps - 1));
-        sp->hist_len = N - sp->hop;
-        sp->partitions = 1;
-        sp->ola_h = ola_h;
-    } else {
-        sp->path = 1;
-        sp->hop = N / 2;
-        sp->partitions = (hrir->taps + sp->hop - 1) / sp->hop;
-        sp->hist_len = sp->partitions * sp->hop;
-        // every tuning knob of this path is read here, never on the process path
-        sp->cmac_group = sp->n_pairs > 8;                               // the marched kernel's lane groups hold up to 8 channel pairs
-        if (const char *e = getenv("AW_PART_CMAC")) sp->cmac_group = sp->cmac_group || std::strcmp(e, "group") == 0;
-        // forward kernel form: all pairs of a window in one workgroup up to 4 pairs (cfg 3: 11.2 against 12.1 ms); with more pairs
-        // the four-channel batches of 56-byte-or-wider frames each re-read every line (14 channels: fabric reads 4.3x the input),
-        // and one pair per workgroup — the pairs of a window side by side on one XCD — wins (27.0 -> 22.7 ms).  AW_PART_FWD=1|2 forces.
-        sp->fwd_one_pair = sp->n_pairs > 4;
-        if (const char *e = getenv("AW_PART_FWD")) sp->fwd_one_pair = atoi(e) == 1;
-        if (const char *e = getenv("AW_PART_HERM")) sp->herm_ok = atoi(e) != 0;          // A/B: 0 stores the last pair's redundant half too
-    }
-    // Long calls may run on the long-window kernels (device/tile_lw.hpp) whatever the path above — chosen per call, see lw_choose();
-    // they use the same history buffer.  AW_LW: 0 never, 32/64/128 force that window, unset = the measured policy.
-    sp->lw_plans.reserve(kLwPlanSlots);                                                  // one entry per window length: pointers into it stay valid (static_assert at kLwRowChoices)
-    if (const char *e = getenv("AW_LW")) sp->lw_mode = atoi(e);
-    if (n_in > 16) sp->lw_mode = 0;                                                      // up to eight channel pairs
+    // Path choice (host/path_policy.hpp).  Every tuning knob of it is read here, never on the process path; those of the context's
+    // LaunchCfg were read at aw_context_create.
+    awp::Knobs knobs;
+    knobs.window = env_knob("AW_WINDOW");
+    knobs.ola = env_knob("AW_OLA");
+    knobs.lw = env_knob("AW_LW");
+    if (const char *e = getenv("AW_PART_CMAC")) knobs.part_cmac_group = std::strcmp(e, "group") == 0;
+    knobs.part_fwd = env_knob("AW_PART_FWD");
+    knobs.part_herm = env_knob("AW_PART_HERM");
+    knobs.hop_align = ctx->cfg.hop_align;
+    knobs.ola_min_blocks_per_wg = ctx->cfg.ola_min_blocks_per_wg;
+    const awp::CreatePlan plan = awp::plan_create(sp_layout(sp), knobs, awk::fused_ola_rows(n_in, hrir->taps));
+    sp->path = plan.path; sp->fused2 = plan.fused2;
+    sp->hop = plan.hop; sp->hist_len = plan.hist_len; sp->partitions = plan.partitions; sp->n_pairs = plan.n_pairs;
+    sp->ola_h = plan.ola_h;
+    sp->cmac_group = plan.cmac_group; sp->fwd_one_pair = plan.fwd_one_pair; sp->herm_ok = plan.herm_ok;
+    sp->lw_mode = plan.lw_mode;
+    // Long calls may run on the long-window kernels (device/tile_lw.hpp) whatever the path above — chosen per call, see awp::lw_choose();
+    // they use the same history buffer.
+    sp->lw_plans.reserve(kLwPlanSlots);                                                  // one entry per window length: pointers into it stay valid (static_assert at kLwPlanSlots)
     // scratch budget per stream chunk: of the partitioned kernels and of the long-window ones, which also serve path-0 layouts
     if (const char *e = getenv("AW_SPEC_SCRATCH_MB")) sp->scratch_budget = (size_t)atoll(e) << 20;
     if (sp->lw_mode != 0) {
@@ -925,24 +809,18 @@ static aw_status sp_process_fused(aw_spatializer *sp, int s_base, int ns_total, 
     if (sp->profiling) { e0 = sp_get_event(sp); e1 = sp_get_event(sp); }
     long long dom_tiles = 0;
     sp->last_ola_h = 0;
-    if (sp->ola_h && !sp->fused2) {
-        // Overlap-add tile: every workgroup walks ONE contiguous run of blocks and pays ceil(hist / hop) warm-up blocks per run and per
-        // stream start; a call needs ola_min_blocks() blocks per workgroup for that to stay a few per cent (cfg 2: 67).  Shorter
-        // calls, and streams too long for 32-bit byte offsets, run the overlap-save tile on the same tables and history.
+    // Overlap-add tile where the call has the blocks for it (the CALL's block count — every stream of the spatializer — not this chunk's:
+    // the staged chunks of a host-entry call run the very tile the device entry runs on the whole batch, so both entries give the same
+    // bits); else the overlap-save tile on the same tables and history.
+    if (awp::use_ola_tile(sp_plan(sp), sp_layout(sp), frames, sp->ctx->cfg.persistent_wgs, sp->ctx->cfg.ola_min_blocks_per_wg)) {
         const int hop_ola = 512 * sp->ola_h;
-        // (the CALL's block count — every stream of the spatializer — not this chunk's: the staged chunks of a host-entry call run the
-        // very tile the device entry runs on the whole batch, so both entries give the same bits)
-        const long long blocks = (long long)sp->n_streams * ((frames + hop_ola - 1) / hop_ola);
-        const long long wgs = std::max(1, sp->ctx->cfg.persistent_wgs);
-        if (blocks >= (long long)ola_min_blocks(sp) * wgs && frames * sp->n_channels * 4LL <= awk::kOlaMaxBytes) {
-            p.hop = hop_ola;
-            p.tiles_per_stream = (int)((frames + hop_ola - 1) / hop_ola);
-            AW_HIP_TRY(awk::launch_fused_ola(p, sp->ola_h, ns_total, sp->ctx->stream, e0, e1));
-            sp->last_ola_h = sp->ola_h;
-            sp->dominant_frames = (long long)ns_total * frames;              // one launch covers the whole call
-            if (sp->profiling) sp->pending.emplace_back(e0, e1);
-            return AW_OK;
-        }
+        p.hop = hop_ola;
+        p.tiles_per_stream = (int)((frames + hop_ola - 1) / hop_ola);
+        AW_HIP_TRY(awk::launch_fused_ola(p, sp->ola_h, ns_total, sp->ctx->stream, e0, e1));
+        sp->last_ola_h = sp->ola_h;
+        sp->dominant_frames = (long long)ns_total * frames;              // one launch covers the whole call
+        if (sp->profiling) sp->pending.emplace_back(e0, e1);
+        return AW_OK;
     }
     if (sp->fused2) AW_HIP_TRY(awk::launch_fused_ols2(p, ns_total, sp->ctx->stream, e0, e1, &dom_tiles));
     else AW_HIP_TRY(awk::launch_fused_ols(p, ns_total, sp->ctx->stream, e0, e1, &dom_tiles));
@@ -1043,109 +921,19 @@ static aw_status sp_process_partitioned(aw_spatializer *sp, int s_base, int ns_t
 
 
 /* ---- long-window path (device/tile_lw.hpp) ---------------------------------------------------- */
-// Per call: windows of N = R x 4096 frames (R = 8 RA rows, lw_choose below), hop = N - hist_len; hist_len is the history the spatializer's
+// Per call: windows of N = R x 4096 frames (R = 8 RA rows), hop = N - hist_len; hist_len is the history the spatializer's
 // other kernel set keeps too (path 1: P x 4096 >= taps; path 0: the fused window minus its hop, any value >= taps - 1), so both kernel
 // sets serve the same spatializer and the choice is free per call.
-// Cost model (fabric bytes): the long-window kernels move 12 C + 24 bytes per WINDOW frame (input + rows
-// written, rows read + s1/s2 written, s1/s2 read + stereo out); what they are compared with: below.
-// Path-0 spatializers (HRIRs one fused window can hold): HRIR length from which the long-window kernels measure faster than
-// the fused 8192- / 16384-frame tiles on long calls (tools/lw_sweep.py, 128 streams x 10 s); 1 << 30 = never.
-// Round 4 (16-point rows kernel; profiles/round4_v1/lw_sweep.txt), G frames/s fused / long-window:
-//   C=1  8640 taps 147 / 113;   C=2  8640: 93 / 89;   C=3  6145: 85 / 70, 8640: 68 / 69;   C=4  4320: 70 / 60, 5300: 54 / 58;
-//   C=5  6145: 52 / 49, 8640: 41 / 48;   C=6  4320: 47 / 43, 5300: 38 / 43;   C=7  4320: 40.6 / 39.9, 5300: 37 / 40;   C=8  4320: 40 / 36, 5300: 32 / 36;
-//   C=9  4320: 30.2 / 29.4, 6145: 19 / 29;   C=10, 12  4320: 29 / 27, 26 / 24;   C=14  3000: 25.8 / 22.3, 4320: 20.5 / 22.3;   C=16  3000: 20.1 / 19.7, 4320: 16.4 / 19.6
-// The long-window kernels' rate does not depend on the HRIR length; the fused tiles' hop shrinks with it.
-static int lw_fused_crossover_taps(int channels, int ola_h) {
-    if (ola_h) return 5122;      // Round 6, spatializers on the overlap-add tile (blocks of 8 / 7 / 6 rows up to 4097 / 4609 / 5121 taps): faster than the
-                                 // long-window kernels on every layout and length it is chosen for (ola_policy(); profiles/round6_v1/ola_sweep.txt)
-    switch (channels) {          // profiles/round4_v2/policy_sweeps_final.txt and lw_sweep.txt (both fused kernels on the half-wave row transform)
-        case 1: return 10800;
-        case 2: return 9300;
-        case 3: return 9000;
-        case 4: return 5200;
-        case 5: return 7500;
-        case 6: return 5500;
-        case 7: return 4700;
-        case 8: return 5200;
-        case 13: return 4000;
-        case 14: return 4300;
-        case 15: case 16: return 3200;     // the two-pass layouts (15 channels at 3900 taps: 18.6 against 21.7)
-        default: return 4900;       // 9 - 12 channels
-    }
-}
-
-// A call runs as at most two groups of windows: `n` windows of R_a rows, then one window of R_b rows for what is left (either may be
-// absent).  Window lengths R = 8 RA, RA = 4 .. 16 without 11 and 13: the padded length sum(N) stays close to frames + windows x
-// history for every call length — the reference's cost per frame does not depend on the stream length (uniform partitions,
-// ConvolutionEngine.swift:93,232-367), and with three window lengths and one length per call this path's did (x 1.49 at 11 s).
-struct LwGroup { int R; int n_windows; long long frame0, frame_end; };
-struct LwCallPlan { int n_groups; LwGroup g[2]; double cost; };
-
-static const int kLwRowChoices[] = {32, 40, 48, 56, 64, 72, 80, 96, 112, 120, 128};
-static_assert(sizeof(kLwRowChoices) / sizeof(kLwRowChoices[0]) <= kLwPlanSlots, "aw_spatializer::lw_plans holds one table set per window length and never reallocates (sp_process_longwin keeps pointers into it)");
-
-static LwCallPlan lw_choose(const aw_spatializer *sp, int64_t frames, bool for_reserve = false) {
-    LwCallPlan none{};
-    if (sp->lw_mode == 0 || sp->n_channels > 16) return none;
-    if (sp->path == 0 && sp->lw_mode < 0 && sp->taps < lw_fused_crossover_taps(sp->n_channels, sp->ola_h)) return none;
-    // calls inside what aw_spatializer_reserve() sized never build tables: only window lengths whose tables exist are candidates
-    const bool existing_only = !for_reserve && frames <= sp->reserved_frames;
-    auto have = [&](int R) { for (const auto &pl : sp->lw_plans) if (pl.R == R) return true; return false; };
-    auto usable = [&](int R) {
-        const long long N = (long long)R * awk::kLwM, hop = N - sp->hist_len;
-        if (hop < N / 4) return false;                                  // the window must be mostly new frames
-        if (sp->lw_mode > 0 && sp->lw_mode != R) return false;
-        if (existing_only && !have(R)) return false;
-        return true;
-    };
-    const int C = sp->n_channels;
-    const double per_frame = 12.0 * C + 24.0;
-    // a second group costs three more launches and their ramps: ~40 us of the device's time, in the cost's currency (bytes at ~5 TB/s)
-    const double group_penalty = 2.0e8 / (double)std::max(1, sp->n_streams);
-    LwCallPlan best{};
-    for (int Ra : kLwRowChoices) {
-        if (!usable(Ra)) continue;
-        const long long Na = (long long)Ra * awk::kLwM, hopa = Na - sp->hist_len;
-        {   // one group
-            const long long n = (frames + hopa - 1) / hopa;
-            const double cost = (double)n * (double)Na * per_frame;
-            if (!best.n_groups || cost < best.cost) { best = LwCallPlan{1, {{Ra, (int)n, 0, frames}, {}}, cost}; }
-        }
-        if (sp->lw_mode > 0) continue;                                  // a forced window length: one group
-        for (int Rb : kLwRowChoices) {
-            if (Rb >= Ra || !usable(Rb)) continue;
-            const long long Nb = (long long)Rb * awk::kLwM, hopb = Nb - sp->hist_len;
-            const long long n = frames > hopb ? (frames - hopb + hopa - 1) / hopa : 0;
-            if (n < 1) continue;                                        // (the remainder window alone: the one-group case of Rb)
-            const long long rest = frames - n * hopa;
-            if (rest <= 0) continue;
-            const double cost = ((double)n * (double)Na + (double)Nb) * per_frame + group_penalty;
-            if (cost < best.cost) best = LwCallPlan{2, {{Ra, (int)n, 0, n * hopa}, {Rb, 1, n * hopa, frames}}, cost};
-        }
-    }
-    if (!best.n_groups || sp->lw_mode > 0) return best;
-    long long row_tiles = 0;
-    for (int i = 0; i < best.n_groups; ++i) row_tiles += (long long)sp->n_streams * best.g[i].n_windows * (best.g[i].R / 2);
-    if (row_tiles < 32) return none;     // (measured down to ONE stream x 10 s, 64 row tiles: 7 channels x 32768 taps 8.2 against 3.9 G frames/s partitioned)
-    // path 0: the crossovers above were measured on batches that fill the chip; a small batch stays on the fused tiles, which serve
-    // a single stream well (cfg 1: 9.7 G frames/s), until its row tiles cover the CUs twice
-    if (sp->path == 0 && row_tiles < 2LL * sp->ctx->cfg.cus) return none;
-    double other_cost;
-    if (sp->path == 0) {
-        // past the measured crossover (above) the long call only has to fill its windows to 80 %
-        other_cost = 1.25 * (double)frames * per_frame;
-    } else {
-        // Partitioned kernels, in the same currency (fabric-byte equivalents at the rate both kernel sets reach): a long call costs
-        // ~110 + 13 C bytes per output frame up to eight channels (measured 20-23 G frames/s for C = 7, 29 for C = 2; the one-pair
-        // forward kernels of wider layouts ~30 C), 86 % of it per input WINDOW (forward transform + marched CMAC) — and a call of
-        // n blocks transforms n + P - 1 windows, which is what makes short calls expensive there — and 14 % per output block.
-        // tools/lw_calls_sweep.py (G frames/s, partitioned / long-window, 128 streams x 7 channels x 32768 taps): 16 384 frames
-        // 6.2 / 5.9, 32 768: 9.9 / 10.9, 49 152: 11.5 / 15.6, 65 536: 13.1 / 20.0, 131 072: 15.8 / 21.0, 480 000: 20.0 / 35.8.
-        const double b_part = C <= 8 ? 110.0 + 13.0 * C : 30.0 * C;
-        const long long blocks = (frames + sp->hop - 1) / sp->hop;
-        other_cost = (double)sp->hop * b_part * (0.86 * (double)(blocks + sp->partitions - 1) + 0.14 * (double)blocks);
-    }
-    return best.cost < other_cost ? best : none;
+// The choice is awp::lw_choose (host/path_policy.hpp) over these inputs.
+using awp::LwCallPlan;
+using awp::LwGroup;
+static_assert(awp::kLwRowChoiceCount <= (int)kLwPlanSlots, "aw_spatializer::lw_plans holds one table set per window length and never reallocates (sp_process_longwin keeps pointers into it)");
+static awp::LwInputs lw_inputs(const aw_spatializer *sp) {
+    awp::LwInputs in{sp_layout(sp), sp_plan(sp), sp->ctx->cfg.cus, sp->reserved_frames, 0u};
+    for (int i = 0; i < awp::kLwRowChoiceCount; ++i)
+        for (const auto &pl : sp->lw_plans)
+            if (pl.R == awp::kLwRowChoices[i]) in.have |= 1u << i;
+    return in;
 }
 
 static aw_status lw_get_plan(aw_spatializer *sp, int R, const aw_spatializer::LwPlan **out) {
@@ -1330,9 +1118,10 @@ static int64_t part_longest_call(const aw_spatializer *sp, int64_t max_frames) {
     const int64_t B = sp->hop, n_blocks = (max_frames + B - 1) / B;
     const int64_t stride = std::max<int64_t>(1, n_blocks / 2048);
     int64_t longest = 0;
+    const awp::LwInputs in = lw_inputs(sp);
     for (int64_t nb = 1;; nb += stride) {
         const int64_t f = std::min<int64_t>(std::min(nb, n_blocks) * B, max_frames);
-        if (!lw_choose(sp, f, true).n_groups) longest = std::min<int64_t>(f + (stride - 1) * B, max_frames);
+        if (!awp::lw_choose(in, f, true).n_groups) longest = std::min<int64_t>(f + (stride - 1) * B, max_frames);
         if (nb >= n_blocks) break;
     }
     return longest;
@@ -1346,7 +1135,7 @@ aw_status aw_spatializer_reserve(aw_spatializer *sp, int64_t max_frames) try {
     AW_HIP_TRY(hipSetDevice(sp->ctx->device));
     std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
     sp->reserve_tables_us = sp->reserve_upload_us = sp->reserve_scratch_us = 0;
-    const LwCallPlan lw_res = lw_choose(sp, max_frames, true);
+    const LwCallPlan lw_res = awp::lw_choose(lw_inputs(sp), max_frames, true);
     if (sp->path == 1 || lw_res.n_groups) {
         for (int i = 0; i < lw_res.n_groups; ++i) {
             const aw_spatializer::LwPlan *plan = nullptr;
@@ -1434,7 +1223,7 @@ static aw_status sp_run_streams(aw_spatializer *sp, const LwCallPlan &lw, int s_
 static LwCallPlan sp_begin_call(aw_spatializer *sp, int64_t frames, uint64_t *pos0 = nullptr) {
     if (pos0) *pos0 = sp->position;
     sp->position += (uint64_t)frames;
-    const LwCallPlan lw = lw_choose(sp, frames);
+    const LwCallPlan lw = awp::lw_choose(lw_inputs(sp), frames);
     sp->last_lw_R = lw.n_groups ? lw.g[0].R : 0;
     sp->last_lw_R2 = lw.n_groups > 1 ? lw.g[1].R : 0;
     return lw;

@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from policy_points import LONG_HRIR_PATHS, LONG_HRIR_STREAMS, WINDOW_POLICY
+
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
 
@@ -17,7 +19,7 @@ def aw():
 
 
 def _aligned(hop):
-    """runtime.cpp align_hop: tiles start on 64-frame boundaries of the timeline."""
+    """host/path_policy.hpp align_hop: tiles start on 64-frame boundaries of the timeline."""
     return hop - hop % 64 if hop > 1024 else hop
 
 
@@ -104,12 +106,9 @@ def test_hrir_lengths_on_the_fused_path(aw, oracle, taps):
     assert oracle.peak_rel_error(y[0], ref) < TOL
 
 
-@pytest.mark.parametrize("channels,taps,streams,fft", [(2, 4320, 1, 8192), (2, 4320, 23, 8192), (2, 4320, 24, 16384), (2, 1799, 64, 8192), (2, 1800, 64, 16384), (1, 4320, 7, 8192), (1, 4320, 8, 16384),
-                                                       (8, 4320, 128, 8192), (8, 5499, 16, 8192), (8, 5500, 16, 16384), (8, 6100, 4, 8192), (2, 6146, 1, 16384), (4, 5299, 128, 8192), (4, 5300, 128, 16384), (6, 4699, 128, 8192), (6, 4700, 128, 16384),
-                                                       (1, 512, 16, 16384), (3, 1799, 128, 8192), (3, 1800, 128, 16384), (3, 4320, 128, 16384), (3, 4320, 11, 8192), (5, 4320, 32, 16384), (5, 3399, 128, 8192), (5, 3400, 128, 16384),
-                                                       (7, 4320, 128, 8192), (7, 4399, 16, 8192), (7, 4400, 16, 16384), (12, 6145, 16, 8192), (9, 6145, 16, 8192), (13, 6000, 16, 8192), (16, 5900, 16, 8192)])
+@pytest.mark.parametrize("channels,taps,streams,fft", WINDOW_POLICY)
 def test_window_policy(aw, oracle, channels, taps, streams, fft):
-    """runtime.cpp: the measured crossover of the two fused kernels by layout and HRIR length, 8192-frame windows for
+    """host/path_policy.hpp: the measured crossover of the two fused kernels by layout and HRIR length, 8192-frame windows for
     batches too small to fill the chip with 16384-frame tiles, 16384 whenever one 8192-frame window cannot hold the HRIR."""
     h = oracle.synth_hrir(14, taps, seed=1)
     lt = (np.arange(channels) % 14).astype(np.int32)
@@ -253,18 +252,16 @@ def test_long_tap_partitioned_path(aw, oracle, golden_dir):
     assert oracle.peak_rel_error(sp.process(x)[0], g["expected"]) < TOL
 
 
-@pytest.mark.parametrize("taps,channels,path,fft", [(6146, 2, 0, 16384), (7800, 8, 0, 16384), (8640, 8, 0, 16384), (11200, 8, 0, 16384), (11201, 8, 1, 8192), (8640, 7, 0, 16384), (11500, 7, 0, 16384), (12288, 5, 0, 16384), (8500, 6, 0, 16384),
-                                                    (12288, 7, 1, 8192), (10500, 4, 0, 16384), (10501, 4, 1, 8192), (12288, 6, 0, 16384), (12290, 6, 1, 8192), (12290, 5, 1, 8192), (6100, 12, 0, 8192), (6146, 12, 1, 8192), (6145, 9, 0, 8192), (6000, 16, 1, 8192), (20000, 3, 1, 8192),
-                                                    (20000, 1, 1, 8192), (40000, 2, 1, 8192), (70000, 7, 1, 8192)])
+@pytest.mark.parametrize("taps,channels,path,fft", LONG_HRIR_PATHS)
 def test_long_hrir_paths_chunks_and_state(aw, oracle, taps, channels, path, fft, monkeypatch):
     """HRIRs beyond one 8192-frame window: up to 12288 taps (cfg 4: 4320 taps resampled x2 = 8640) run fused on
-    16384-frame windows where that measures faster (runtime.cpp: per channel count), longer ones — and the long end
+    16384-frame windows where that measures faster (host/path_policy.hpp: per channel count), longer ones — and the long end
     of the wider layouts — on the partitioned path (with stream chunking of its scratch)."""
     monkeypatch.setenv("AW_SPEC_SCRATCH_MB", "3")          # forces several stream chunks
     h = oracle.synth_hrir(14, taps, seed=taps)
     lt = np.resize(np.array([0, 8, 6, 6, 4, 12, 2, 10], dtype=np.int32), channels)
     rt = np.resize(np.array([1, 7, 13, 13, 5, 11, 3, 9], dtype=np.int32), channels)
-    S, F = 3, 30000
+    S, F = LONG_HRIR_STREAMS, 30000
     x = oracle.synth_input(S, F, channels, seed=21)
     sp = aw.Spatializer(aw.HRIR(h), lt, rt, n_streams=S)
     assert sp.info()["path"] == path and sp.info()["fft"] == fft

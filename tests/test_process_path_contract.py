@@ -31,6 +31,8 @@ def test_no_environment_lookups_on_process_paths():
         assert "getenv" not in _body(rt, fn), fn
     eq = open(os.path.join(ROOT, "airwave_amd", "csrc", "eq_runtime.cpp")).read()
     assert "getenv" not in eq
+    # the planner those entries call is pure: the knobs come to it as arguments
+    assert "getenv" not in open(os.path.join(ROOT, "airwave_amd", "csrc", "host", "path_policy.hpp")).read()
     for f in ("kernels.hip", "march_kernels.hip", "eq_kernels.hip"):
         src = open(os.path.join(ROOT, "airwave_amd", "csrc", "device", f)).read()
         for m in re.finditer(r"getenv", src):       # only inside prepare_kernels (context creation)

@@ -1,5 +1,5 @@
 """Per-call choice for long HRIRs (path-1 spatializers): partitioned kernels (AW_LW=0) against the policy's choice (lw_choose in
-runtime.cpp) by call length.   python tools/lw_calls_sweep.py [channels]      (env: S=128 TAPS=32768)"""
+airwave_amd/csrc/host/path_policy.hpp) by call length.   python tools/lw_calls_sweep.py [channels]      (env: S=128 TAPS=32768)"""
 import os, sys, time
 import numpy as np
 import torch

@@ -1,6 +1,6 @@
 """Long-window kernels (tile_lw.hpp) against the default choice of aw_spatializer_create for path-0 layouts (HRIRs one fused
 window can hold), by HRIR length: G stereo frames/s, S streams x SECONDS s at 48 kHz, synthetic HRIR.  Feeds
-lw_fused_crossover_taps() in runtime.cpp.   python tools/lw_sweep.py [channels ...]     (env: S=128 SECONDS=10 TAPS=...)"""
+lw_crossover_taps of the table in airwave_amd/csrc/host/path_policy.hpp.   python tools/lw_sweep.py [channels ...]     (env: S=128 SECONDS=10 TAPS=...)"""
 import os, sys, time
 import numpy as np
 import torch

@@ -1,6 +1,6 @@
 """The overlap-add tile (tile_ola.hpp) against what served the layout before it (the overlap-save tiles on 8192- or 16384-frame windows,
 whichever the round-4 policy picks: AW_OLA=0) and against the long-window kernels (AW_LW=128), by layout and HRIR length: G stereo
-frames/s, S streams x SECONDS s at 48 kHz, synthetic HRIR.  Feeds ola_policy() and lw_fused_crossover_taps() in runtime.cpp.
+frames/s, S streams x SECONDS s at 48 kHz, synthetic HRIR.  Feeds ola_need and lw_crossover_taps of the table in airwave_amd/csrc/host/path_policy.hpp.
     python tools/ola_sweep.py [channels ...]     (env: S=128 SECONDS=10 TAPS=...)"""
 import os, sys, time
 import numpy as np

@@ -1,6 +1,7 @@
 """Path choice by channel count and HRIR length: two AW_WINDOW settings side by side (default WINS=16384,4096: the 16384-frame
 window kernels against the partitioned path, which AW_WINDOW=4096 forces; WINS=8192,4096 for the end of the 8192-frame
-window's range).  TAPS=a,b,c overrides the HRIR lengths.  Run on the GPU box."""
+window's range).  TAPS=a,b,c overrides the HRIR lengths.  Run on the GPU box.
+Feeds fused2_upto and the 16-channel rule of airwave_amd/csrc/host/path_policy.hpp."""
 import os, sys, time
 import numpy as np
 import torch

@@ -1,4 +1,5 @@
-"""Small batches: 8192- against 16384-frame windows by stream count (10 s per stream, 4320 taps).  Run on the GPU box."""
+"""Small batches: 8192- against 16384-frame windows by stream count (10 s per stream, 4320 taps).  Run on the GPU box.
+Feeds fused2_min_streams of the table in airwave_amd/csrc/host/path_policy.hpp."""
 import os, sys, time
 import numpy as np
 import torch

@@ -1,5 +1,6 @@
 """Fused window choice: frames/s of the 8192- and 16384-frame window kernels against HRIR length (8 channels,
-128 streams x 4 s, synthetic HRIR).  Run on the GPU box; AW_WINDOW is read at spatializer creation."""
+128 streams x 4 s, synthetic HRIR).  Run on the GPU box; AW_WINDOW is read at spatializer creation.
+Feeds fused2_from of the table in airwave_amd/csrc/host/path_policy.hpp."""
 import os, sys, time
 import numpy as np
 import torch
