@@ -1,5 +1,5 @@
 // limiter_tile.hpp — device code of the limiter kernel (rules: limiter.hpp): one workgroup of kLimThreads threads produces one tile of
-// kLimTile output frames of one stream.  Plain C++ over an execution context (limiter_kernels.hip: the GPU's; tests/emu/emu_limiter.cpp:
+// kLimTile output frames of one stream.  Plain C++ over an execution context (stage_gpu_ctx.hpp: the GPU's; tests/emu/emu_stage_ctx.hpp:
 // threads on the CPU), so the code hipcc compiles is the code the emulation runs.
 //
 // LDS holds three images (49,440 bytes: three workgroups per CU):

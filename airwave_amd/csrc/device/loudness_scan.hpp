@@ -1,5 +1,6 @@
 // loudness_scan.hpp — the K-weighted hop energies of batches of stereo streams (rules: loudness.hpp), device code shared between hipcc
-// (loudness_kernels.hip) and the CPU thread-emulation harness (tests/emu/emu_loudness.cpp).
+// (loudness_kernels.hip over scan_gpu_ctx.hpp's context, the EQ kernels' too) and the CPU thread-emulation harness
+// (tests/emu/emu_loudness.cpp over emu_ctx.hpp's).
 //
 // The K-weighting is a cascade of two Float64 biquads, a time recurrence over the whole stream, so the time axis is parallelised the
 // way the parametric EQ's is, with the machinery of eq_cascade.hpp as it stands: one workgroup per stream walks the call in spans of

@@ -1,50 +1,14 @@
 // truepeak_kernels.hip — gfx950 kernel of the per-stream true peak (device code in truepeak_tile.hpp).
 #include "truepeak_kernels.hpp"
+#include "stage_gpu_ctx.hpp"
 
 namespace awk {
-
-namespace {
-
-struct TpGpuCtx {
-    float *lds_;
-    __device__ __forceinline__ int tid() const { return (int)threadIdx.x; }
-    __device__ __forceinline__ float *lds() const { return lds_; }
-    __device__ __forceinline__ void barrier() const { __syncthreads(); }
-    __device__ __forceinline__ void ld16(const float *g, float (&x)[4]) const {
-        const float4 v = *reinterpret_cast<const float4 *>(g);
-        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-    }
-    __device__ __forceinline__ void st16(float *l, const float (&x)[4]) const { *reinterpret_cast<float4 *>(l) = make_float4(x[0], x[1], x[2], x[3]); }
-    __device__ __forceinline__ void ld_lds16(const float *l, float *x) const {
-        const float4 v = *reinterpret_cast<const float4 *>(l);
-        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-    }
-    __device__ __forceinline__ void ld_lds8(const float *l, float *x) const {
-        const float2 v = *reinterpret_cast<const float2 *>(l);
-        x[0] = v.x; x[1] = v.y;
-    }
-    // every wave is launched whole and keeps its lanes together up to here, so the shuffles see all 64 lanes
-    __device__ __forceinline__ uint32_t wave_max(uint32_t v) const {
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) { const uint32_t o = __shfl_xor(v, m); v = o > v ? o : v; }
-        return v;
-    }
-    __device__ __forceinline__ unsigned wave_sum(unsigned v) const {
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-        return v;
-    }
-    __device__ __forceinline__ void atomic_max(uint32_t *a, uint32_t v) const { atomicMax(a, v); }
-    __device__ __forceinline__ void atomic_add(unsigned long long *a, unsigned long long v) const { atomicAdd(a, v); }
-};
-
-}  // namespace
 
 // grid: (tiles of a stream, streams)
 __global__ void __launch_bounds__(kTpThreads) aw_true_peak_kernel(TruePeakParams p) {
     __shared__ __align__(16) float tp_lds[kTpLdsFloats];
-    TpGpuCtx ctx{tp_lds};
-    truepeak_tile<TpGpuCtx>(ctx, p, (long long)blockIdx.y, (long long)blockIdx.x);
+    StageGpuCtx<float> ctx{tp_lds};
+    truepeak_tile<StageGpuCtx<float>>(ctx, p, (long long)blockIdx.y, (long long)blockIdx.x);
 }
 
 hipError_t prepare_truepeak_kernels() { return hipSuccess; }      // static LDS under 64 KB: nothing to set

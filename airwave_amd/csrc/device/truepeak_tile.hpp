@@ -1,5 +1,5 @@
 // truepeak_tile.hpp — device code of the true-peak kernel (rules: truepeak.hpp): one workgroup of kTpThreads threads measures one tile of
-// kTpTile frames of one stream.  Plain C++ over an execution context (truepeak_kernels.hip: the GPU's; tests/emu/emu_true_peak.cpp:
+// kTpTile frames of one stream.  Plain C++ over an execution context (stage_gpu_ctx.hpp: the GPU's; tests/emu/emu_stage_ctx.hpp:
 // threads on the CPU), so the code hipcc compiles is the code the emulation runs.
 //
 // A tile goes from global memory into LDS once, in 16-byte words whatever the stream's alignment (a dense [streams][frames][2] chunk

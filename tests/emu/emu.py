@@ -1,18 +1,19 @@
 """TEST-ONLY: ctypes access to the thread-emulated tile kernel (tests/emu/emu_harness.cpp)."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
+
+import _build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
 _DEFS = os.environ.get("AW_EMU_DEFINES", "").split()          # e.g. "-DAW_SUBFFT_SKEW=1": emulate a tuning variant
 _LIB = os.path.join(_HERE, "libemu.so" if not _DEFS else "libemu_variant.so")
-_SRCS = [os.path.join(_HERE, "emu_harness.cpp"), os.path.join(_HERE, "emu_lw.cpp"), os.path.join(_ROOT, "airwave_amd/csrc/host/tables.cpp"),
-         os.path.join(_ROOT, "airwave_amd/csrc/host/eq.cpp")]
-_DEPS = _SRCS + [os.path.join(_HERE, "emu_ctx.hpp")] + [os.path.join(_ROOT, "airwave_amd/csrc/device", f) for f in ("tile_ols.hpp", "tile_ola.hpp", "tile_ols2.hpp", "tile_march.hpp", "tile_lw.hpp", "tile_lw16.hpp", "cplx.hpp", "eq_cascade.hpp")] + [
-    os.path.join(_ROOT, "airwave_amd/csrc/host/tables.hpp"), os.path.join(_ROOT, "airwave_amd/csrc/host/eq.hpp")]
+# the translation units compile side by side (the long-window kernels alone are 176 template instantiations)
+_UNITS = [(os.path.join(_HERE, "emu_harness.cpp"), _DEFS), (os.path.join(_HERE, "emu_lw.cpp"), _DEFS),
+          (os.path.join(_ROOT, "airwave_amd/csrc/host/tables.cpp"), _DEFS), (os.path.join(_ROOT, "airwave_amd/csrc/host/eq.cpp"), _DEFS)] + [
+    (os.path.join(_HERE, "emu_lw.cpp"), _DEFS + [f"-DEMU_LW_PART={k}"]) for k in (1, 2, 3)]
 _lib = None
 
 fp = ctypes.POINTER(ctypes.c_float)
@@ -22,17 +23,7 @@ ip = ctypes.POINTER(ctypes.c_int32)
 def lib():
     global _lib
     if _lib is None:
-        if _DEFS or not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(d) for d in _DEPS):
-            # the translation units compile side by side (the long-window kernels alone are 176 template instantiations)
-            units = [(src, []) for src in _SRCS] + [(os.path.join(_HERE, "emu_lw.cpp"), [f"-DEMU_LW_PART={k}"]) for k in (1, 2, 3)]
-            objs = [f"{_LIB}.{i}.o" for i in range(len(units))]
-            procs = [subprocess.Popen(["g++", "-std=c++20", "-O2", "-pthread", "-fPIC"] + _DEFS + extra + ["-c", src, "-o", o]) for (src, extra), o in zip(units, objs)]
-            if any(p.wait() != 0 for p in procs):
-                raise RuntimeError("emulation harness failed to compile")
-            subprocess.run(["g++", "-shared", "-pthread", "-o", _LIB] + objs, check=True)
-            for o in objs:
-                os.remove(o)
-        _lib = ctypes.CDLL(_LIB)
+        _lib = _build.load(_LIB, _UNITS, link_flags=["-pthread"], force=bool(_DEFS))          # a variant is built afresh every time
         _lib.emu_fused_ols.argtypes = [fp, fp, fp, fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ip, ip,
                                        ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int]
         _lib.emu_fused_ola.argtypes = [fp, fp, fp, fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ip, ip,

@@ -1,8 +1,9 @@
 #pragma once
-// emu_ctx.hpp — TEST-ONLY thread emulation of the HIP tile kernels: the execution context shared by emu_harness.cpp and emu_lw.cpp.
+// emu_ctx.hpp — TEST-ONLY thread emulation of the HIP tile kernels: the execution context shared by emu_harness.cpp, emu_lw.cpp and
+// emu_loudness.cpp (the output-stage kernels' context: emu_stage_ctx.hpp; the workgroup runner of both: emu_workgroup.hpp).
 //
 // Compiles airwave_amd/csrc/device/tile_ols.hpp (the exact code the GPU runs) with g++ and
-// executes one workgroup as 512 std::threads: workgroup barriers are std::barrier(512),
+// executes one workgroup as 512 CPU threads: workgroup barriers are std::barrier(512),
 // wave-level syncs are std::barrier(64).  It exists so index math, twiddles and LDS hazards can
 // be checked on the CPU-only build container before spending GPU minutes.  It is NOT part of the
 // product library and nothing under airwave_amd/ links it.
@@ -12,8 +13,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <thread>
 #include <vector>
+
+#include "emu_workgroup.hpp"
 
 #include "../../airwave_amd/csrc/device/tile_ols.hpp"
 #include "../../airwave_amd/csrc/device/tile_ola.hpp"

@@ -37,25 +37,21 @@ static int emu_fused_ols2(const float *in, float *out, const float *hist, const 
     auto run = [&](bool interior, long long n_tiles) {
         const long long G = n_tiles < 3 ? n_tiles : 3;
         for (long long g = 0; g < G; ++g) {
-            std::vector<std::thread> th;
-            th.reserve(kThreads);
-            for (int t = 0; t < kThreads; ++t)
-                th.emplace_back([&, t]() {
-                    EmuCtx ctx{t, &sh};
-                    if (interior) {
-                        switch (n_channels) {
-                            case 1: tiles_fused_ols2<EmuCtx, 1, 1, true>(ctx, p, g, G, n_tiles); break;
-                            case 2: tiles_fused_ols2<EmuCtx, 2, 1, true>(ctx, p, g, G, n_tiles); break;
-                            case 3: tiles_fused_ols2<EmuCtx, 3, 2, true>(ctx, p, g, G, n_tiles); break;
-                            case 5: tiles_fused_ols2<EmuCtx, 5, 3, true>(ctx, p, g, G, n_tiles); break;
-                            case 7: tiles_fused_ols2<EmuCtx, 7, 4, true>(ctx, p, g, G, n_tiles); break;
-                            default: tiles_fused_ols2<EmuCtx, 8, 4, true>(ctx, p, g, G, n_tiles); break;
-                        }
-                    } else {
-                        tiles_fused_ols2<EmuCtx, 0, 0, false>(ctx, p, g, G, n_tiles);
+            emu_workgroup(kThreads, [&](int t) {
+                EmuCtx ctx{t, &sh};
+                if (interior) {
+                    switch (n_channels) {
+                        case 1: tiles_fused_ols2<EmuCtx, 1, 1, true>(ctx, p, g, G, n_tiles); break;
+                        case 2: tiles_fused_ols2<EmuCtx, 2, 1, true>(ctx, p, g, G, n_tiles); break;
+                        case 3: tiles_fused_ols2<EmuCtx, 3, 2, true>(ctx, p, g, G, n_tiles); break;
+                        case 5: tiles_fused_ols2<EmuCtx, 5, 3, true>(ctx, p, g, G, n_tiles); break;
+                        case 7: tiles_fused_ols2<EmuCtx, 7, 4, true>(ctx, p, g, G, n_tiles); break;
+                        default: tiles_fused_ols2<EmuCtx, 8, 4, true>(ctx, p, g, G, n_tiles); break;
                     }
-                });
-            for (auto &x : th) x.join();
+                } else {
+                    tiles_fused_ols2<EmuCtx, 0, 0, false>(ctx, p, g, G, n_tiles);
+                }
+            });
         }
     };
     run(true, (long long)n_streams * (hi - lo));
@@ -101,60 +97,56 @@ int emu_fused_ols(const float *in, float *out, const float *hist, const float *t
     auto run = [&](bool interior, long long n_tiles) {
         const long long G = n_tiles < 3 ? n_tiles : 3;
         for (long long g = 0; g < G; ++g) {
-            std::vector<std::thread> th;
-            th.reserve(kThreads);
-            for (int t = 0; t < kThreads; ++t)
-                th.emplace_back([&, t]() {
-                    EmuCtx ctx{t, &sh};
-                    // mirror of awk::launch_fused_ols' variant choice
-                    if (interior) {
-                        // wide layouts: first pass over 4 pairs, then an accumulating pass over the rest (input and tables shifted)
-                        TileParams q = p;
-                        q.in = p.in + 8;
-                        q.tab = p.tab + 4 * (long long)kN;
-                        switch (n_channels) {
-                            case 2: tiles_fused_ols<EmuCtx, 2, 1, true>(ctx, p, g, G, n_tiles); break;
-                            case 3: tiles_fused_ols<EmuCtx, 3, 2, true>(ctx, p, g, G, n_tiles); break;
-                            case 4: tiles_fused_ols<EmuCtx, 4, 2, true>(ctx, p, g, G, n_tiles); break;
-                            case 5: tiles_fused_ols<EmuCtx, 5, 3, true>(ctx, p, g, G, n_tiles); break;
-                            case 6: tiles_fused_ols<EmuCtx, 6, 3, true>(ctx, p, g, G, n_tiles); break;
-                            case 7: tiles_fused_ols<EmuCtx, 7, 4, true>(ctx, p, g, G, n_tiles); break;
-                            case 8: tiles_fused_ols<EmuCtx, 8, 4, true>(ctx, p, g, G, n_tiles); break;
-                            // variant 1 (the default): one pass over two eight-channel groups; variant 5: the two-pass form (AW_WIDE_TWO_PASS=1)
-                            case 15: tiles_fused_ols<EmuCtx, 15, 4, true>(ctx, p, g, G, n_tiles); ctx.barrier(); tiles_fused_ols<EmuCtx, 15, 4, true, true>(ctx, q, g, G, n_tiles); break;
-                            case 9: tiles_fused_ols<EmuCtx, 9, 5, true>(ctx, p, g, G, n_tiles); break;
-                            case 11: tiles_fused_ols<EmuCtx, 11, 6, true>(ctx, p, g, G, n_tiles); break;
-                            case 13: tiles_fused_ols<EmuCtx, 13, 7, true>(ctx, p, g, G, n_tiles); break;
-                            case 10: if (variant != 5) { tiles_fused_ols<EmuCtx, 10, 5, true>(ctx, p, g, G, n_tiles); break; }
-                                     tiles_fused_ols<EmuCtx, 10, 4, true>(ctx, p, g, G, n_tiles); ctx.barrier(); tiles_fused_ols<EmuCtx, 10, 1, true, true>(ctx, q, g, G, n_tiles); break;
-                            case 14: if (variant != 5) { tiles_fused_ols<EmuCtx, 14, 7, true>(ctx, p, g, G, n_tiles); break; }
-                                     tiles_fused_ols<EmuCtx, 14, 4, true>(ctx, p, g, G, n_tiles); ctx.barrier(); tiles_fused_ols<EmuCtx, 14, 3, true, true>(ctx, q, g, G, n_tiles); break;
-                            case 12: if (variant != 5) { tiles_fused_ols<EmuCtx, 12, 6, true>(ctx, p, g, G, n_tiles); break; }
-                                     tiles_fused_ols<EmuCtx, 12, 4, true>(ctx, p, g, G, n_tiles); ctx.barrier(); tiles_fused_ols<EmuCtx, 12, 2, true, true>(ctx, q, g, G, n_tiles); break;
-                            default: tiles_fused_ols<EmuCtx, 16, 4, true>(ctx, p, g, G, n_tiles); ctx.barrier(); tiles_fused_ols<EmuCtx, 16, 4, true, true>(ctx, q, g, G, n_tiles); break;
-                        }
-                    } else if (p.n_pairs > 4 && p.n_pairs <= 8 && (variant == 1 || variant == 5)) {      // launch_gen's two passes for 9-16 channels
-                        TileParams q = p;
-                        q.in = p.in + 8; q.hist = p.hist + 8; q.tab = p.tab + 4 * (long long)kN; q.ch_base = 8;
-                        tiles_fused_ols<EmuCtx, 0, 4, false>(ctx, p, g, G, n_tiles);
-                        ctx.barrier();
-                        switch (p.n_pairs - 4) {
-                            case 1: tiles_fused_ols<EmuCtx, 0, 1, false, true>(ctx, q, g, G, n_tiles); break;
-                            case 2: tiles_fused_ols<EmuCtx, 0, 2, false, true>(ctx, q, g, G, n_tiles); break;
-                            case 3: tiles_fused_ols<EmuCtx, 0, 3, false, true>(ctx, q, g, G, n_tiles); break;
-                            default: tiles_fused_ols<EmuCtx, 0, 4, false, true>(ctx, q, g, G, n_tiles); break;
-                        }
-                    } else {
-                        switch (p.n_pairs <= 4 && (variant == 1 || variant == 5) ? p.n_pairs : 0) {
-                            case 1: tiles_fused_ols<EmuCtx, 0, 1, false>(ctx, p, g, G, n_tiles); break;
-                            case 2: tiles_fused_ols<EmuCtx, 0, 2, false>(ctx, p, g, G, n_tiles); break;
-                            case 3: tiles_fused_ols<EmuCtx, 0, 3, false>(ctx, p, g, G, n_tiles); break;
-                            case 4: tiles_fused_ols<EmuCtx, 0, 4, false>(ctx, p, g, G, n_tiles); break;
-                            default: tiles_fused_ols<EmuCtx, 0, 0, false>(ctx, p, g, G, n_tiles); break;
-                        }
+            emu_workgroup(kThreads, [&](int t) {
+                EmuCtx ctx{t, &sh};
+                // mirror of awk::launch_fused_ols' variant choice
+                if (interior) {
+                    // wide layouts: first pass over 4 pairs, then an accumulating pass over the rest (input and tables shifted)
+                    TileParams q = p;
+                    q.in = p.in + 8;
+                    q.tab = p.tab + 4 * (long long)kN;
+                    switch (n_channels) {
+                        case 2: tiles_fused_ols<EmuCtx, 2, 1, true>(ctx, p, g, G, n_tiles); break;
+                        case 3: tiles_fused_ols<EmuCtx, 3, 2, true>(ctx, p, g, G, n_tiles); break;
+                        case 4: tiles_fused_ols<EmuCtx, 4, 2, true>(ctx, p, g, G, n_tiles); break;
+                        case 5: tiles_fused_ols<EmuCtx, 5, 3, true>(ctx, p, g, G, n_tiles); break;
+                        case 6: tiles_fused_ols<EmuCtx, 6, 3, true>(ctx, p, g, G, n_tiles); break;
+                        case 7: tiles_fused_ols<EmuCtx, 7, 4, true>(ctx, p, g, G, n_tiles); break;
+                        case 8: tiles_fused_ols<EmuCtx, 8, 4, true>(ctx, p, g, G, n_tiles); break;
+                        // variant 1 (the default): one pass over two eight-channel groups; variant 5: the two-pass form (AW_WIDE_TWO_PASS=1)
+                        case 15: tiles_fused_ols<EmuCtx, 15, 4, true>(ctx, p, g, G, n_tiles); ctx.barrier(); tiles_fused_ols<EmuCtx, 15, 4, true, true>(ctx, q, g, G, n_tiles); break;
+                        case 9: tiles_fused_ols<EmuCtx, 9, 5, true>(ctx, p, g, G, n_tiles); break;
+                        case 11: tiles_fused_ols<EmuCtx, 11, 6, true>(ctx, p, g, G, n_tiles); break;
+                        case 13: tiles_fused_ols<EmuCtx, 13, 7, true>(ctx, p, g, G, n_tiles); break;
+                        case 10: if (variant != 5) { tiles_fused_ols<EmuCtx, 10, 5, true>(ctx, p, g, G, n_tiles); break; }
+                                 tiles_fused_ols<EmuCtx, 10, 4, true>(ctx, p, g, G, n_tiles); ctx.barrier(); tiles_fused_ols<EmuCtx, 10, 1, true, true>(ctx, q, g, G, n_tiles); break;
+                        case 14: if (variant != 5) { tiles_fused_ols<EmuCtx, 14, 7, true>(ctx, p, g, G, n_tiles); break; }
+                                 tiles_fused_ols<EmuCtx, 14, 4, true>(ctx, p, g, G, n_tiles); ctx.barrier(); tiles_fused_ols<EmuCtx, 14, 3, true, true>(ctx, q, g, G, n_tiles); break;
+                        case 12: if (variant != 5) { tiles_fused_ols<EmuCtx, 12, 6, true>(ctx, p, g, G, n_tiles); break; }
+                                 tiles_fused_ols<EmuCtx, 12, 4, true>(ctx, p, g, G, n_tiles); ctx.barrier(); tiles_fused_ols<EmuCtx, 12, 2, true, true>(ctx, q, g, G, n_tiles); break;
+                        default: tiles_fused_ols<EmuCtx, 16, 4, true>(ctx, p, g, G, n_tiles); ctx.barrier(); tiles_fused_ols<EmuCtx, 16, 4, true, true>(ctx, q, g, G, n_tiles); break;
                     }
-                });
-            for (auto &x : th) x.join();
+                } else if (p.n_pairs > 4 && p.n_pairs <= 8 && (variant == 1 || variant == 5)) {      // launch_gen's two passes for 9-16 channels
+                    TileParams q = p;
+                    q.in = p.in + 8; q.hist = p.hist + 8; q.tab = p.tab + 4 * (long long)kN; q.ch_base = 8;
+                    tiles_fused_ols<EmuCtx, 0, 4, false>(ctx, p, g, G, n_tiles);
+                    ctx.barrier();
+                    switch (p.n_pairs - 4) {
+                        case 1: tiles_fused_ols<EmuCtx, 0, 1, false, true>(ctx, q, g, G, n_tiles); break;
+                        case 2: tiles_fused_ols<EmuCtx, 0, 2, false, true>(ctx, q, g, G, n_tiles); break;
+                        case 3: tiles_fused_ols<EmuCtx, 0, 3, false, true>(ctx, q, g, G, n_tiles); break;
+                        default: tiles_fused_ols<EmuCtx, 0, 4, false, true>(ctx, q, g, G, n_tiles); break;
+                    }
+                } else {
+                    switch (p.n_pairs <= 4 && (variant == 1 || variant == 5) ? p.n_pairs : 0) {
+                        case 1: tiles_fused_ols<EmuCtx, 0, 1, false>(ctx, p, g, G, n_tiles); break;
+                        case 2: tiles_fused_ols<EmuCtx, 0, 2, false>(ctx, p, g, G, n_tiles); break;
+                        case 3: tiles_fused_ols<EmuCtx, 0, 3, false>(ctx, p, g, G, n_tiles); break;
+                        case 4: tiles_fused_ols<EmuCtx, 0, 4, false>(ctx, p, g, G, n_tiles); break;
+                        default: tiles_fused_ols<EmuCtx, 0, 0, false>(ctx, p, g, G, n_tiles); break;
+                    }
+                }
+            });
         }
     };
     run(true, (long long)n_streams * (hi - lo));
@@ -187,18 +179,14 @@ int emu_fused_ola(const float *in, float *out, const float *hist, const float *t
     int rc = 0;
     for (long long g = 0; g < G; ++g) {
         const long long first = n_tiles * g / G, end = n_tiles * (g + 1) / G;
-        std::vector<std::thread> th;
-        th.reserve(kThreads);
-        for (int t = 0; t < kThreads; ++t)
-            th.emplace_back([&, t]() {
-                EmuCtx ctx{t, &sh};
+        emu_workgroup(kThreads, [&](int t) {
+            EmuCtx ctx{t, &sh};
 #define AW_OLA_CASE(CS, HH) if (n_channels == CS && H == HH) { tiles_fused_ola<EmuCtx, CS, (CS + 1) / 2, HH>(ctx, p, first, end); return; }
-                AW_OLA_CASE(2, 7) AW_OLA_CASE(2, 8) AW_OLA_CASE(7, 7) AW_OLA_CASE(7, 8) AW_OLA_CASE(8, 7) AW_OLA_CASE(8, 8) AW_OLA_CASE(8, 5) AW_OLA_CASE(8, 6)
-                AW_OLA_CASE(14, 7) AW_OLA_CASE(14, 8) AW_OLA_CASE(14, 6) AW_OLA_CASE(16, 7) AW_OLA_CASE(5, 4) AW_OLA_CASE(12, 7) AW_OLA_CASE(6, 7) AW_OLA_CASE(13, 7) AW_OLA_CASE(9, 8)
+            AW_OLA_CASE(2, 7) AW_OLA_CASE(2, 8) AW_OLA_CASE(7, 7) AW_OLA_CASE(7, 8) AW_OLA_CASE(8, 7) AW_OLA_CASE(8, 8) AW_OLA_CASE(8, 5) AW_OLA_CASE(8, 6)
+            AW_OLA_CASE(14, 7) AW_OLA_CASE(14, 8) AW_OLA_CASE(14, 6) AW_OLA_CASE(16, 7) AW_OLA_CASE(5, 4) AW_OLA_CASE(12, 7) AW_OLA_CASE(6, 7) AW_OLA_CASE(13, 7) AW_OLA_CASE(9, 8)
 #undef AW_OLA_CASE
-                if (t == 0) rc = -2;
-            });
-        for (auto &x : th) x.join();
+            if (t == 0) rc = -2;
+        });
     }
     return rc;
 }
@@ -232,12 +220,7 @@ int emu_partitioned(const float *in, float *out, const float *hist, const float 
     EmuShared sh;
     auto run = [&](auto fn, int count) {
         for (int s = 0; s < n_streams; ++s)
-            for (int i = 0; i < count; ++i) {
-                std::vector<std::thread> th;
-                th.reserve(kThreads);
-                for (int t = 0; t < kThreads; ++t) th.emplace_back([&, t]() { EmuCtx ctx{t, &sh}; fn(ctx, s, i); });
-                for (auto &x : th) x.join();
-            }
+            for (int i = 0; i < count; ++i) emu_workgroup(kThreads, [&](int t) { EmuCtx ctx{t, &sh}; fn(ctx, s, i); });
     };
     {   // interior / head / generic split of awk::launch_part_forward (vector variants are emulated for 5, 7 and 8 channels here)
         const long long usable = frames - ((n_channels % 4 != 0 && n_channels != 2) ? 1 : 0);
@@ -369,20 +352,13 @@ int emu_eq_process(const float *in, float *out, double *z, int n_streams, long l
     if (body > 0) {
         p.frames = body;
         EmuShared sh(kEqThreads, (size_t)kEqLdsBytes / sizeof(cf));
-        for (int s = 0; s < n_streams; ++s) {
-            std::vector<std::thread> th;
-            th.reserve(kEqThreads);
-            for (int ear = 0; ear < (ear_split ? 2 : 1); ++ear) {        // E = 1: one emulated workgroup per (stream, ear)
-                th.clear();
-                for (int t = 0; t < kEqThreads; ++t)
-                    th.emplace_back([&, t]() {
-                        EmuCtx ctx{t, &sh};
-                        if (ear_split) eq_cascade_stream<EmuCtx, 1>(ctx, p, s, ear);
-                        else eq_cascade_stream<EmuCtx, 2>(ctx, p, s, 0);
-                    });
-                for (auto &x : th) x.join();
-            }
-        }
+        for (int s = 0; s < n_streams; ++s)
+            for (int ear = 0; ear < (ear_split ? 2 : 1); ++ear)          // E = 1: one emulated workgroup per (stream, ear)
+                emu_workgroup(kEqThreads, [&](int t) {
+                    EmuCtx ctx{t, &sh};
+                    if (ear_split) eq_cascade_stream<EmuCtx, 1>(ctx, p, s, ear);
+                    else eq_cascade_stream<EmuCtx, 2>(ctx, p, s, 0);
+                });
     }
     if (frames > body) {
         p.in = in + body * 2; p.out = out + body * 2; p.frames = frames - body;
@@ -405,26 +381,23 @@ int emu_sub_fft512h(const float *rows, float *fwd, float *back) {
     const int wave = 3;                                    // rows 3 and 13 of the exchange buffer
     for (int s = 0; s < 2; ++s)
         for (int k = 0; k < kSub; ++k) buf[wave_row(wave, s) * kRowStride + k] = mk(rows[(s * kSub + k) * 2], rows[(s * kSub + k) * 2 + 1]);
-    std::vector<std::thread> th;
-    for (int lane = 0; lane < 64; ++lane)
-        th.emplace_back([&, lane] {
-            EmuCtx ctx{wave * 64 + lane, &sh};
-            const HLane L = hl_make(ctx, buf, twh, lane, wave);
-            cf z[16];
-            for (int j = 0; j < 16; ++j) z[j] = ctx.ld(L.row + L.h + 32 * j);
-            sub_fft512h_fwd(ctx, z, L);
-            const int s = lane >> 5;
-            for (int kb = 0; kb < 16; ++kb) {
-                const int k = L.col + 32 * kb;
-                fwd[(s * kSub + k) * 2] = z[kb].x; fwd[(s * kSub + k) * 2 + 1] = z[kb].y;
-            }
-            sub_fft512h_inv(ctx, z, L);
-            for (int j = 0; j < 16; ++j) {
-                const int n = L.h + 32 * j;
-                back[(s * kSub + n) * 2] = z[j].x; back[(s * kSub + n) * 2 + 1] = z[j].y;
-            }
-        });
-    for (auto &t : th) t.join();
+    emu_workgroup(64, [&](int lane) {                      // one wave of the workgroup
+        EmuCtx ctx{wave * 64 + lane, &sh};
+        const HLane L = hl_make(ctx, buf, twh, lane, wave);
+        cf z[16];
+        for (int j = 0; j < 16; ++j) z[j] = ctx.ld(L.row + L.h + 32 * j);
+        sub_fft512h_fwd(ctx, z, L);
+        const int s = lane >> 5;
+        for (int kb = 0; kb < 16; ++kb) {
+            const int k = L.col + 32 * kb;
+            fwd[(s * kSub + k) * 2] = z[kb].x; fwd[(s * kSub + k) * 2 + 1] = z[kb].y;
+        }
+        sub_fft512h_inv(ctx, z, L);
+        for (int j = 0; j < 16; ++j) {
+            const int n = L.h + 32 * j;
+            back[(s * kSub + n) * 2] = z[j].x; back[(s * kSub + n) * 2 + 1] = z[j].y;
+        }
+    });
     return 0;
 }
 

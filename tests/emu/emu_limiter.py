@@ -1,16 +1,13 @@
 """TEST-ONLY: ctypes access to the thread-emulated limiter kernel and the sequential rule (tests/emu/emu_limiter.cpp)."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
+import _build
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
 _LIB = os.path.join(_HERE, "libemu_limiter.so")
-_SRCS = [os.path.join(_HERE, "emu_limiter.cpp")]
-_DEPS = _SRCS + [os.path.join(_ROOT, "airwave_amd/csrc/device", f)
-                 for f in ("limiter.hpp", "limiter_tile.hpp", "truepeak.hpp", "levels.hpp", "pcm.hpp")]
 _lib = None
 V = ctypes.c_void_p
 ONE_BITS = 0x3F800000
@@ -19,9 +16,7 @@ ONE_BITS = 0x3F800000
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(d) for d in _DEPS):
-            subprocess.run(["g++", "-std=c++20", "-O2", "-pthread", "-fPIC", "-shared"] + _SRCS + ["-o", _LIB], check=True)
-        _lib = ctypes.CDLL(_LIB)
+        _lib = _build.load(_LIB, [(os.path.join(_HERE, "emu_limiter.cpp"), [])], link_flags=["-pthread"])
         i, ll, f = ctypes.c_int, ctypes.c_longlong, ctypes.c_float
         _lib.emu_limiter.argtypes = [V, V, i, ll, V, i, i, f, V, V, V, V, V]
         _lib.emu_limiter_sequential.argtypes = [V, V, i, ll, V, i, i, f, V, V, V, V, V, V]

@@ -28,16 +28,8 @@ long long emu_loudness(const float *in, int n_streams, long long frames, double 
     if (body > 0) {
         p.frames = body;
         EmuShared sh(kEqThreads, (size_t)(kLdLdsBytes + sizeof(cf) - 1) / sizeof(cf));
-        for (int s = 0; s < n_streams; ++s) {
-            std::vector<std::thread> th;
-            th.reserve(kEqThreads);
-            for (int t = 0; t < kEqThreads; ++t)
-                th.emplace_back([&, t]() {
-                    EmuCtx ctx{t, &sh};
-                    loudness_stream<EmuCtx>(ctx, p, s);
-                });
-            for (auto &x : th) x.join();
-        }
+        for (int s = 0; s < n_streams; ++s)
+            emu_workgroup(kEqThreads, [&](int t) { EmuCtx ctx{t, &sh}; loudness_stream(ctx, p, s); });
     }
     if (frames > body) {
         p.in = in + body * 2; p.frames = frames - body; p.frame0 = frame0 + body;

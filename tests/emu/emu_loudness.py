@@ -1,16 +1,15 @@
 """TEST-ONLY: ctypes access to the thread-emulated loudness kernels (tests/emu/emu_loudness.cpp)."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
+
+import _build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
 _LIB = os.path.join(_HERE, "libemu_loudness.so")
-_SRCS = [os.path.join(_HERE, "emu_loudness.cpp"), os.path.join(_ROOT, "airwave_amd/csrc/host/eq.cpp")]
-_DEPS = _SRCS + [os.path.join(_HERE, "emu_ctx.hpp"), os.path.join(_ROOT, "airwave_amd/csrc/host/eq.hpp")] + [
-    os.path.join(_ROOT, "airwave_amd/csrc/device", f) for f in ("loudness.hpp", "loudness_scan.hpp", "eq_cascade.hpp", "cplx.hpp", "pcm.hpp")]
+_UNITS = [(os.path.join(_HERE, "emu_loudness.cpp"), []), (os.path.join(_ROOT, "airwave_amd/csrc/host/eq.cpp"), [])]
 _lib = None
 dp = ctypes.POINTER(ctypes.c_double)
 
@@ -18,9 +17,7 @@ dp = ctypes.POINTER(ctypes.c_double)
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(d) for d in _DEPS):
-            subprocess.run(["g++", "-std=c++20", "-O2", "-pthread", "-fPIC", "-shared"] + _SRCS + ["-o", _LIB], check=True)
-        _lib = ctypes.CDLL(_LIB)
+        _lib = _build.load(_LIB, _UNITS, link_flags=["-pthread"])
         _lib.emu_loudness.restype = ctypes.c_longlong
         _lib.emu_loudness.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, ctypes.c_longlong, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]

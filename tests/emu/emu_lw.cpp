@@ -19,10 +19,7 @@ template <int RA> void emu_lw_split_or_merge(const awk::LwParams &p, long long n
     using namespace awk;
     EmuShared sh;
     auto run = [&](auto fn) {            // one emulated persistent workgroup walks every tile
-        std::vector<std::thread> th;
-        th.reserve(kThreads);
-        for (int t = 0; t < kThreads; ++t) th.emplace_back([&, t]() { EmuCtx ctx{t, &sh}; fn(ctx); });
-        for (auto &x : th) x.join();
+        emu_workgroup(kThreads, [&](int t) { EmuCtx ctx{t, &sh}; fn(ctx); });
     };
     const long long n_st = n_sw * kLwChunks;
     const int n_channels = p.n_channels;
@@ -94,10 +91,7 @@ int emu_longwin(const float *in, float *out, const float *hist, const float *tra
     p.twa = tw.twa.data(); p.twb = tw.twb.data();
     EmuShared sh;
     auto run = [&](auto fn) {            // one emulated persistent workgroup walks every tile
-        std::vector<std::thread> th;
-        th.reserve(kThreads);
-        for (int t = 0; t < kThreads; ++t) th.emplace_back([&, t]() { EmuCtx ctx{t, &sh}; fn(ctx); });
-        for (auto &x : th) x.join();
+        emu_workgroup(kThreads, [&](int t) { EmuCtx ctx{t, &sh}; fn(ctx); });
     };
     const long long n_st = n_sw * kLwChunks;
     std::vector<float> tail(32, 0.f);
@@ -129,23 +123,19 @@ int emu_longwin(const float *in, float *out, const float *hist, const float *tra
     };
     if (form16) {
         EmuShared sh16(kR16Threads, (size_t)kR16LdsElems);
-        std::vector<std::thread> th;
-        th.reserve(kR16Threads);
-        for (int t = 0; t < kR16Threads; ++t)
-            th.emplace_back([&, t]() {
-                EmuCtx ctx{t, &sh16};
-                auto go = [&](auto NPP, auto REAL) {
-                    lw_rows16_tiles<EmuCtx, decltype(NPP)::value, (decltype(REAL)::value != 0)>(ctx, p, 0, 1, n_sw, 0, 1);
-                };
-                auto go_np = [&](auto REAL) {
-                    switch (p.n_pairs) {
-                        case 1: go(LwIdx<1>{}, REAL); break; case 2: go(LwIdx<2>{}, REAL); break; case 3: go(LwIdx<3>{}, REAL); break; case 4: go(LwIdx<4>{}, REAL); break;
-                        case 5: go(LwIdx<5>{}, REAL); break; case 6: go(LwIdx<6>{}, REAL); break; case 7: go(LwIdx<7>{}, REAL); break; default: go(LwIdx<8>{}, REAL); break;
-                    }
-                };
-                if (p.real_last) go_np(LwIdx<1>{}); else go_np(LwIdx<0>{});
-            });
-        for (auto &x : th) x.join();
+        emu_workgroup(kR16Threads, [&](int t) {
+            EmuCtx ctx{t, &sh16};
+            auto go = [&](auto NPP, auto REAL) {
+                lw_rows16_tiles<EmuCtx, decltype(NPP)::value, (decltype(REAL)::value != 0)>(ctx, p, 0, 1, n_sw, 0, 1);
+            };
+            auto go_np = [&](auto REAL) {
+                switch (p.n_pairs) {
+                    case 1: go(LwIdx<1>{}, REAL); break; case 2: go(LwIdx<2>{}, REAL); break; case 3: go(LwIdx<3>{}, REAL); break; case 4: go(LwIdx<4>{}, REAL); break;
+                    case 5: go(LwIdx<5>{}, REAL); break; case 6: go(LwIdx<6>{}, REAL); break; case 7: go(LwIdx<7>{}, REAL); break; default: go(LwIdx<8>{}, REAL); break;
+                }
+            };
+            if (p.real_last) go_np(LwIdx<1>{}); else go_np(LwIdx<0>{});
+        });
     } else if (rows_pb == 1) rows(LwIdx<1>{}); else rows(LwIdx<2>{});
     with_ra([&](auto RA) { emu_lw_split_or_merge<decltype(RA)::value>(p, n_sw, true); });
     (void)n_st;

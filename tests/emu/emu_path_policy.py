@@ -3,15 +3,11 @@ airwave_amd/csrc/host/path_policy.hpp), built with plain g++ like the library's 
 -march=native), so that the cost comparisons run in the library's arithmetic."""
 import ctypes
 import os
-import subprocess
+
+import _build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
 _LIB = os.path.join(_HERE, "libemu_path_policy.so")
-_SRCS = [os.path.join(_HERE, "emu_path_policy.cpp")]
-_CSRC = os.path.join(_ROOT, "airwave_amd", "csrc")
-_DEPS = _SRCS + [os.path.join(_CSRC, "host", f) for f in ("path_policy.hpp", "tables.hpp")] + \
-    [os.path.join(_CSRC, "device", f) for f in ("ola_layouts.hpp", "tile_ola.hpp", "tile_ols.hpp", "tile_ols2.hpp", "tile_lw.hpp", "tile_lw16.hpp", "cplx.hpp")]
 _lib = None
 
 ENV_KNOBS = ("AW_WINDOW", "AW_OLA", "AW_LW")
@@ -21,9 +17,7 @@ PLAN_FIELDS = ("path", "fused2", "hop", "hist_len", "partitions", "n_pairs", "ol
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(d) for d in _DEPS):
-            subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=fast", "-fPIC", "-shared"] + _SRCS + ["-o", _LIB], check=True)
-        _lib = ctypes.CDLL(_LIB)
+        _lib = _build.load(_LIB, [(os.path.join(_HERE, "emu_path_policy.cpp"), [])], compile_flags=("-std=c++17", "-O2", "-ffp-contract=fast"))
         i, ll, p = ctypes.c_int, ctypes.c_longlong, ctypes.POINTER(ctypes.c_int)
         _lib.pp_plan_create.argtypes = [i, i, i, p, p]
         _lib.pp_use_ola_tile.argtypes = [p, i, i, i, ll, i, i]

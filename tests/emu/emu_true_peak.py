@@ -1,15 +1,13 @@
 """TEST-ONLY: ctypes access to the thread-emulated true-peak kernel (tests/emu/emu_true_peak.cpp)."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
+import _build
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(os.path.dirname(_HERE))
 _LIB = os.path.join(_HERE, "libemu_true_peak.so")
-_SRCS = [os.path.join(_HERE, "emu_true_peak.cpp")]
-_DEPS = _SRCS + [os.path.join(_ROOT, "airwave_amd/csrc/device", f) for f in ("truepeak.hpp", "truepeak_tile.hpp", "pcm.hpp")]
 _lib = None
 V = ctypes.c_void_p
 
@@ -17,9 +15,7 @@ V = ctypes.c_void_p
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(d) for d in _DEPS):
-            subprocess.run(["g++", "-std=c++20", "-O2", "-pthread", "-fPIC", "-shared"] + _SRCS + ["-o", _LIB], check=True)
-        _lib = ctypes.CDLL(_LIB)
+        _lib = _build.load(_LIB, [(os.path.join(_HERE, "emu_true_peak.cpp"), [])], link_flags=["-pthread"])
         _lib.emu_true_peak.argtypes = [V, ctypes.c_int, ctypes.c_longlong, V, V, V, V, V]
         _lib.emu_true_peak_sequential.argtypes = [V, ctypes.c_int, ctypes.c_longlong, V, V, V, V]
         _lib.emu_true_peak_filter.argtypes = [V]
