@@ -95,7 +95,9 @@ struct CreatePlan {
 };
 
 // Tiles start on 64-frame boundaries of the timeline: a shorter hop costs < 2 % more tiles and makes every tile's
-// loads and stores start line-aligned (measured cfg 2: 1.555 -> 1.530 ms per call).  hop_align 1 = off.
+// loads and stores start line-aligned (measured cfg 2: 1.555 -> 1.530 ms per call).  hop_align is AW_HOP_ALIGN's atoi, unchecked: below 2
+// it is off, and so is a value the hop is not sixteen times as long as.  The 8192-frame and the overlap-add tile run any hop; the 16384-frame
+// tile needs an even one (plan_create).
 constexpr int align_hop(int hop_align, int hop) { return (hop_align > 1 && hop > 16 * hop_align) ? hop - hop % hop_align : hop; }
 
 // Overlap-add tile or overlap-save tile for a path-0 spatializer on 8192-frame windows?  Block rows H (0: overlap-save).  `rows_carried`:
@@ -138,6 +140,7 @@ inline CreatePlan plan_create(const Layout &l, const Knobs &k, int ola_rows_carr
     if (!force_partitioned && ((window == awk::kN2 && fits2) || (!fits1 && fused2_ok))) {
         p.path = 0; p.fused2 = true;
         p.hop = align_hop(k.hop_align, awk::kN2 - hist2);
+        p.hop -= p.hop & 1;                                          // an odd AW_HOP_ALIGN: the tile stores frames in pairs from an even window position on (tile_ols2.hpp: first_valid is even), an odd history would drop the first new frame of every tile
         p.hist_len = awk::kN2 - p.hop;                               // even, >= 2 * floor(taps / 2)
         p.n_pairs = (2 * C + 1) / 2;                                 // pseudo-pairs of the half-rate 2C-channel view
     } else if (fits1 && !force_partitioned) {

@@ -123,7 +123,11 @@ AW_API double aw_hrir_sample_rate(const aw_hrir *h);
  * its two-renderer cap:  out_L = sum_c x_c * h[left_track[c]],  out_R = sum_c x_c * h[right_track[c]].
  * A channel with left_track[c] < 0 or right_track[c] < 0 is skipped (HRIRManager.swift:370-372);
  * an index >= n_tracks is AW_ERR_INVALID_CHANNEL_MAPPING (:375-379); no mapped channel at all is
- * AW_ERR_CONVOLUTION_SETUP_FAILED (:420-422).  block_hint: 0 = automatic (results do not depend on it). */
+ * AW_ERR_CONVOLUTION_SETUP_FAILED (:420-422).  block_hint: 0 = automatic (results do not depend on it).
+ * Any n_in_channels > 0 and any HRIR length are accepted.  Tested on the GPU: 1 - 18, 24 and 32 channels (up to 16 on every
+ * kernel path; beyond 16 there is no overlap-add tile and no long-window kernel, AW_OLA / AW_LW are ignored there and every call
+ * runs the run-time-loop kernels of the fused or the partitioned path), HRIRs of up to 98 305 taps on the partitioned path and
+ * up to 131 072 on the long-window kernels (tests/test_gpu_wide_layouts.py, tests/test_gpu_long_hrir.py). */
 typedef struct aw_spatializer aw_spatializer;
 AW_API aw_status aw_spatializer_create(aw_context *ctx, const aw_hrir *hrir, int32_t n_in_channels,
                                        const int32_t *left_track, const int32_t *right_track,

@@ -43,19 +43,20 @@ def lib():
 
 
 def fused_ols(x, tracks, left_track, right_track, hop=None, hist=None, variant=1):
-    """x: [streams][frames][C] float32 -> [streams][frames][2]."""
+    """x: [streams][frames][C] float32 -> [streams][frames][2].  hop: of the 8192-frame tile, or (variant 2) of the 16384-frame tile;
+    None: the longest the HRIR allows."""
     x = np.ascontiguousarray(x, dtype=np.float32)
     S, F, C = x.shape
     tr = np.ascontiguousarray(tracks, dtype=np.float32)
     lt = np.ascontiguousarray(left_track, dtype=np.int32)
     rt = np.ascontiguousarray(right_track, dtype=np.int32)
     if hop is None:
-        hop = 8192 - (tr.shape[1] - 1)
+        hop = 8192 - (tr.shape[1] - 1) if variant != 2 else 16384 - 2 * (tr.shape[1] // 2)
     out = np.full((S, F, 2), np.nan, dtype=np.float32)
     h = None
     if hist is not None:
         h = np.ascontiguousarray(hist, dtype=np.float32)
-        assert h.shape == ((S, 8192 - hop, C) if variant != 2 else (S, 2 * (tr.shape[1] // 2), C))
+        assert h.shape == (S, (8192 if variant != 2 else 16384) - hop, C)
     rc = lib().emu_fused_ols(x.ctypes.data_as(fp), out.ctypes.data_as(fp), None if h is None else h.ctypes.data_as(fp),
                              tr.ctypes.data_as(fp), tr.shape[0], tr.shape[1], C, lt.ctypes.data_as(ip),
                              rt.ctypes.data_as(ip), F, S, hop, variant)

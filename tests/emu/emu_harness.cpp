@@ -5,10 +5,11 @@ extern "C" {
 
 // Builds tables + twiddles on the host and runs every tile of every stream through the emulated
 // workgroup.  Layouts as TileParams.  hist may be NULL (zeros).
-// The 16384-frame window path (tile_ols2.hpp): hop and history follow from the taps; hist is [stream][hist][C].
+// The 16384-frame window path (tile_ols2.hpp): hop <= 0: hop and history follow from the taps, else the history is the window minus that
+// hop (an aligned hop, path_policy.hpp); hist is [stream][hist][C].
 static int emu_fused_ols2(const float *in, float *out, const float *hist, const float *tracks, int n_tracks, int taps,
                           int n_channels, const int32_t *left_track, const int32_t *right_track, long long frames,
-                          int n_streams) {
+                          int n_streams, int hop) {
     using namespace awk;
     awh::Twiddles tw;
     awh::build_twiddles(tw);
@@ -20,6 +21,10 @@ static int emu_fused_ols2(const float *in, float *out, const float *hist, const 
     p.tw1 = tw.tw1.data(); p.twa = tw.twa.data(); p.twb = tw.twb.data(); p.zeros = g_zeros;
     p.frames = frames; p.n_channels = n_channels; p.n_pairs = (2 * n_channels + 1) / 2;
     p.hist_len = awh::poly_history_frames(taps); p.hop = kN2 - p.hist_len;
+    if (hop > 0) {
+        if (hop > p.hop) return -1;
+        p.hop = hop; p.hist_len = kN2 - hop;
+    }
     p.tiles_per_stream = (int)((frames + p.hop - 1) / p.hop);
     std::vector<float> zero_hist;
     if (!hist) { zero_hist.assign((size_t)n_streams * p.hist_len * n_channels + 4, 0.f); hist = zero_hist.data(); }
@@ -63,7 +68,7 @@ int emu_fused_ols(const float *in, float *out, const float *hist, const float *t
                   int taps, int n_channels, const int32_t *left_track, const int32_t *right_track,
                   long long frames, int n_streams, int hop, int variant) {
     using namespace awk;
-    if (variant == 2) return emu_fused_ols2(in, out, hist, tracks, n_tracks, taps, n_channels, left_track, right_track, frames, n_streams);
+    if (variant == 2) return emu_fused_ols2(in, out, hist, tracks, n_tracks, taps, n_channels, left_track, right_track, frames, n_streams, hop);
     if (hop <= 0 || hop > kN - (taps - 1)) return -1;
     awh::Twiddles tw;
     std::vector<cf2> tab;

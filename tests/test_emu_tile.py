@@ -143,3 +143,95 @@ def test_half_wave_row_transform_against_numpy():
     k = np.arange(512)
     assert np.max(np.abs(f2[0] - np.exp(-2j * np.pi * k / 512))) < 1e-6
     assert np.max(np.abs(f2[1] - 1j * np.exp(2j * np.pi * k / 512))) < 1e-6
+
+
+# ---- beyond the grid the GPU suite ran before test_gpu_long_hrir.py / test_gpu_wide_layouts.py / test_gpu_knob_forms.py
+def _end_heavy(oracle, channels, taps, frames):
+    import spectral_cases as sc
+    h, lt, rt, x = sc.end_heavy_input(oracle, channels, taps, 1, frames)
+    return h, lt, rt, x, oracle.spatialize_f64(x[0], h, lt, rt)
+
+
+@pytest.mark.parametrize("taps,channels,cmac", [(49153, 1, "march"), (65536, 2, "march"), (65537, 3, "march"), (49153, 3, "group")])
+def test_emulated_partitioned_passes_beyond_the_second(oracle, taps, channels, cmac):
+    """P = 13: the marched CMAC's first later pass of more than four partitions (PQ = 8, accumulating); P = 16 | 17: two whole passes | a third;
+    the block-group kernel at P = 13.  End-heavy HRIRs on the narrowest layouts; head, interior and ragged-tail blocks."""
+    h, lt, rt, x, ref = _end_heavy(oracle, channels, taps, 9001)
+    y = emu.partitioned(x, h, lt, rt, cmac=cmac)
+    assert not np.isnan(y).any()
+    assert oracle.peak_rel_error(y[0], ref) < TOL
+
+
+def test_emulated_long_window_carries_a_sixteen_partition_history(oracle):
+    """R = 32 with 65 536 frames of history in and out (hop = N / 2), two windows."""
+    taps, R, C = 65536, 32, 2
+    hist_len = 65536
+    hop = R * 4096 - hist_len
+    frames = hop + 5000
+    import spectral_cases as sc
+    h, lt, rt, x = sc.end_heavy_input(oracle, C, taps, 1, hist_len + frames)
+    ref = oracle.spatialize_f64(x[0], h, lt, rt)
+    hist = x[:, :hist_len].copy()
+    hist_out = np.full((1, hist_len, C), np.nan, dtype=np.float32)
+    y = emu.longwin(x[:, hist_len:], h, lt, rt, R=R, hop=hop, hist=hist, hist_out=hist_out, rows_pb=16)
+    assert not np.isnan(y).any()
+    assert np.array_equal(hist_out, x[:, -hist_len:])
+    for ear in range(2):
+        assert oracle.peak_rel_error(y[0, :, ear], ref[hist_len:, ear]) < TOL
+
+
+@pytest.mark.parametrize("channels", [17, 24])
+@pytest.mark.parametrize("kernel", ["ols8192", "ols16384", "part-group"])
+def test_emulated_layouts_of_more_than_sixteen_channels(oracle, channels, kernel):
+    """The run-time-loop kernels every wider layout falls back to: <0, 0, false> of the 8192- and of the 16384-frame tile (9 / 12 pairs, 17 / 24
+    pseudo-pairs) and the partitioned path with the block-group CMAC (the marched kernel's lane groups hold eight pairs)."""
+    import spectral_ref as sr
+    taps, frames = (9000, 9001) if kernel == "part-group" else (4320, 16500)
+    h = oracle.synth_hrir(14, taps, seed=taps)
+    lt, rt = sr.maps(channels)
+    x = oracle.synth_input(1, frames, channels, seed=channels)
+    if kernel == "part-group":
+        y = emu.partitioned(x, h, lt, rt, cmac="group")
+    else:
+        y = emu.fused_ols(x, h, lt, rt, variant=1 if kernel == "ols8192" else 2)
+    assert not np.isnan(y).any()
+    assert oracle.peak_rel_error(y[0], oracle.spatialize_f64(x[0], h, lt, rt)) < TOL
+
+
+@pytest.mark.parametrize("channels", [2, 7])
+@pytest.mark.parametrize("hop", [3873, 3872, 3871, 3840, 3800])
+def test_emulated_8192_tile_at_any_hop(oracle, channels, hop):
+    """AW_HOP_ALIGN: the 8192-frame tile needs hop <= 8193 - taps and nothing else — odd hops, hops that are no multiple of 64 or of 4 (frame loads
+    are dword-aligned 16-byte or naturally aligned 8-byte loads at every frame, stores 8 bytes per frame)."""
+    h = oracle.synth_hrir(14, 4320, seed=3)
+    lt = (np.arange(channels) % 14).astype(np.int32)
+    rt = ((np.arange(channels) + 7) % 14).astype(np.int32)
+    x = oracle.synth_input(1, 20011, channels, seed=channels)
+    y = emu.fused_ols(x, h, lt, rt, hop=hop)
+    assert not np.isnan(y).any()
+    assert oracle.peak_rel_error(y[0], oracle.spatialize_f64(x[0], h, lt, rt)) < TOL
+
+
+@pytest.mark.parametrize("channels", [2, 7])
+@pytest.mark.parametrize("hop", [12064, 12062, 12000, 11990])
+def test_emulated_16384_tile_at_even_hops(oracle, channels, hop):
+    """The 16384-frame tile at hops below the longest: any EVEN hop (plan_create rounds an odd one down, next test)."""
+    h = oracle.synth_hrir(14, 4320, seed=3)
+    lt = (np.arange(channels) % 14).astype(np.int32)
+    rt = ((np.arange(channels) + 7) % 14).astype(np.int32)
+    x = oracle.synth_input(1, 30011, channels, seed=channels)
+    y = emu.fused_ols(x, h, lt, rt, hop=hop, variant=2)
+    assert not np.isnan(y).any()
+    assert oracle.peak_rel_error(y[0], oracle.spatialize_f64(x[0], h, lt, rt)) < TOL
+
+
+def test_emulated_16384_tile_needs_an_even_history(oracle):
+    """Why plan_create keeps the 16384-frame tile's hop even: the tile stores frames in pairs from an even window position on (tile_ols2.hpp,
+    tile_inverse_final2), so with an odd history (window minus an odd hop) the first new frame of every tile is never written — here the frames
+    that stay at the output's NaN fill are exactly the multiples of the hop."""
+    hop = 12063
+    h = oracle.synth_hrir(14, 4320, seed=3)
+    x = oracle.synth_input(1, 30011, 2, seed=2)
+    y = emu.fused_ols(x, h, [0, 1], [1, 0], hop=hop, variant=2)
+    missing = np.flatnonzero(np.isnan(y[0]).any(axis=1))
+    assert list(missing) == [0, hop, 2 * hop]

@@ -55,6 +55,32 @@ def test_response_lengths_of_the_bundled_presets(golden_dir):
         assert 1.8 * a < b < 2.2 * a
 
 
+# (preamp dB, (type, Hz, gain dB, Q)): a bell at 20 Hz that rings for about 1.1 s — the longest kind of response the default 65 536-tap limit lets fold
+LONG_FOLD = (-1.0, (0, 20.0, 6.0, 3.0))
+
+
+def test_a_low_bell_folds_into_an_hrir_of_fifteen_partitions(oracle, golden_dir):
+    """The fold that test_gpu_long_hrir.py runs end to end: 53 029 frames of response at 48 kHz, so StageSH1.0 (4320 taps) comes out at 57 348
+    taps — between 49 153 and 65 536, fifteen 4096-frame partitions — with the tail within the tolerance; the response length is the smallest such."""
+    d = aw.EqualizerDefinition(LONG_FOLD[0], [aw.EqualizerFilter(1, 1, True, *LONG_FOLD[1])])
+    w = oracle.wav_load(os.path.join(golden_dir, "hrtf", "StageSH1.0.wav"))
+    f = aw.fold_equalizer(np.asarray(w.audio_data), d, 48000.0)
+    assert f.responseTaps == 53029 and 0.0 <= f.tailBound <= 1e-7
+    assert f.tracks.shape == (w.channel_count, 4320 + f.responseTaps - 1) and 49153 <= f.tracks.shape[1] <= 65536
+    assert -(-f.tracks.shape[1] // 4096) == 15
+    imp = np.zeros(1 << 17, np.float32)
+    imp[0] = 1.0
+    od = oracle.EqualizerDefinition(LONG_FOLD[0], [oracle.EqualizerFilter(1, 1, True, *LONG_FOLD[1])])
+    g, _ = oracle.eq_prepare(od, 48000.0).process(imp, imp.copy())
+    a = np.abs(g.astype(np.float64))
+    tail = np.cumsum(a[::-1])[::-1]
+    assert tail[f.responseTaps] <= 1.01e-7 * a.max() + 1e-12 and tail[f.responseTaps - 2] > 0.9e-7 * a.max()
+    x = np.zeros(f.tracks.shape[1], np.float32)
+    x[:4320] = w.audio_data[3]
+    want, _ = oracle.eq_prepare(od, 48000.0).process(x, x.copy())
+    assert np.array_equal(f.tracks[3], want)
+
+
 def test_unity_and_disabled_filters_leave_the_tracks_alone():
     h = np.arange(12, dtype=np.float32).reshape(2, 6) - 5
     f = aw.fold_equalizer(h, None, 48000.0)

@@ -293,8 +293,13 @@ def adef(aw, preamp, filters):
 
 @pytest.mark.parametrize("calls", [[1, 15, 16, 17], [31, 32, 33, 64], [4095, 4096, 4097], [8191, 8192, 8193], [10000, 3, 70000], [8192, 8192]])
 def test_state_batch_matches_oracle_over_ragged_calls(aw, oracle, calls):
+    check_state_batch_over_ragged_calls(aw, oracle, calls)
+
+
+def check_state_batch_over_ragged_calls(aw, oracle, calls, ctx=None):
+    """ctx: a context of another kernel form (test_gpu_knob_forms.py: AW_EQ_EAR_SPLIT=0); None: the default context."""
     S = 5
-    st = aw.ParametricEqualizerState(adef(aw, -2.56, FILTERS), 48000.0, n_streams=S)
+    st = aw.ParametricEqualizerState(adef(aw, -2.56, FILTERS), 48000.0, n_streams=S, ctx=ctx)
     ref = [oracle.eq_prepare(odef(oracle, -2.56, FILTERS), 48000.0) for _ in range(S)]
     rng = np.random.default_rng(sum(calls))
     for n in calls:
@@ -314,12 +319,16 @@ def test_state_batch_matches_oracle_over_ragged_calls(aw, oracle, calls):
 
 
 def test_sixty_four_filters_and_other_rates(aw, oracle):
+    check_sixty_four_filters_and_other_rates(aw, oracle)
+
+
+def check_sixty_four_filters_and_other_rates(aw, oracle, S=2, ctx=None):
     many = [(i % 3, 100.0 + 300.0 * i, ((i % 5) - 2) * 1.5, 0.5 + 0.1 * i) for i in range(64)]
     rng = np.random.default_rng(5)
     for fs in (44100.0, 96000.0):
-        x = rng.uniform(-1, 1, (2, 9000, 2)).astype(np.float32)
-        y = aw.ParametricEqualizerState(adef(aw, -6.0, many), fs, n_streams=2).process_batch(x)
-        for s in range(2):
+        x = rng.uniform(-1, 1, (S, 9000, 2)).astype(np.float32)
+        y = aw.ParametricEqualizerState(adef(aw, -6.0, many), fs, n_streams=S, ctx=ctx).process_batch(x)
+        for s in range(S):
             e = oracle.eq_prepare(odef(oracle, -6.0, many), fs).process(x[s, :, 0], x[s, :, 1])
             assert oracle.peak_rel_error(y[s, :, 0], e[0]) < 1e-6 and oracle.peak_rel_error(y[s, :, 1], e[1]) < 1e-6
 
@@ -327,8 +336,12 @@ def test_sixty_four_filters_and_other_rates(aw, oracle):
 def test_processor_batch_crossfade_matches_oracle(aw, oracle):
     """Targets published between batch calls: fades start at call boundaries, end mid-call, queue and retire
     exactly like the oracle's restatement of ParametricEqualizerProcessor."""
-    S, fs = 3, 48000.0
-    p = aw.ParametricEqualizerProcessor(fs, maxFramesPerCallback=0, n_streams=S)
+    check_processor_batch_crossfade(aw, oracle)
+
+
+def check_processor_batch_crossfade(aw, oracle, S=3, ctx=None):
+    fs = 48000.0
+    p = aw.ParametricEqualizerProcessor(fs, maxFramesPerCallback=0, n_streams=S, ctx=ctx)
     refs = [oracle.ParametricEqualizerProcessor(fs) for _ in range(S)]
     for r in refs:
         r.max_frames = 1 << 30
@@ -396,16 +409,20 @@ def test_low_frequency_cascade_found_by_the_fuzzer(aw, oracle, golden_dir):
     """64 random sections at 96 kHz, a dozen of them below 50 Hz (tools/fuzz_eq.py seed 12, script 2688): with the scan tables
     formed in double the carried state was 1e-7 off at the wave boundaries and the output 4.6 ulp of the peak off; the
     double-double tables (host/eq.cpp) bring it back under one."""
+    check_low_frequency_cascade(aw, oracle, golden_dir)
+
+
+def check_low_frequency_cascade(aw, oracle, golden_dir, S=2, ctx=None):
     import json
     case = json.load(open(os.path.join(golden_dir, "eq", "fuzz_seed12_script2688.json")))
     fl = [tuple(f) for f in case["filters"]]
-    st = aw.ParametricEqualizerState(adef(aw, case["preamp_db"], fl), 96000.0, n_streams=2)
-    ref = [oracle.eq_prepare(odef(oracle, case["preamp_db"], fl), 96000.0) for _ in range(2)]
+    st = aw.ParametricEqualizerState(adef(aw, case["preamp_db"], fl), 96000.0, n_streams=S, ctx=ctx)
+    ref = [oracle.eq_prepare(odef(oracle, case["preamp_db"], fl), 96000.0) for _ in range(S)]
     rng = np.random.default_rng(2688)
     for n in (25229, 22327):
-        x = rng.uniform(-0.5, 0.5, (2, n, 2)).astype(np.float32)
+        x = rng.uniform(-0.5, 0.5, (S, n, 2)).astype(np.float32)
         y = st.process_batch(x)
-        for s in range(2):
+        for s in range(S):
             el, er = ref[s].process(x[s, :, 0], x[s, :, 1])
             scale = max(1.0, float(np.max(np.abs(el))), float(np.max(np.abs(er))))
             assert max(np.max(np.abs(y[s, :, 0] - el)), np.max(np.abs(y[s, :, 1] - er))) <= 2.5 * ULP * scale      # 1.25 x 2^-23; the double-precision tables gave 9 ULP

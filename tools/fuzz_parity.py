@@ -59,7 +59,13 @@ while time.time() < t_end:
             env.pop("AW_WINDOW", None)
             if env.get("AW_LW") not in (None, "0") and rng.random() < 0.7: env.pop("AW_LW")
     elif r5 < 0.55: env["AW_OLA"] = "0"
-    for k in ("AW_WINDOW", "AW_PART_FWD", "AW_PART_CMAC", "AW_PART_HERM", "AW_SPEC_SCRATCH_MB", "AW_LW", "AW_LW_ROWS_PB", "AW_LW_ROWS_FORM", "AW_HOST_CHUNK_MB", "AW_LW_TABLES", "AW_OLA", "AW_OLA_MIN_BLOCKS", "AW_PERSISTENT_WGS"):
+    # the ground of tests/test_gpu_knob_forms.py, test_gpu_long_hrir.py and test_gpu_wide_layouts.py: hops that are odd or no multiple of 64 (any
+    # integer is accepted), the rows kernel's grid, HRIRs on either side of the marched CMAC's passes, layouts of more than 16 channels
+    if rng.random() < 0.25: env["AW_HOP_ALIGN"] = str(int(rng.choice([0, 1, 2, 3, 7, 32, 48, 100, 128, 4096])))
+    if "AW_LW" in env and env["AW_LW"] != "0" and rng.random() < 0.3: env["AW_LW_ROWS16_WGS"] = str(int(rng.choice([1, 2, 4])))
+    if rng.random() < 0.08: taps = int(rng.choice([49152, 49153, 65536, 65537, 69633, 70000]))
+    if rng.random() < 0.08: C = int(rng.choice([17, 18, 24, 32]))
+    for k in ("AW_WINDOW", "AW_PART_FWD", "AW_PART_CMAC", "AW_PART_HERM", "AW_SPEC_SCRATCH_MB", "AW_LW", "AW_LW_ROWS_PB", "AW_LW_ROWS_FORM", "AW_HOST_CHUNK_MB", "AW_LW_TABLES", "AW_OLA", "AW_OLA_MIN_BLOCKS", "AW_PERSISTENT_WGS", "AW_HOP_ALIGN", "AW_LW_ROWS16_WGS"):
         os.environ.pop(k, None)
     os.environ.update(env)
     n_tracks = int(rng.choice([2, 7, 14]))
@@ -75,7 +81,7 @@ while time.time() < t_end:
     if os.environ.get("AW_FUZZ_TRACE"):
         print("CASE", C, taps, S, total, bounds, env, n_tracks, flush=True)
     try:
-        ctx = aw.Context(0) if any(k in env for k in ("AW_LW_ROWS_PB", "AW_LW_ROWS_FORM", "AW_HOST_CHUNK_MB", "AW_LW_TABLES", "AW_OLA_MIN_BLOCKS", "AW_PERSISTENT_WGS")) else None        # (those knobs are read when a context is created)
+        ctx = aw.Context(0) if any(k in env for k in ("AW_LW_ROWS_PB", "AW_LW_ROWS_FORM", "AW_HOST_CHUNK_MB", "AW_LW_TABLES", "AW_OLA_MIN_BLOCKS", "AW_PERSISTENT_WGS", "AW_HOP_ALIGN", "AW_LW_ROWS16_WGS")) else None       # (those knobs are read when a context is created)
         sp = aw.Spatializer(aw.HRIR(h, ctx=ctx), lt, rt, n_streams=S, ctx=ctx) if ctx else aw.Spatializer(aw.HRIR(h), lt, rt, n_streams=S)
         y = np.concatenate([sp.process(x[:, a:b]) for a, b in zip(bounds[:-1], bounds[1:])], axis=1)
         info = sp.info()
