@@ -168,6 +168,13 @@ static aw_status sp_grow(aw_spatializer *sp, T **buf, size_t *cap, size_t need) 
     return AW_OK;
 }
 
+// The record getters' read-back: field f (host/stage_records.hpp) of the n streams from first_stream on, out of the stage's allocation d.
+template <class T> static aw_status get_field(const awst::Field<T> &f, unsigned char *d, int32_t first_stream, int32_t n, std::vector<T> *host) {
+    host->resize((size_t)n * f.per_stream);
+    AW_HIP_TRY(hipMemcpy(host->data(), f.at(d, (size_t)first_stream), host->size() * sizeof(T), hipMemcpyDeviceToHost));
+    return AW_OK;
+}
+
 extern "C" {
 
 const char *aw_version(void) { return "airwave-hip 0.1 (gfx950)"; }
@@ -624,11 +631,9 @@ void aw_spatializer_destroy(aw_spatializer *sp) {
     if (sp->d_pcm_in) (void)hipFree(sp->d_pcm_in);
     if (sp->d_pcm_out) (void)hipFree(sp->d_pcm_out);
     if (sp->d_clip) (void)hipFree(sp->d_clip);
-    if (sp->d_levels) (void)hipFree(sp->d_levels);
-    if (sp->d_loud) (void)hipFree(sp->d_loud);
-    if (sp->d_tp) (void)hipFree(sp->d_tp);
-    if (sp->d_lim) (void)hipFree(sp->d_lim);
-    if (sp->d_lim_y) (void)hipFree(sp->d_lim_y);
+    for (unsigned char *d : {sp->lv.d, sp->ld.d, sp->tp.d, sp->lim.d})      // the output stages' records
+        if (d) (void)hipFree(d);
+    if (sp->lim.d_y) (void)hipFree(sp->lim.d_y);
     if (sp->k0) (void)hipEventDestroy(sp->k0);
     if (sp->k1) (void)hipEventDestroy(sp->k1);
     for (auto &pr : sp->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -651,7 +656,7 @@ int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what) {
         case 7: return sp->last_lw_R;         // long-window path: rows R of the last call's windows (N = R x 4096); 0 = the partitioned kernels ran
         case 8: return sp->last_lw_R2;        // rows of the last call's remainder window when it ran as two groups of windows (0: one group)
         case 9: return (int64_t)sp->lw_plans.size();   // long-window table sets built so far (one per window length; reserve builds those of its plan)
-        case 6: return (int64_t)(sp->ctx->pool_capacity * sizeof(awk::cf) + (sp->stage_in_cap + sp->stage_out_cap + sp->lim_y_cap) * sizeof(float) + sp->pcm_in_cap + sp->pcm_out_cap);   // grow-only device buffers, bytes (the context's scratch pool + this handle's staging)
+        case 6: return (int64_t)(sp->ctx->pool_capacity * sizeof(awk::cf) + (sp->stage_in_cap + sp->stage_out_cap + sp->lim.y_cap) * sizeof(float) + sp->pcm_in_cap + sp->pcm_out_cap);   // grow-only device buffers, bytes (the context's scratch pool + this handle's staging)
         case 10: return sp->reserve_tables_us;    // last aw_spatializer_reserve: float64 table build on host threads, microseconds
         case 11: return sp->reserve_upload_us;    //   table upload (hipMalloc + hipMemcpy)
         case 12: return sp->reserve_scratch_us;   //   scratch pool growth (hipMalloc)
@@ -661,12 +666,12 @@ int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what) {
         case 16: return sp->last_ola_h;           // rows H of the overlap-add blocks (512 H frames) the last call ran on; 0: it ran another tile
         case 17: return sp->ola_h;                // rows H this spatializer's long-enough calls use (0: the overlap-add tile is not used)
         case 18: return (int64_t)sp->position;    // frames processed since create / the last reset (the dither's frame position)
-        case 19: return sp->metering ? 1 : 0;     // the level meter is on (aw_spatializer_set_metering)
-        case 20: return sp->gain_mode;            // aw_gain_mode of the batch entries (aw_spatializer_set_gain)
-        case 21: return sp->loudness ? 1 : 0;     // the loudness measurement is on (aw_spatializer_set_loudness)
-        case 22: return sp->true_peak ? 1 : 0;    // the true-peak measurement is on (aw_spatializer_set_true_peak)
-        case 23: return sp->limiter ? 1 : 0;      // the limiter is on (aw_spatializer_set_limiter)
-        case 24: return sp->limiter ? awlim::delay(sp->lim_attack) : 0;      // its latency in frames
+        case 19: return sp->lv.metering ? 1 : 0;  // the level meter is on (aw_spatializer_set_metering)
+        case 20: return sp->lv.gain_mode;         // aw_gain_mode of the batch entries (aw_spatializer_set_gain)
+        case 21: return sp->ld.on ? 1 : 0;        // the loudness measurement is on (aw_spatializer_set_loudness)
+        case 22: return sp->tp.on ? 1 : 0;        // the true-peak measurement is on (aw_spatializer_set_true_peak)
+        case 23: return sp->lim.on ? 1 : 0;       // the limiter is on (aw_spatializer_set_limiter)
+        case 24: return sp->lim.on ? awlim::delay(sp->lim.attack) : 0;      // its latency in frames
         default: return -1;
     }
 }
@@ -1181,8 +1186,8 @@ aw_status aw_spatializer_reserve(aw_spatializer *sp, int64_t max_frames) try {
         if (st != AW_OK) return st;
     }
     sp->reserved_frames = std::max<int64_t>(sp->reserved_frames, max_frames);
-    if (sp->limiter) {              // the float32 staging in front of the limiter: every stream of the longest call
-        const aw_status st = sp_grow(sp, &sp->d_lim_y, &sp->lim_y_cap, (size_t)sp->n_streams * (size_t)max_frames * 2);
+    if (sp->lim.on) {              // the float32 staging in front of the limiter: every stream of the longest call
+        const aw_status st = sp_grow(sp, &sp->lim.d_y, &sp->lim.y_cap, (size_t)sp->n_streams * (size_t)max_frames * 2);
         if (st != AW_OK) return st;
     }
     return AW_OK;
@@ -1233,47 +1238,45 @@ static LwCallPlan sp_begin_call(aw_spatializer *sp, int64_t frames, uint64_t *po
 static_assert(AW_GAIN_NONE == awl::kGainNone && AW_GAIN_FIXED == awl::kGainFixed && AW_GAIN_PEAK_CEILING == awl::kGainPeakCeiling, "aw_gain_mode");
 static_assert(AW_GAIN_TRUE_PEAK_CEILING == 3, "aw_gain_mode");
 static_assert(sizeof(aw_stream_levels) == 56 && sizeof(awl::Record) == 40, "aw_stream_levels");
-static awl::Record *lv_records(const aw_spatializer *sp) { return reinterpret_cast<awl::Record *>(sp->d_levels); }
-static uint32_t *lv_call_peaks(const aw_spatializer *sp) { return reinterpret_cast<uint32_t *>(sp->d_levels + (size_t)sp->n_streams * sizeof(awl::Record)); }
-static float *lv_gains(const aw_spatializer *sp) { return reinterpret_cast<float *>(lv_call_peaks(sp) + sp->n_streams); }
-// a batch call has anything to do here; while this is false every entry launches what it always has
-static bool lv_active(const aw_spatializer *sp) { return sp->metering || sp->gain_mode != AW_GAIN_NONE; }
-// the levels kernel runs: the meter wants the sums, the automatic gain the call's peaks
-static bool lv_measures(const aw_spatializer *sp) { return sp->metering || sp->gain_mode == AW_GAIN_PEAK_CEILING; }
-
-// the one allocation (set_metering(1) / set_gain make it: never the process path), zeroed
-static aw_status lv_buffers(aw_spatializer *sp) {
-    if (sp->d_levels) return AW_OK;
-    const size_t bytes = (size_t)sp->n_streams * (sizeof(awl::Record) + sizeof(uint32_t) + sizeof(float));
-    AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sp->d_levels), bytes));
+// Every output stage (levels lv_, loudness ld_, true peak tp_, limiter lim_) answers the same calls: its setter makes its one allocation
+// (stage_alloc: never the process path), X_begin_call runs once per call before its first launch, PingPong::end_call flips its history
+// after a call that ran, lv_reset zeroes the reset range of each, and aw_spatializer_destroy frees `d`.  Where its bytes lie: X_layout.
+static awst::Levels lv_layout(const aw_spatializer *sp) { return awst::Levels{{(size_t)sp->n_streams}}; }
+static aw_status stage_zero(aw_spatializer *sp, void *p, size_t bytes) { AW_HIP_TRY(hipMemsetAsync(p, 0, bytes, sp->ctx->stream)); return AW_OK; }
+static aw_status stage_alloc(aw_spatializer *sp, unsigned char **d, size_t bytes, size_t zeroed) {       // (the first `zeroed` bytes start as zeros)
+    AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(d), bytes));
     sp->ctx->device_allocs += 1;
-    AW_HIP_TRY(hipMemsetAsync(sp->d_levels, 0, bytes, sp->ctx->stream));
-    return AW_OK;
+    return zeroed ? stage_zero(sp, *d, zeroed) : AW_OK;
 }
+// a batch call has anything to do here; while this is false every entry launches what it always has
+static bool lv_active(const aw_spatializer *sp) { return sp->lv.metering || sp->lv.gain_mode != AW_GAIN_NONE; }
+// the levels kernel runs: the meter wants the sums, the automatic gain the call's peaks
+static bool lv_measures(const aw_spatializer *sp) { return sp->lv.metering || sp->lv.gain_mode == AW_GAIN_PEAK_CEILING; }
+static aw_status lv_buffers(aw_spatializer *sp) { return sp->lv.d ? AW_OK : stage_alloc(sp, &sp->lv.d, lv_layout(sp).total, lv_layout(sp).total); }      // (set_metering(1) / set_gain)
 
 // Once per batch call, before its first launch: what the call applies (aw_stream_levels::gain), the frames it meters, and — where the
 // levels kernel runs (device) — the call-local peaks start from zero.
 static aw_status lv_begin_call(aw_spatializer *sp, int64_t frames, bool device) {
-    if (!lv_active(sp)) { sp->applied_mode = AW_GAIN_NONE; return AW_OK; }
-    sp->applied_mode = sp->gain_mode;
-    sp->applied_ceiling = sp->gain_ceiling;
-    sp->applied_on_host = !device;
-    if (sp->gain_mode == AW_GAIN_FIXED) sp->applied_gains = sp->gains;
-    if (sp->metering) sp->metered_frames += (uint64_t)frames;
-    if (device && lv_measures(sp)) AW_HIP_TRY(hipMemsetAsync(lv_call_peaks(sp), 0, (size_t)sp->n_streams * sizeof(uint32_t), sp->ctx->stream));
-    return AW_OK;
+    if (!lv_active(sp)) { sp->lv.applied_mode = AW_GAIN_NONE; return AW_OK; }
+    sp->lv.applied_mode = sp->lv.gain_mode;
+    sp->lv.applied_ceiling = sp->lv.gain_ceiling;
+    sp->lv.applied_on_host = !device;
+    if (sp->lv.gain_mode == AW_GAIN_FIXED) sp->lv.applied_gains = sp->lv.gains;
+    if (sp->lv.metering) sp->lv.frames += (uint64_t)frames;
+    return device && lv_measures(sp) ? stage_zero(sp, lv_layout(sp).call_peaks.at(sp->lv.d), lv_layout(sp).call_peaks.bytes()) : AW_OK;
 }
 
 // the true-peak kernel runs (below): the measurement is on, or the gain wants the call's true peaks
-static bool tp_runs(const aw_spatializer *sp) { return sp->true_peak || sp->gain_mode == AW_GAIN_TRUE_PEAK_CEILING; }
-static uint32_t *tp_call_peaks(const aw_spatializer *sp);
+static bool tp_runs(const aw_spatializer *sp) { return sp->tp.on || sp->lv.gain_mode == AW_GAIN_TRUE_PEAK_CEILING; }
+static awst::TruePeak tp_layout(const aw_spatializer *sp) { return awst::TruePeak{{(size_t)sp->n_streams}}; }
 
 // AW_GAIN_TRUE_PEAK_CEILING is the kernels' peak-ceiling gain over the call-local TRUE peaks
 static awk::PcmGain lv_gain_launch(const aw_spatializer *sp, int64_t s0) {
-    awl::Record *rec = sp->metering ? lv_records(sp) + s0 : nullptr;
-    if (sp->limiter) return awk::PcmGain{awl::kGainNone, 0.0f, lv_gains(sp) + s0, lv_call_peaks(sp) + s0, rec};      // (the limiter has applied the fixed gain)
-    if (sp->gain_mode == AW_GAIN_TRUE_PEAK_CEILING) return awk::PcmGain{awl::kGainPeakCeiling, sp->gain_ceiling, lv_gains(sp) + s0, tp_call_peaks(sp) + s0, rec};
-    return awk::PcmGain{sp->gain_mode, sp->gain_ceiling, lv_gains(sp) + s0, lv_call_peaks(sp) + s0, rec};
+    const awst::Levels L = lv_layout(sp);
+    awk::PcmGain g{sp->lv.gain_mode, sp->lv.gain_ceiling, L.gains.at(sp->lv.d, s0), L.call_peaks.at(sp->lv.d, s0), sp->lv.metering ? L.records.at(sp->lv.d, s0) : nullptr};
+    if (sp->lim.on) { g.mode = awl::kGainNone; g.ceiling = 0.0f; }      // (the limiter has applied the fixed gain)
+    else if (sp->lv.gain_mode == AW_GAIN_TRUE_PEAK_CEILING) { g.mode = awl::kGainPeakCeiling; g.call_peak = tp_layout(sp).call_peaks.at(sp->tp.d, s0); }
+    return g;
 }
 
 // After the kernels of the streams [s0, s0 + ns) have written their float32 output to f_out: meter it, and — float32 output with a gain
@@ -1284,10 +1287,11 @@ static aw_status lv_after_run(aw_spatializer *sp, float *f_out, int64_t s0, int 
     if (lv_measures(sp)) {
         SpStageTimer tm(sp);
         if (sp->profiling) tm.begin();
-        AW_HIP_TRY(awk::launch_levels(f_out, n, frames, sp->metering ? lv_records(sp) + s0 : nullptr, lv_call_peaks(sp) + s0, sp->ctx->stream));
+        const awst::Levels L = lv_layout(sp);
+        AW_HIP_TRY(awk::launch_levels(f_out, n, frames, sp->lv.metering ? L.records.at(sp->lv.d, s0) : nullptr, L.call_peaks.at(sp->lv.d, s0), sp->ctx->stream));
         if (sp->profiling) tm.end("aw_levels_kernel");
     }
-    if (float_out && sp->gain_mode != AW_GAIN_NONE) {
+    if (float_out && sp->lv.gain_mode != AW_GAIN_NONE) {
         SpStageTimer tm(sp);
         if (sp->profiling) tm.begin();
         AW_HIP_TRY(awk::launch_scale(f_out, n, frames, lv_gain_launch(sp, s0), sp->ctx->stream));
@@ -1302,29 +1306,31 @@ static float lv_host_call(aw_spatializer *sp, const float *y, size_t n) {
     double en[2] = {0.0, 0.0};
     unsigned nf = 0;
     if (lv_measures(sp)) for (size_t i = 0; i < n; ++i) awl::contribute(y[i], pk[i & 1], en[i & 1], nf);
-    if (sp->metering) {
+    aw_spatializer::Levels &lv = sp->lv;
+    if (lv.metering) {
         for (int e = 0; e < 2; ++e) {
-            sp->h_levels.peak_bits[e] = std::max(sp->h_levels.peak_bits[e], pk[e]);
-            sp->h_levels.energy[e] += en[e];
+            lv.host.peak_bits[e] = std::max(lv.host.peak_bits[e], pk[e]);
+            lv.host.energy[e] += en[e];
         }
-        sp->h_levels.nonfinite += nf;
+        lv.host.nonfinite += nf;
     }
     float g = 1.0f;
-    if (sp->gain_mode == AW_GAIN_FIXED) g = sp->gains[0];
-    else if (sp->gain_mode == AW_GAIN_PEAK_CEILING) g = awl::auto_gain(awl::bits_float(std::max(pk[0], pk[1])), sp->gain_ceiling);
-    else if (sp->gain_mode == AW_GAIN_TRUE_PEAK_CEILING) g = awl::auto_gain(awl::bits_float(sp->tp_pinned_call_bits), sp->gain_ceiling);
-    sp->applied_host_gain = g;
+    if (lv.gain_mode == AW_GAIN_FIXED) g = lv.gains[0];
+    else if (lv.gain_mode == AW_GAIN_PEAK_CEILING) g = awl::auto_gain(awl::bits_float(std::max(pk[0], pk[1])), lv.gain_ceiling);
+    else if (lv.gain_mode == AW_GAIN_TRUE_PEAK_CEILING) g = awl::auto_gain(awl::bits_float(sp->tp.pinned_call_bits), lv.gain_ceiling);
+    lv.applied_host_gain = g;
     return g;
 }
 
 /* ---- integrated loudness of the batch entries (aw_spatializer_set_loudness; rules: device/loudness.hpp, kernels: device/loudness_scan.hpp) -- */
 static_assert(sizeof(aw_stream_loudness) == 56, "aw_stream_loudness");
-static double *ld_state(const aw_spatializer *sp) { return reinterpret_cast<double *>(sp->d_loud); }
-static unsigned long long *ld_nonfinite(const aw_spatializer *sp) { return reinterpret_cast<unsigned long long *>(ld_state(sp) + (size_t)sp->n_streams * awk::kLdFilters * 4); }
-static double *ld_hops(const aw_spatializer *sp) { return reinterpret_cast<double *>(ld_nonfinite(sp) + sp->n_streams); }
-static size_t ld_record_bytes(const aw_spatializer *sp) { return (size_t)sp->n_streams * (awk::kLdFilters * 4 + 1 + (size_t)sp->loud_cap) * 8; }
-static double *ld_tables(const aw_spatializer *sp) { return reinterpret_cast<double *>(sp->d_loud + ld_record_bytes(sp)); }
 constexpr size_t kLdTabDoubles = (size_t)awk::kLdFilters * awk::kEqTabDoubles, kLdPlaneDoubles = (size_t)awk::kLdFilters * awh::kEqSectionPlaneDoubles;
+static awst::Loudness ld_layout(const aw_spatializer *sp) { return awst::Loudness{{(size_t)sp->n_streams}, (size_t)sp->ld.cap, kLdTabDoubles + kLdPlaneDoubles}; }
+
+static uint64_t ld_begin_call(aw_spatializer *sp, int64_t frames) {      // once per call: the count moves past it -> the frames measured before it (its hop index)
+    if (sp->ld.on) sp->ld.frames += (uint64_t)frames;
+    return sp->ld.frames - (sp->ld.on ? (uint64_t)frames : 0);
+}
 
 // The float32 output y of the streams [s0, s0 + ns) of a call (dense: `frames` apart), before any gain; frame0: frames measured before
 // this call.  Chunks of streams are independent (one workgroup owns a stream), so chunking changes no bit.
@@ -1332,59 +1338,33 @@ static aw_status ld_measure(aw_spatializer *sp, const float *y, int64_t s0, int 
     SpStageTimer tm(sp);
     if (sp->profiling) tm.begin();
     awk::LoudnessParams p{};
-    p.in = y;
-    p.z = ld_state(sp) + (size_t)s0 * awk::kLdFilters * 4;
-    p.hops = ld_hops(sp) + (size_t)s0 * (size_t)sp->loud_cap;
-    p.nonfinite = ld_nonfinite(sp) + s0;
-    p.tab = ld_tables(sp); p.plane = ld_tables(sp) + kLdTabDoubles;
-    p.frames = frames; p.stride_frames = frames; p.frame0 = (long long)frame0;
-    p.hop = sp->loud_hop; p.cap_hops = sp->loud_cap;
+    const awst::Loudness L = ld_layout(sp);
+    p.z = L.state.at(sp->ld.d, s0); p.hops = L.hops.at(sp->ld.d, s0); p.nonfinite = L.nonfinite.at(sp->ld.d, s0);
+    p.tab = L.tables.at(sp->ld.d); p.plane = p.tab + kLdTabDoubles;
+    p.in = y; p.frames = frames; p.stride_frames = frames; p.frame0 = (long long)frame0;
+    p.hop = sp->ld.hop; p.cap_hops = sp->ld.cap;
     AW_HIP_TRY(awk::launch_loudness(p, ns, sp->ctx->stream));
     if (sp->profiling) tm.end("aw_loudness_kernel");
-    return AW_OK;
-}
-
-// the records start over (the setting and the capacity stay)
-static aw_status ld_reset(aw_spatializer *sp) {
-    sp->loud_frames = 0;
-    if (sp->d_loud) AW_HIP_TRY(hipMemsetAsync(sp->d_loud, 0, ld_record_bytes(sp), sp->ctx->stream));
     return AW_OK;
 }
 
 /* ---- true peak of the batch entries (aw_spatializer_set_true_peak, AW_GAIN_TRUE_PEAK_CEILING; rules: device/truepeak.hpp, kernel:
  * device/truepeak_tile.hpp) ---- */
 static_assert(sizeof(aw_stream_true_peak) == 32, "aw_stream_true_peak");
-constexpr size_t kTpHistFloats = 2 * (size_t)awtp::kHistory;
-static unsigned long long *tp_nonfinite(const aw_spatializer *sp) { return reinterpret_cast<unsigned long long *>(sp->d_tp); }
-static uint32_t *tp_peaks(const aw_spatializer *sp) { return reinterpret_cast<uint32_t *>(tp_nonfinite(sp) + sp->n_streams); }
-static uint32_t *tp_call_peaks(const aw_spatializer *sp) { return tp_peaks(sp) + 2 * (size_t)sp->n_streams; }
-static float *tp_history(const aw_spatializer *sp, int slot) {
-    return reinterpret_cast<float *>(tp_call_peaks(sp) + sp->n_streams) + (size_t)slot * (size_t)sp->n_streams * kTpHistFloats;
-}
-static size_t tp_record_bytes(const aw_spatializer *sp) { return (size_t)sp->n_streams * (8 + 3 * 4); }
-static size_t tp_bytes(const aw_spatializer *sp) { return tp_record_bytes(sp) + 2 * (size_t)sp->n_streams * kTpHistFloats * sizeof(float); }
-
-// the one allocation (the setters make it: never the process path), zeroed, and the coefficients
+// the interpolator's coefficients, shared with the limiter: whichever setter runs first builds them
+static void tp_filter_once(aw_spatializer *sp) { if (!sp->tp_filter_built) { awtp::filter(sp->tp_filter); sp->tp_filter_built = true; } }
+// (set_true_peak(1) / set_gain(AW_GAIN_TRUE_PEAK_CEILING) when the kernel did not run before): the allocation, zeroed, and the coefficients.
+// Frames of unmeasured calls are not predecessors: where the allocation is there, the kernel starts again behind silence.
 static aw_status tp_buffers(aw_spatializer *sp) {
-    if (sp->d_tp) return AW_OK;
-    awtp::filter(sp->tp_filter);
-    AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sp->d_tp), tp_bytes(sp)));
-    sp->ctx->device_allocs += 1;
-    AW_HIP_TRY(hipMemsetAsync(sp->d_tp, 0, tp_bytes(sp), sp->ctx->stream));
-    return AW_OK;
-}
-
-// frames of unmeasured calls are not predecessors: the kernel starts (again) behind silence
-static aw_status tp_zero_history(aw_spatializer *sp) {
-    AW_HIP_TRY(hipMemsetAsync(tp_history(sp, 0), 0, 2 * (size_t)sp->n_streams * kTpHistFloats * sizeof(float), sp->ctx->stream));
-    return AW_OK;
+    const awst::TruePeak L = tp_layout(sp);
+    tp_filter_once(sp);
+    return sp->tp.d ? stage_zero(sp, L.history.at(sp->tp.d), 2 * L.history.bytes()) : stage_alloc(sp, &sp->tp.d, L.total, L.total);
 }
 
 // once per call that runs the kernel, before its first launch
 static aw_status tp_begin_call(aw_spatializer *sp, int64_t frames) {
-    if (sp->true_peak) sp->tp_frames += (uint64_t)frames;
-    AW_HIP_TRY(hipMemsetAsync(tp_call_peaks(sp), 0, (size_t)sp->n_streams * sizeof(uint32_t), sp->ctx->stream));
-    return AW_OK;
+    if (sp->tp.on) sp->tp.frames += (uint64_t)frames;
+    return stage_zero(sp, tp_layout(sp).call_peaks.at(sp->tp.d), tp_layout(sp).call_peaks.bytes());
 }
 
 // The float32 output y of the streams [s0, s0 + ns) of a call (dense: `frames` apart), before any gain.  A workgroup's tile lies in one
@@ -1394,69 +1374,46 @@ static aw_status tp_measure(aw_spatializer *sp, const float *y, int64_t s0, int 
     if (sp->profiling) tm.begin();
     awk::TruePeakParams p{};
     p.in = y; p.frames = frames; p.n_streams = ns;
-    p.hist_in = tp_history(sp, sp->tp_cur) + (size_t)s0 * kTpHistFloats;
-    p.hist_out = tp_history(sp, sp->tp_cur ^ 1) + (size_t)s0 * kTpHistFloats;
-    if (sp->true_peak) { p.tp_bits = tp_peaks(sp) + 2 * (size_t)s0; p.nonfinite = tp_nonfinite(sp) + s0; }
-    p.call_tp = tp_call_peaks(sp) + s0;
+    const awst::TruePeak L = tp_layout(sp);
+    p.hist_in = L.history.at(sp->tp.d, s0, sp->tp.hist.cur);
+    p.hist_out = L.history.at(sp->tp.d, s0, sp->tp.hist.cur ^ 1);
+    if (sp->tp.on) { p.tp_bits = L.peaks.at(sp->tp.d, s0); p.nonfinite = L.nonfinite.at(sp->tp.d, s0); }
+    p.call_tp = L.call_peaks.at(sp->tp.d, s0);
     std::memcpy(p.c, sp->tp_filter, sizeof(p.c));
     AW_HIP_TRY(awk::launch_truepeak(p, sp->ctx->stream));
-    sp->tp_ran = true;
+    sp->tp.hist.ran = true;
     if (sp->profiling) tm.end("aw_true_peak_kernel");
-    return AW_OK;
-}
-
-// the records and the history start over (the setting stays)
-static aw_status tp_reset(aw_spatializer *sp) {
-    sp->tp_frames = 0;
-    sp->tp_pinned_call_bits = 0;
-    if (sp->d_tp) AW_HIP_TRY(hipMemsetAsync(sp->d_tp, 0, tp_bytes(sp), sp->ctx->stream));
     return AW_OK;
 }
 
 /* ---- look-ahead true-peak limiter of the batch entries (aw_spatializer_set_limiter; rules: device/limiter.hpp, kernel:
  * device/limiter_tile.hpp) ---- */
 static_assert(sizeof(aw_stream_limiter) == 32, "aw_stream_limiter");
-static size_t lim_hist_floats(const aw_spatializer *sp) { return 2 * (size_t)awlim::halo(sp->lim_attack, sp->lim_hold); }
-static unsigned long long *lim_limited(const aw_spatializer *sp) { return reinterpret_cast<unsigned long long *>(sp->d_lim); }
-static unsigned long long *lim_nonfinite(const aw_spatializer *sp) { return lim_limited(sp) + sp->n_streams; }
-static uint32_t *lim_min_gain(const aw_spatializer *sp) { return reinterpret_cast<uint32_t *>(lim_nonfinite(sp) + sp->n_streams); }
-static float *lim_history(const aw_spatializer *sp, int slot) {
-    return reinterpret_cast<float *>(lim_min_gain(sp) + sp->n_streams) + (size_t)slot * (size_t)sp->n_streams * lim_hist_floats(sp);
-}
-static size_t lim_bytes_for(int n_streams, int attack, int hold) {
-    return (size_t)n_streams * (8 + 8 + 4 + 2 * 2 * (size_t)awlim::halo(attack, hold) * sizeof(float));
-}
+static awst::Limiter lim_layout(const aw_spatializer *sp) { return awst::Limiter{{(size_t)sp->n_streams}, sp->lim.attack, sp->lim.hold}; }
 
-// the history starts over behind silence (off -> on; a reset), on the device and for the single-stream path
-static aw_status lim_zero_history(aw_spatializer *sp) {
-    AW_HIP_TRY(hipMemsetAsync(lim_history(sp, 0), 0, 2 * (size_t)sp->n_streams * lim_hist_floats(sp) * sizeof(float), sp->ctx->stream));
-    sp->h_lim_hist.assign(lim_hist_floats(sp), 0.0f);
-    sp->lim_hist_on_host = false;
-    return AW_OK;
-}
-
-// the records start over: no frame limited, a lowest gain of 1
-static aw_status lim_zero_records(aw_spatializer *sp) {
-    sp->lim_frames = 0;
-    sp->h_lim = awlim::Record{};
-    AW_HIP_TRY(hipMemsetAsync(sp->d_lim, 0, (size_t)sp->n_streams * 16, sp->ctx->stream));
-    AW_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lim_min_gain(sp)), (int)awlim::kOneBits, (size_t)sp->n_streams, sp->ctx->stream));
-    return AW_OK;
-}
-
-static aw_status lim_reset(aw_spatializer *sp) {
-    if (!sp->d_lim) return AW_OK;
-    const aw_status st = lim_zero_records(sp);
-    return st == AW_OK ? lim_zero_history(sp) : st;
+// records (a reset, a new allocation): the records start over — no frame limited, a lowest gain of 1.  Always (those, and off -> on): the
+// history starts over behind silence, on the device and for the single-stream path.
+static aw_status lim_reset(aw_spatializer *sp, bool records) {
+    const awst::Limiter L = lim_layout(sp);
+    if (records) {
+        sp->lim.frames = 0;
+        sp->lim.host = awlim::Record{};
+        AW_HIP_TRY(hipMemsetAsync(sp->lim.d, 0, L.reset_bytes, sp->ctx->stream));
+        AW_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(L.min_gain.at(sp->lim.d)), (int)awlim::kOneBits, (size_t)sp->n_streams, sp->ctx->stream));
+    }
+    sp->lim.host_hist.assign(L.hist_floats, 0.0f);
+    sp->lim.hist_on_host = false;
+    return stage_zero(sp, L.history.at(sp->lim.d), 2 * L.history.bytes());
 }
 
 // once per call that runs the kernel, before its first launch: where the single-stream path ran last, its history is the newer one
 static aw_status lim_begin_call(aw_spatializer *sp, int64_t frames) {
-    sp->lim_frames += (uint64_t)frames;
-    if (sp->lim_hist_on_host) {
-        AW_HIP_TRY(hipMemcpyAsync(lim_history(sp, sp->lim_cur), sp->h_lim_hist.data(), lim_hist_floats(sp) * sizeof(float), hipMemcpyHostToDevice, sp->ctx->stream));
+    sp->lim.frames += (uint64_t)frames;
+    if (sp->lim.hist_on_host) {
+        const awst::Limiter L = lim_layout(sp);
+        AW_HIP_TRY(hipMemcpyAsync(L.history.at(sp->lim.d, 0, sp->lim.hist.cur), sp->lim.host_hist.data(), L.hist_floats * sizeof(float), hipMemcpyHostToDevice, sp->ctx->stream));
         AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
-        sp->lim_hist_on_host = false;
+        sp->lim.hist_on_host = false;
     }
     return AW_OK;
 }
@@ -1468,14 +1425,15 @@ static aw_status lim_run(aw_spatializer *sp, const float *y, float *z, int64_t s
     if (sp->profiling) tm.begin();
     awk::LimiterParams p{};
     p.in = y; p.out = z; p.frames = frames; p.n_streams = ns;
-    p.gain = sp->gain_mode == AW_GAIN_FIXED ? lv_gains(sp) + s0 : nullptr;
-    p.hist_in = lim_history(sp, sp->lim_cur) + (size_t)s0 * lim_hist_floats(sp);
-    p.hist_out = lim_history(sp, sp->lim_cur ^ 1) + (size_t)s0 * lim_hist_floats(sp);
-    p.min_gain = lim_min_gain(sp) + s0; p.limited = lim_limited(sp) + s0; p.nonfinite = lim_nonfinite(sp) + s0;
-    p.L = sp->lim_attack; p.H = sp->lim_hold; p.ceiling = sp->lim_ceiling;
+    const awst::Limiter L = lim_layout(sp);
+    p.gain = sp->lv.gain_mode == AW_GAIN_FIXED ? lv_layout(sp).gains.at(sp->lv.d, s0) : nullptr;
+    p.hist_in = L.history.at(sp->lim.d, s0, sp->lim.hist.cur);
+    p.hist_out = L.history.at(sp->lim.d, s0, sp->lim.hist.cur ^ 1);
+    p.min_gain = L.min_gain.at(sp->lim.d, s0); p.limited = L.limited.at(sp->lim.d, s0); p.nonfinite = L.nonfinite.at(sp->lim.d, s0);
+    p.L = sp->lim.attack; p.H = sp->lim.hold; p.ceiling = sp->lim.ceiling;
     std::memcpy(p.c, sp->tp_filter, sizeof(p.c));
     AW_HIP_TRY(awk::launch_limiter(p, sp->ctx->stream));
-    sp->lim_ran = true;
+    sp->lim.hist.ran = true;
     if (sp->profiling) tm.end("aw_limiter_kernel");
     return AW_OK;
 }
@@ -1483,12 +1441,14 @@ static aw_status lim_run(aw_spatializer *sp, const float *y, float *z, int64_t s
 // The single-stream page-locked path: the rule itself on the CPU, in place over the n = 2 * frames output samples y (the context's
 // stream is idle).  gain: what lv_host_call returned.
 static aw_status lim_host_call(aw_spatializer *sp, float *y, int64_t frames, float gain) {
-    if (!sp->lim_hist_on_host) {
-        AW_HIP_TRY(hipMemcpy(sp->h_lim_hist.data(), lim_history(sp, sp->lim_cur), lim_hist_floats(sp) * sizeof(float), hipMemcpyDeviceToHost));
-        sp->lim_hist_on_host = true;
+    aw_spatializer::Limiter &lim = sp->lim;
+    if (!lim.hist_on_host) {
+        const awst::Limiter L = lim_layout(sp);
+        AW_HIP_TRY(hipMemcpy(lim.host_hist.data(), L.history.at(lim.d, 0, lim.hist.cur), L.hist_floats * sizeof(float), hipMemcpyDeviceToHost));
+        lim.hist_on_host = true;
     }
-    sp->lim_frames += (uint64_t)frames;
-    awlim::sequential(sp->tp_filter, sp->lim_attack, sp->lim_hold, sp->lim_ceiling, gain, y, frames, sp->h_lim_hist.data(), y, sp->h_lim);
+    lim.frames += (uint64_t)frames;
+    awlim::sequential(sp->tp_filter, lim.attack, lim.hold, lim.ceiling, gain, y, frames, lim.host_hist.data(), y, lim.host);
     return AW_OK;
 }
 
@@ -1674,10 +1634,9 @@ static aw_status batch_begin(aw_spatializer *sp, BatchCall *call, unsigned long 
     if (metered) {
         aw_status st = lv_begin_call(sp, call->frames, true);
         if (st != AW_OK) return st;
-        call->loud0 = sp->loud_frames;
-        if (sp->loudness) sp->loud_frames += (uint64_t)call->frames;
+        call->loud0 = ld_begin_call(sp, call->frames);
         if (tp_runs(sp) && (st = tp_begin_call(sp, call->frames)) != AW_OK) return st;
-        if (sp->limiter && (st = lim_begin_call(sp, call->frames)) != AW_OK) return st;
+        if (sp->lim.on && (st = lim_begin_call(sp, call->frames)) != AW_OK) return st;
     }
     if (zero_clip) AW_HIP_TRY(hipMemsetAsync(clip, 0, sizeof(unsigned long long), sp->ctx->stream));
     return AW_OK;
@@ -1686,8 +1645,8 @@ static aw_status batch_begin(aw_spatializer *sp, BatchCall *call, unsigned long 
 // every chunk's kernels are queued: the history they wrote is the next call's
 static void batch_end(aw_spatializer *sp) {
     sp->hist_cur ^= 1;
-    if (sp->tp_ran) { sp->tp_cur ^= 1; sp->tp_ran = false; }
-    if (sp->lim_ran) { sp->lim_cur ^= 1; sp->lim_ran = false; }
+    sp->tp.hist.end_call();
+    sp->lim.hist.end_call();
 }
 
 // The streams [s0, s0 + ns) of a call, on the context's stream: pcm_src -> decode into f_in -> kernels -> meter / gain -> encode of f_out
@@ -1699,11 +1658,11 @@ static aw_status batch_chunk(aw_spatializer *sp, const BatchCall &call, int64_t 
     if (call.dec) st = pcm_decode(sp, call.in_fmt, pcm_src, f_in, (int64_t)ns * call.in_ps);
     const float *x = call.dec ? f_in : static_cast<const float *>(pcm_src);
     float *dst = call.enc ? f_out : static_cast<float *>(pcm_dst);
-    const bool lim = call.metered && sp->limiter;
-    if (st == AW_OK && lim) st = sp_grow(sp, &sp->d_lim_y, &sp->lim_y_cap, (size_t)ns * call.out_ps);      // (reserved for: nothing happens)
-    float *y = lim ? sp->d_lim_y : dst;
+    const bool lim = call.metered && sp->lim.on;
+    if (st == AW_OK && lim) st = sp_grow(sp, &sp->lim.d_y, &sp->lim.y_cap, (size_t)ns * call.out_ps);      // (reserved for: nothing happens)
+    float *y = lim ? sp->lim.d_y : dst;
     if (st == AW_OK) st = sp_run_streams(sp, call.lw, (int)s0, ns, x, y, call.frames);
-    if (st == AW_OK && call.metered && sp->loudness) st = ld_measure(sp, y, s0, ns, call.frames, call.loud0);      // (before the gain)
+    if (st == AW_OK && call.metered && sp->ld.on) st = ld_measure(sp, y, s0, ns, call.frames, call.loud0);      // (before the gain)
     if (st == AW_OK && call.metered && tp_runs(sp)) st = tp_measure(sp, y, s0, ns, call.frames);                   // (the gain may read its result)
     if (st == AW_OK && call.metered) st = lv_after_run(sp, y, s0, ns, call.frames, !call.enc && !lim);
     if (st == AW_OK && lim) st = lim_run(sp, y, dst, s0, ns, call.frames);
@@ -1717,18 +1676,16 @@ static aw_status batch_run_pinned(aw_spatializer *sp, int64_t frames, bool meter
     const LwCallPlan lw = sp_begin_call(sp, frames, pos0);
     aw_status st = metered ? lv_begin_call(sp, frames, false) : AW_OK;
     if (st == AW_OK) st = sp_run_streams(sp, lw, 0, 1, sp->h_pin_in, sp->h_pin_out, frames);
-    if (st == AW_OK && metered && sp->loudness) {        // the loudness kernels read the page-locked output as the convolution kernels wrote it
-        st = ld_measure(sp, sp->h_pin_out, 0, 1, frames, sp->loud_frames);
-        sp->loud_frames += (uint64_t)frames;
-    }
+    if (st == AW_OK && metered && sp->ld.on)             // the loudness kernels read the page-locked output as the convolution kernels wrote it
+        st = ld_measure(sp, sp->h_pin_out, 0, 1, frames, ld_begin_call(sp, frames));
     const bool tp = metered && tp_runs(sp);
     if (st == AW_OK && tp) st = tp_begin_call(sp, frames);
     if (st == AW_OK && tp) st = tp_measure(sp, sp->h_pin_out, 0, 1, frames);
-    if (st != AW_OK) { sp->tp_ran = false; return st; }
+    if (st != AW_OK) { sp->tp.hist.end_call(false); return st; }       // (the limiter runs on the CPU here: lim_host_call)
     batch_end(sp);
     AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
-    if (tp && sp->gain_mode == AW_GAIN_TRUE_PEAK_CEILING)       // the CPU gains this call: it needs the call's true peak
-        AW_HIP_TRY(hipMemcpy(&sp->tp_pinned_call_bits, tp_call_peaks(sp), sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (tp && sp->lv.gain_mode == AW_GAIN_TRUE_PEAK_CEILING)    // the CPU gains this call: it needs the call's true peak
+        AW_HIP_TRY(hipMemcpy(&sp->tp.pinned_call_bits, tp_layout(sp).call_peaks.at(sp->tp.d), sizeof(uint32_t), hipMemcpyDeviceToHost));
     return AW_OK;
 }
 
@@ -1760,7 +1717,7 @@ static aw_status host_process_pinned(aw_spatializer *sp, const BatchCall &call, 
     if (st != AW_OK) return st;
     const bool lv = lv_active(sp);
     float gain = lv ? lv_host_call(sp, sp->h_pin_out, out_ps) : 1.0f;
-    if (sp->limiter) {                   // z replaces y in the staging; the fixed gain went in with it
+    if (sp->lim.on) {                   // z replaces y in the staging; the fixed gain went in with it
         const aw_status sl = lim_host_call(sp, sp->h_pin_out, call.frames, gain);
         if (sl != AW_OK) return sl;
         gain = 1.0f;
@@ -1775,9 +1732,9 @@ static aw_status host_process_pinned(aw_spatializer *sp, const BatchCall &call, 
             else awp::encode_dithered_at(out_fmt, mode, sp->h_pin_out[i], key, pos0 + i / 2, (int)(i & 1), out + i * out_b, &k);
             n_clip += k;
         }
-        if (sp->metering) sp->h_levels.clipped += n_clip;
+        if (sp->lv.metering) sp->lv.host.clipped += n_clip;
         if (clipped) *clipped = n_clip;
-    } else if (sp->gain_mode != AW_GAIN_NONE) {
+    } else if (sp->lv.gain_mode != AW_GAIN_NONE) {
         float *o = reinterpret_cast<float *>(out);
         for (size_t i = 0; i < out_ps; ++i) o[i] = awl::apply_gain(sp->h_pin_out[i], gain);
     } else {
@@ -1979,15 +1936,30 @@ aw_status aw_spatializer_process_planar(aw_spatializer *sp, const float *in_l, c
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 
-// the records start over (the setting stays)
+// every stage's records start over (the settings stay)
 static aw_status lv_reset(aw_spatializer *sp) {
-    sp->h_levels = awl::Record{};
-    sp->metered_frames = 0;
-    sp->applied_mode = AW_GAIN_NONE;
-    if (sp->d_levels) AW_HIP_TRY(hipMemsetAsync(sp->d_levels, 0, (size_t)sp->n_streams * (sizeof(awl::Record) + sizeof(uint32_t)), sp->ctx->stream));
-    aw_status st = ld_reset(sp);
-    if (st == AW_OK) st = tp_reset(sp);
-    return st == AW_OK ? lim_reset(sp) : st;
+    sp->lv.host = awl::Record{};
+    sp->lv.applied_mode = AW_GAIN_NONE;
+    sp->lv.frames = sp->ld.frames = sp->tp.frames = 0;
+    sp->tp.pinned_call_bits = 0;
+    aw_status st = sp->lv.d ? stage_zero(sp, sp->lv.d, lv_layout(sp).reset_bytes) : AW_OK;
+    if (st == AW_OK && sp->ld.d) st = stage_zero(sp, sp->ld.d, ld_layout(sp).reset_bytes);
+    if (st == AW_OK && sp->tp.d) st = stage_zero(sp, sp->tp.d, tp_layout(sp).reset_bytes);
+    return st == AW_OK && sp->lim.d ? lim_reset(sp, true) : st;
+}
+
+// The prologue of the four record getters, answered in this order: a NULL handle, the stream range, n == 0 (AW_OK, *lk left unlocked: the
+// call is over), a NULL out, a stage (base: its allocation) whose records were never made; then the device is current, the launch lock held, the stream idle.
+static aw_status get_begin(aw_spatializer *sp, int32_t first_stream, int32_t n, const void *out, unsigned char *(*base)(const aw_spatializer *), const char *never, std::unique_lock<std::mutex> *lk) {
+    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    if (first_stream < 0 || n < 0 || (int64_t)first_stream + n > sp->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "streams out of range");
+    if (n == 0) return AW_OK;
+    if (!out) return fail(AW_ERR_INVALID_ARGUMENT, "out_host is NULL");
+    if (!base(sp)) return fail(AW_ERR_INVALID_ARGUMENT, never);
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    *lk = std::unique_lock<std::mutex>(sp->ctx->launch_mu);
+    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
+    return AW_OK;
 }
 
 aw_status aw_spatializer_reset(aw_spatializer *sp) try {
@@ -2008,7 +1980,7 @@ aw_status aw_spatializer_set_metering(aw_spatializer *sp, int32_t on) try {
         const aw_status st = lv_buffers(sp);
         if (st != AW_OK) return st;
     }
-    sp->metering = on != 0;
+    sp->lv.metering = on != 0;
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 
@@ -2019,36 +1991,32 @@ aw_status aw_spatializer_reset_levels(aw_spatializer *sp) try {
 } AW_NOEXCEPT_TAIL
 
 aw_status aw_spatializer_get_levels(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_levels *out) try {
-    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
-    if (first_stream < 0 || n < 0 || (int64_t)first_stream + n > sp->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "streams out of range");
-    if (n == 0) return AW_OK;
-    if (!out) return fail(AW_ERR_INVALID_ARGUMENT, "out_host is NULL");
-    if (!sp->d_levels) return fail(AW_ERR_INVALID_ARGUMENT, "no levels: neither aw_spatializer_set_metering nor aw_spatializer_set_gain has been called");
-    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
-    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
-    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
-    std::vector<awl::Record> rec((size_t)n);
-    std::vector<uint32_t> peaks((size_t)n);
-    AW_HIP_TRY(hipMemcpy(rec.data(), lv_records(sp) + first_stream, (size_t)n * sizeof(awl::Record), hipMemcpyDeviceToHost));
-    const uint32_t *call_peaks = sp->applied_mode == AW_GAIN_TRUE_PEAK_CEILING && sp->d_tp ? tp_call_peaks(sp) : lv_call_peaks(sp);
-    AW_HIP_TRY(hipMemcpy(peaks.data(), call_peaks + first_stream, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    std::unique_lock<std::mutex> lk;
+    aw_status st = get_begin(sp, first_stream, n, out, [](const aw_spatializer *s) { return s->lv.d; }, "no levels: neither aw_spatializer_set_metering nor aw_spatializer_set_gain has been called", &lk);
+    if (st != AW_OK || !lk) return st;
+    std::vector<awl::Record> rec;
+    std::vector<uint32_t> peaks;
+    if ((st = get_field(lv_layout(sp).records, sp->lv.d, first_stream, n, &rec)) != AW_OK) return st;
+    st = sp->lv.applied_mode == AW_GAIN_TRUE_PEAK_CEILING && sp->tp.d ? get_field(tp_layout(sp).call_peaks, sp->tp.d, first_stream, n, &peaks)
+                                                                      : get_field(lv_layout(sp).call_peaks, sp->lv.d, first_stream, n, &peaks);
+    if (st != AW_OK) return st;
     for (int32_t i = 0; i < n; ++i) {
         awl::Record r = rec[(size_t)i];
         const int32_t s = first_stream + i;
         if (s == 0) {                    // the single-stream path's share (a handle of one stream)
-            for (int e = 0; e < 2; ++e) { r.peak_bits[e] = std::max(r.peak_bits[e], sp->h_levels.peak_bits[e]); r.energy[e] += sp->h_levels.energy[e]; }
-            r.clipped += sp->h_levels.clipped;
-            r.nonfinite += sp->h_levels.nonfinite;
+            for (int e = 0; e < 2; ++e) { r.peak_bits[e] = std::max(r.peak_bits[e], sp->lv.host.peak_bits[e]); r.energy[e] += sp->lv.host.energy[e]; }
+            r.clipped += sp->lv.host.clipped;
+            r.nonfinite += sp->lv.host.nonfinite;
         }
         aw_stream_levels &o = out[i];
         o.peak[0] = awl::bits_float(r.peak_bits[0]); o.peak[1] = awl::bits_float(r.peak_bits[1]);
         o.gain = 1.0f;
-        if (sp->applied_mode == AW_GAIN_FIXED && (size_t)s < sp->applied_gains.size()) o.gain = sp->applied_gains[(size_t)s];
-        else if (sp->applied_mode == AW_GAIN_PEAK_CEILING || sp->applied_mode == AW_GAIN_TRUE_PEAK_CEILING)
-            o.gain = sp->applied_on_host ? sp->applied_host_gain : awl::auto_gain(awl::bits_float(peaks[(size_t)i]), sp->applied_ceiling);
+        if (sp->lv.applied_mode == AW_GAIN_FIXED && (size_t)s < sp->lv.applied_gains.size()) o.gain = sp->lv.applied_gains[(size_t)s];
+        else if (sp->lv.applied_mode == AW_GAIN_PEAK_CEILING || sp->lv.applied_mode == AW_GAIN_TRUE_PEAK_CEILING)
+            o.gain = sp->lv.applied_on_host ? sp->lv.applied_host_gain : awl::auto_gain(awl::bits_float(peaks[(size_t)i]), sp->lv.applied_ceiling);
         o.reserved = 0;
         o.energy[0] = r.energy[0]; o.energy[1] = r.energy[1];
-        o.frames = sp->metered_frames;
+        o.frames = sp->lv.frames;
         o.clipped = r.clipped;
         o.nonfinite = r.nonfinite;
     }
@@ -2059,14 +2027,14 @@ aw_status aw_spatializer_get_levels(aw_spatializer *sp, int32_t first_stream, in
 // makes new, empty records.
 aw_status aw_spatializer_set_loudness(aw_spatializer *sp, int32_t on, double max_seconds) try {
     if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
-    if (!on) { sp->loudness = false; return AW_OK; }
+    if (!on) { sp->ld.on = false; return AW_OK; }
     if (!std::isfinite(max_seconds) || !(max_seconds > 0.0) || max_seconds > 1e9) return fail(AW_ERR_INVALID_ARGUMENT, "max_seconds must be finite and positive");
     const long long hop = awlo::hop_frames(sp->sample_rate);
     if (hop <= 0) return fail(AW_ERR_INVALID_ARGUMENT, "loudness needs an HRIR sample rate that is a finite positive multiple of 10 Hz");
     const int64_t cap = (int64_t)std::ceil((double)awlo::kHopsPerSecond * max_seconds);
     AW_HIP_TRY(hipSetDevice(sp->ctx->device));
     std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
-    if (!sp->d_loud || cap != sp->loud_cap) {
+    if (!sp->ld.d || cap != sp->ld.cap) {
         double kw[awlo::kFilters][5];
         awlo::k_weighting(sp->sample_rate, kw);
         std::vector<double> tables(kLdTabDoubles + kLdPlaneDoubles);
@@ -2074,44 +2042,38 @@ aw_status aw_spatializer_set_loudness(aw_spatializer *sp, int32_t on, double max
             awh::eq_section_tables(awh::Biquad{kw[k][0], kw[k][1], kw[k][2], kw[k][3], kw[k][4]}, &tables[(size_t)k * awk::kEqTabDoubles],
                                    &tables[kLdTabDoubles + (size_t)k * awh::kEqSectionPlaneDoubles]);
         AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));            // whatever still reads the old records
-        if (sp->d_loud) { (void)hipFree(sp->d_loud); sp->d_loud = nullptr; sp->loudness = false; }
-        sp->loud_hop = hop; sp->loud_cap = cap; sp->loud_frames = 0;
-        const size_t rec = ld_record_bytes(sp);
-        AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sp->d_loud), rec + tables.size() * sizeof(double)));
-        sp->ctx->device_allocs += 1;
-        AW_HIP_TRY(hipMemsetAsync(sp->d_loud, 0, rec, sp->ctx->stream));
-        AW_HIP_TRY(hipMemcpyAsync(ld_tables(sp), tables.data(), tables.size() * sizeof(double), hipMemcpyHostToDevice, sp->ctx->stream));
+        if (sp->ld.d) { (void)hipFree(sp->ld.d); sp->ld.d = nullptr; sp->ld.on = false; }
+        sp->ld.hop = hop; sp->ld.cap = cap; sp->ld.frames = 0;
+        const awst::Loudness L = ld_layout(sp);
+        const aw_status st = stage_alloc(sp, &sp->ld.d, L.total, L.reset_bytes);
+        if (st != AW_OK) return st;
+        AW_HIP_TRY(hipMemcpyAsync(L.tables.at(sp->ld.d), tables.data(), tables.size() * sizeof(double), hipMemcpyHostToDevice, sp->ctx->stream));
         AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));            // (the upload reads `tables`)
     }
-    sp->loudness = true;
+    sp->ld.on = true;
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 
 aw_status aw_spatializer_get_loudness(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_loudness *out) try {
-    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
-    if (first_stream < 0 || n < 0 || (int64_t)first_stream + n > sp->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "streams out of range");
-    if (n == 0) return AW_OK;
-    if (!out) return fail(AW_ERR_INVALID_ARGUMENT, "out_host is NULL");
-    if (!sp->d_loud) return fail(AW_ERR_INVALID_ARGUMENT, "no loudness: aw_spatializer_set_loudness has not been called");
-    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
-    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
-    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
-    const uint64_t cap_frames = (uint64_t)sp->loud_cap * (uint64_t)sp->loud_hop;
-    const int64_t n_hops = (int64_t)(std::min(sp->loud_frames, cap_frames) / (uint64_t)sp->loud_hop);     // complete hops only
+    std::unique_lock<std::mutex> lk;
+    aw_status st = get_begin(sp, first_stream, n, out, [](const aw_spatializer *s) { return s->ld.d; }, "no loudness: aw_spatializer_set_loudness has not been called", &lk);
+    if (st != AW_OK || !lk) return st;
+    const awst::Loudness L = ld_layout(sp);
+    const uint64_t cap_frames = (uint64_t)sp->ld.cap * (uint64_t)sp->ld.hop;
+    const int64_t n_hops = (int64_t)(std::min(sp->ld.frames, cap_frames) / (uint64_t)sp->ld.hop);     // complete hops only
     std::vector<double> e((size_t)n * (size_t)std::max<int64_t>(n_hops, 1));
-    std::vector<unsigned long long> nf((size_t)n);
-    if (n_hops > 0)
-        AW_HIP_TRY(hipMemcpy2D(e.data(), (size_t)n_hops * 8, ld_hops(sp) + (size_t)first_stream * (size_t)sp->loud_cap, (size_t)sp->loud_cap * 8, (size_t)n_hops * 8,
-                               (size_t)n, hipMemcpyDeviceToHost));
-    AW_HIP_TRY(hipMemcpy(nf.data(), ld_nonfinite(sp) + first_stream, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    std::vector<unsigned long long> nf;
+    if (n_hops > 0)                                       // (the complete hops of each stream's row, not the whole field)
+        AW_HIP_TRY(hipMemcpy2D(e.data(), (size_t)n_hops * 8, L.hops.at(sp->ld.d, (size_t)first_stream), L.hops.per_stream * 8, (size_t)n_hops * 8, (size_t)n, hipMemcpyDeviceToHost));
+    if ((st = get_field(L.nonfinite, sp->ld.d, first_stream, n, &nf)) != AW_OK) return st;
     for (int32_t i = 0; i < n; ++i) {
-        const awlo::Gated g = awlo::gate(e.data() + (size_t)i * (size_t)n_hops, n_hops, sp->loud_hop);
+        const awlo::Gated g = awlo::gate(e.data() + (size_t)i * (size_t)n_hops, n_hops, sp->ld.hop);
         aw_stream_loudness &o = out[i];
         o.integrated_lufs = g.integrated_lufs; o.relative_threshold_lufs = g.relative_threshold_lufs;
         o.blocks = g.blocks; o.blocks_above_absolute = g.blocks_above_absolute; o.blocks_gated = g.blocks_gated;
         o.reserved = 0;
-        o.frames = sp->loud_frames;
-        o.frames_dropped = sp->loud_frames > cap_frames ? sp->loud_frames - cap_frames : 0;
+        o.frames = sp->ld.frames;
+        o.frames_dropped = sp->ld.frames > cap_frames ? sp->ld.frames - cap_frames : 0;
         o.nonfinite = nf[(size_t)i];
     }
     return AW_OK;
@@ -2120,13 +2082,13 @@ aw_status aw_spatializer_get_loudness(aw_spatializer *sp, int32_t first_stream, 
 aw_status aw_spatializer_get_loudness_hops(aw_spatializer *sp, int32_t stream, int64_t first_hop, int64_t n, double *out) try {
     if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
     if (stream < 0 || stream >= sp->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "stream out of range");
-    if (first_hop < 0 || n < 0 || first_hop > sp->loud_cap || n > sp->loud_cap - first_hop) return fail(AW_ERR_INVALID_ARGUMENT, "hops out of range");
+    if (first_hop < 0 || n < 0 || first_hop > sp->ld.cap || n > sp->ld.cap - first_hop) return fail(AW_ERR_INVALID_ARGUMENT, "hops out of range");
     if (n == 0) return AW_OK;
     if (!out) return fail(AW_ERR_INVALID_ARGUMENT, "out_host is NULL");
     AW_HIP_TRY(hipSetDevice(sp->ctx->device));
     std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
     AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
-    AW_HIP_TRY(hipMemcpy(out, ld_hops(sp) + (size_t)stream * (size_t)sp->loud_cap + (size_t)first_hop, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    AW_HIP_TRY(hipMemcpy(out, ld_layout(sp).hops.at(sp->ld.d, (size_t)stream) + (size_t)first_hop, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 
@@ -2139,38 +2101,31 @@ aw_status aw_loudness_gain(double lufs, double target_lufs, float *gain) try {
 // The one allocation is made here, never on the process path.  Off -> on: the history is zeroed, the peaks stay.
 aw_status aw_spatializer_set_true_peak(aw_spatializer *sp, int32_t on) try {
     if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
-    if (!on) { sp->true_peak = false; return AW_OK; }
-    if (sp->true_peak) return AW_OK;
+    if (!on) { sp->tp.on = false; return AW_OK; }
+    if (sp->tp.on) return AW_OK;
     if (!sp->ctx || sp->n_streams < 1) return fail(AW_ERR_INVALID_ARGUMENT, "the handle has no streams");
     AW_HIP_TRY(hipSetDevice(sp->ctx->device));
     std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
-    aw_status st = tp_buffers(sp);
-    if (st == AW_OK) st = tp_zero_history(sp);
-    if (st != AW_OK) return st;
-    sp->true_peak = true;
-    return AW_OK;
+    const aw_status st = tp_buffers(sp);
+    if (st == AW_OK) sp->tp.on = true;
+    return st;
 } AW_NOEXCEPT_TAIL
 
 aw_status aw_spatializer_get_true_peak(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_true_peak *out) try {
-    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
-    if (first_stream < 0 || n < 0 || (int64_t)first_stream + n > sp->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "streams out of range");
-    if (n == 0) return AW_OK;
-    if (!out) return fail(AW_ERR_INVALID_ARGUMENT, "out_host is NULL");
-    if (!sp->d_tp) return fail(AW_ERR_INVALID_ARGUMENT, "no true peak: neither aw_spatializer_set_true_peak nor AW_GAIN_TRUE_PEAK_CEILING has been used");
-    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
-    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
-    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
-    std::vector<unsigned long long> nf((size_t)n);
-    std::vector<uint32_t> pk(2 * (size_t)n), call((size_t)n);
-    AW_HIP_TRY(hipMemcpy(nf.data(), tp_nonfinite(sp) + first_stream, nf.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    AW_HIP_TRY(hipMemcpy(pk.data(), tp_peaks(sp) + 2 * (size_t)first_stream, pk.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    AW_HIP_TRY(hipMemcpy(call.data(), tp_call_peaks(sp) + first_stream, call.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    std::unique_lock<std::mutex> lk;
+    aw_status st = get_begin(sp, first_stream, n, out, [](const aw_spatializer *s) { return s->tp.d; }, "no true peak: neither aw_spatializer_set_true_peak nor AW_GAIN_TRUE_PEAK_CEILING has been used", &lk);
+    if (st != AW_OK || !lk) return st;
+    const awst::TruePeak L = tp_layout(sp);
+    std::vector<unsigned long long> nf;
+    std::vector<uint32_t> pk, call;
+    if ((st = get_field(L.nonfinite, sp->tp.d, first_stream, n, &nf)) != AW_OK || (st = get_field(L.peaks, sp->tp.d, first_stream, n, &pk)) != AW_OK ||
+        (st = get_field(L.call_peaks, sp->tp.d, first_stream, n, &call)) != AW_OK) return st;
     for (int32_t i = 0; i < n; ++i) {
         aw_stream_true_peak &o = out[i];
         o.true_peak[0] = awtp::bits_float(pk[2 * (size_t)i]); o.true_peak[1] = awtp::bits_float(pk[2 * (size_t)i + 1]);
         o.call_true_peak = awtp::bits_float(call[(size_t)i]);
         o.reserved = 0;
-        o.frames = sp->tp_frames;
+        o.frames = sp->tp.frames;
         o.nonfinite = nf[(size_t)i];
     }
     return AW_OK;
@@ -2188,64 +2143,55 @@ aw_status aw_true_peak_filter(float *out36) try {
 // and a change of attack or hold start from empty history; the records stay until a reset unless the allocation is made anew.
 aw_status aw_spatializer_set_limiter(aw_spatializer *sp, int32_t on, float ceiling, int32_t attack_frames, int32_t hold_frames) try {
     if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
-    if (!on) { sp->limiter = false; return AW_OK; }
+    if (!on) { sp->lim.on = false; return AW_OK; }
     if (!sp->ctx || sp->n_streams < 1) return fail(AW_ERR_INVALID_ARGUMENT, "the handle has no streams");
     if (!(ceiling > 0.0f && ceiling <= 1.0f)) return fail(AW_ERR_INVALID_ARGUMENT, "ceiling must lie in (0, 1]");
     if (attack_frames < awlim::kMinAttack || attack_frames > awlim::kMaxAttack) return fail(AW_ERR_INVALID_ARGUMENT, "attack_frames must lie in [16, 512]");
     if (hold_frames < 0 || hold_frames > awlim::kMaxHold) return fail(AW_ERR_INVALID_ARGUMENT, "hold_frames must lie in [0, 1024]");
-    if (sp->gain_mode == AW_GAIN_PEAK_CEILING || sp->gain_mode == AW_GAIN_TRUE_PEAK_CEILING)
+    if (sp->lv.gain_mode == AW_GAIN_PEAK_CEILING || sp->lv.gain_mode == AW_GAIN_TRUE_PEAK_CEILING)
         return fail(AW_ERR_INVALID_ARGUMENT, "a per-call ceiling gain cannot feed the limiter: set AW_GAIN_NONE or AW_GAIN_FIXED first");
     AW_HIP_TRY(hipSetDevice(sp->ctx->device));
     std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
-    const bool same_shape = sp->d_lim && sp->lim_attack == attack_frames && sp->lim_hold == hold_frames;
-    if (sp->limiter && same_shape) { sp->lim_ceiling = ceiling; return AW_OK; }
+    const bool same_shape = sp->lim.d && sp->lim.attack == attack_frames && sp->lim.hold == hold_frames;
+    if (sp->lim.on && same_shape) { sp->lim.ceiling = ceiling; return AW_OK; }
     aw_status st = AW_OK;
     const int64_t longest = std::max(sp->reserved_frames, sp->host_reserved_frames);
-    if (longest > 0 && (st = sp_grow(sp, &sp->d_lim_y, &sp->lim_y_cap, (size_t)sp->n_streams * (size_t)longest * 2)) != AW_OK) return st;
+    if (longest > 0 && (st = sp_grow(sp, &sp->lim.d_y, &sp->lim.y_cap, (size_t)sp->n_streams * (size_t)longest * 2)) != AW_OK) return st;
     if (!same_shape) {
-        const size_t bytes = lim_bytes_for(sp->n_streams, attack_frames, hold_frames);
         unsigned char *d = nullptr;
-        AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), bytes));
-        sp->ctx->device_allocs += 1;
-        if (sp->d_lim) {
+        if ((st = stage_alloc(sp, &d, awst::Limiter{{(size_t)sp->n_streams}, attack_frames, hold_frames}.total, 0)) != AW_OK) return st;
+        if (sp->lim.d) {
             AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
-            (void)hipFree(sp->d_lim);
+            (void)hipFree(sp->lim.d);
         }
-        sp->d_lim = d;
-        sp->lim_attack = attack_frames; sp->lim_hold = hold_frames;
-        sp->lim_cur = 0;
-        if ((st = lim_zero_records(sp)) != AW_OK) return st;
+        sp->lim.d = d;
+        sp->lim.attack = attack_frames; sp->lim.hold = hold_frames; sp->lim.hist.cur = 0;
     }
-    if ((st = lim_zero_history(sp)) != AW_OK) return st;
-    awtp::filter(sp->tp_filter);
-    sp->lim_ceiling = ceiling;
-    sp->limiter = true;
+    if ((st = lim_reset(sp, !same_shape)) != AW_OK) return st;
+    tp_filter_once(sp);
+    sp->lim.ceiling = ceiling;
+    sp->lim.on = true;
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 
 aw_status aw_spatializer_get_limiter(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_limiter *out) try {
-    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
-    if (first_stream < 0 || n < 0 || (int64_t)first_stream + n > sp->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "streams out of range");
-    if (n == 0) return AW_OK;
-    if (!out) return fail(AW_ERR_INVALID_ARGUMENT, "out_host is NULL");
-    if (!sp->d_lim) return fail(AW_ERR_INVALID_ARGUMENT, "no limiter: aw_spatializer_set_limiter has not been called");
-    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
-    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
-    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
-    std::vector<unsigned long long> lim((size_t)n), nf((size_t)n);
-    std::vector<uint32_t> mg((size_t)n);
-    AW_HIP_TRY(hipMemcpy(lim.data(), lim_limited(sp) + first_stream, lim.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    AW_HIP_TRY(hipMemcpy(nf.data(), lim_nonfinite(sp) + first_stream, nf.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    AW_HIP_TRY(hipMemcpy(mg.data(), lim_min_gain(sp) + first_stream, mg.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    std::unique_lock<std::mutex> lk;
+    aw_status st = get_begin(sp, first_stream, n, out, [](const aw_spatializer *s) { return s->lim.d; }, "no limiter: aw_spatializer_set_limiter has not been called", &lk);
+    if (st != AW_OK || !lk) return st;
+    const awst::Limiter L = lim_layout(sp);
+    std::vector<unsigned long long> lim, nf;
+    std::vector<uint32_t> mg;
+    if ((st = get_field(L.limited, sp->lim.d, first_stream, n, &lim)) != AW_OK || (st = get_field(L.nonfinite, sp->lim.d, first_stream, n, &nf)) != AW_OK ||
+        (st = get_field(L.min_gain, sp->lim.d, first_stream, n, &mg)) != AW_OK) return st;
     for (int32_t i = 0; i < n; ++i) {
         if (first_stream + i == 0) {     // the single-stream path's share (a handle of one stream)
-            mg[(size_t)i] = std::min(mg[(size_t)i], sp->h_lim.min_gain_bits);
-            lim[(size_t)i] += sp->h_lim.limited_frames; nf[(size_t)i] += sp->h_lim.nonfinite;
+            mg[(size_t)i] = std::min(mg[(size_t)i], sp->lim.host.min_gain_bits);
+            lim[(size_t)i] += sp->lim.host.limited_frames; nf[(size_t)i] += sp->lim.host.nonfinite;
         }
         aw_stream_limiter &o = out[i];
         o.min_gain = awl::bits_float(mg[(size_t)i]);
         o.reserved = 0;
-        o.frames = sp->lim_frames;
+        o.frames = sp->lim.frames;
         o.limited_frames = lim[(size_t)i];
         o.nonfinite = nf[(size_t)i];
     }
@@ -2264,29 +2210,27 @@ aw_status aw_spatializer_set_gain(aw_spatializer *sp, aw_gain_mode mode, const f
             if (!std::isfinite(gains_host[i])) return fail(AW_ERR_INVALID_ARGUMENT, "gains must be finite");
     }
     if ((mode == AW_GAIN_PEAK_CEILING || mode == AW_GAIN_TRUE_PEAK_CEILING) && !(ceiling > 0.0f && ceiling <= 1.0f)) return fail(AW_ERR_INVALID_ARGUMENT, "ceiling must lie in (0, 1]");
-    if ((mode == AW_GAIN_PEAK_CEILING || mode == AW_GAIN_TRUE_PEAK_CEILING) && sp->limiter)
+    if ((mode == AW_GAIN_PEAK_CEILING || mode == AW_GAIN_TRUE_PEAK_CEILING) && sp->lim.on)
         return fail(AW_ERR_INVALID_ARGUMENT, "a per-call ceiling gain cannot feed the limiter: switch the limiter off first");
-    if (mode == AW_GAIN_NONE) { sp->gain_mode = AW_GAIN_NONE; return AW_OK; }
+    if (mode == AW_GAIN_NONE) { sp->lv.gain_mode = AW_GAIN_NONE; return AW_OK; }
     // the per-stream records below are sized by the stream count: a handle without streams or context has nothing to gain
     if (!sp->ctx || sp->n_streams < 1) return fail(AW_ERR_INVALID_ARGUMENT, "the handle has no streams");
     AW_HIP_TRY(hipSetDevice(sp->ctx->device));
     std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
     aw_status st = lv_buffers(sp);
     if (st != AW_OK) return st;
-    if (mode == AW_GAIN_TRUE_PEAK_CEILING && !tp_runs(sp)) {      // the true-peak kernel starts here, behind silence
-        if ((st = tp_buffers(sp)) != AW_OK || (st = tp_zero_history(sp)) != AW_OK) return st;
-    }
+    if (mode == AW_GAIN_TRUE_PEAK_CEILING && !tp_runs(sp) && (st = tp_buffers(sp)) != AW_OK) return st;      // the true-peak kernel starts here, behind silence
     if (mode == AW_GAIN_FIXED) {
         std::vector<float> g((size_t)sp->n_streams);
         for (int32_t s = 0; s < sp->n_streams; ++s) g[(size_t)s] = gains_host[n == 1 ? 0 : s];
         // ordered behind whatever the context's stream still reads the old gains for
-        AW_HIP_TRY(hipMemcpyAsync(lv_gains(sp), g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice, sp->ctx->stream));
+        AW_HIP_TRY(hipMemcpyAsync(lv_layout(sp).gains.at(sp->lv.d), g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice, sp->ctx->stream));
         AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
-        sp->gains.swap(g);
+        sp->lv.gains.swap(g);
     } else {
-        sp->gain_ceiling = ceiling;
+        sp->lv.gain_ceiling = ceiling;
     }
-    sp->gain_mode = mode;
+    sp->lv.gain_mode = mode;
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 

@@ -11,8 +11,7 @@
 
 #include "../../include/airwave_hip.h"
 #include "device/kernels.hpp"
-#include "device/levels.hpp"
-#include "device/limiter.hpp"
+#include "host/stage_records.hpp"
 
 namespace awr {
 
@@ -124,58 +123,42 @@ struct aw_spatializer {
     int dither = 0;                               // aw_dither
     uint64_t dither_seed = 0, dither_first_stream = 0;
     uint64_t position = 0;
-    // level meter and output gain of the four batch entries (aw_spatializer_set_metering / _set_gain; rules: device/levels.hpp).  One
-    // device allocation, made by set_metering(1) or the first set_gain that is not NONE: [n_streams] awl::Record, then [n_streams] uint32
-    // call-local peaks (zeroed at the start of every call that runs the levels kernel), then [n_streams] float FIXED gains.
-    bool metering = false;
-    int gain_mode = 0;                            // aw_gain_mode
-    float gain_ceiling = 1.0f;
-    std::vector<float> gains;                     // FIXED: one per stream
-    unsigned char *d_levels = nullptr;
-    awl::Record h_levels{};                       // what the single-stream page-locked path metered on the CPU (added to stream 0's record on read)
-    uint64_t metered_frames = 0;                  // frames metered since reset_levels (the same for every stream)
-    // what the last batch call applied, for aw_stream_levels::gain
-    int applied_mode = 0;
-    float applied_ceiling = 1.0f, applied_host_gain = 1.0f;
-    bool applied_on_host = false;                 // PEAK_CEILING: the single-stream path computed it (applied_host_gain), else the call-local peaks hold it
-    std::vector<float> applied_gains;
-    // integrated loudness of the four batch entries (aw_spatializer_set_loudness; rules: device/loudness.hpp).  One device allocation, made
-    // by set_loudness(1, max_seconds): [n_streams][2][4] double filter state, [n_streams] uint64 non-finite counts, [n_streams][loud_cap]
-    // double hop energies (those three are what a reset zeroes), then the two K-weighting sections' kernel tables.
-    bool loudness = false;
-    double sample_rate = 0.0;                     // the HRIR's
-    int64_t loud_hop = 0, loud_cap = 0;           // frames per hop (rate / 10), hops recorded per stream
-    uint64_t loud_frames = 0;                     // frames measured since the last reset (the same for every stream): fixes the hop index
-    unsigned char *d_loud = nullptr;
-    // true peak of the four batch entries (aw_spatializer_set_true_peak, AW_GAIN_TRUE_PEAK_CEILING; rules: device/truepeak.hpp).  One
-    // device allocation, made by set_true_peak(1) or set_gain(AW_GAIN_TRUE_PEAK_CEILING): [n_streams] uint64 non-finite counts,
-    // [n_streams][2] uint32 peaks, [n_streams] uint32 call-local peaks (zeroed at the start of every call that runs the kernel), then two
-    // slots of [n_streams][11][2] float history: a call reads slot tp_cur and writes the other; batch_end flips after a call that ran.
-    bool true_peak = false;
-    int tp_cur = 0;
-    bool tp_ran = false;                          // this call queued the true-peak kernel: its history slot is the next call's
-    uint64_t tp_frames = 0;                       // frames measured since the last reset (the same for every stream)
-    float tp_filter[36] = {};                     // c[p][k], built once by the setter
-    uint32_t tp_pinned_call_bits = 0;             // the single-stream page-locked path under AW_GAIN_TRUE_PEAK_CEILING: the call's true peak, read back
-    unsigned char *d_tp = nullptr;
-    // look-ahead true-peak limiter of the four batch entries (aw_spatializer_set_limiter; rules: device/limiter.hpp).  One device
-    // allocation, made by set_limiter(on): [n_streams] uint64 limited frames, [n_streams] uint64 non-finite counts, [n_streams] uint32
-    // bits of the lowest gain, then two slots of [n_streams][halo][2] float history (raw u): a call reads slot lim_cur and writes the
-    // other; batch_end flips after a call that ran.  d_lim_y is the float32 staging the convolution kernels write y into while the
-    // limiter is on (the kernel is out of place): one chunk of streams, grow-only like the other staging.
-    bool limiter = false;
-    int lim_attack = 0, lim_hold = 0;
-    float lim_ceiling = 0.0f;
-    int lim_cur = 0;
-    bool lim_ran = false;                         // this call queued the limiter kernel: its history slot is the next call's
-    uint64_t lim_frames = 0;                      // frames limited since the last reset (the same for every stream)
-    unsigned char *d_lim = nullptr;               // (made anew when attack or hold change the halo)
-    float *d_lim_y = nullptr;
-    size_t lim_y_cap = 0;
-    // the single-stream page-locked path limits on the CPU: its share of stream 0's record, and the history while it is the newer one
-    awlim::Record h_lim;
-    std::vector<float> h_lim_hist;
-    bool lim_hist_on_host = false;
+    // The output stages of the four batch entries, in pipeline order.  Each has ONE device allocation `d`, made by its setter (never on the
+    // process path) and laid out as host/stage_records.hpp states, and counts the frames it saw since the last reset (the same for every
+    // stream); `host` is what the single-stream page-locked path did on the CPU instead (added to stream 0's record on read).
+    struct Stage { unsigned char *d = nullptr; uint64_t frames = 0; };
+    struct PingPong {                                 // two history slots: a call reads slot cur and writes the other
+        int cur = 0; bool ran = false;                // ran: this call queued the stage's kernel, so its history slot is the next call's
+        void end_call(bool queued = true) { if (ran && queued) cur ^= 1; ran = false; }
+    };
+    struct Levels : Stage {                           // aw_spatializer_set_metering / _set_gain (either makes d); rules: device/levels.hpp
+        bool metering = false;
+        int gain_mode = 0; float gain_ceiling = 1.0f; // aw_gain_mode
+        std::vector<float> gains;                     // FIXED: one per stream
+        awl::Record host{};
+        // what the last batch call applied, for aw_stream_levels::gain
+        int applied_mode = 0;
+        float applied_ceiling = 1.0f, applied_host_gain = 1.0f;
+        bool applied_on_host = false;                 // PEAK_CEILING: the single-stream path computed it (applied_host_gain), else the call-local peaks hold it
+        std::vector<float> applied_gains;
+    } lv;
+    double sample_rate = 0.0;                         // the HRIR's
+    // aw_spatializer_set_loudness; rules: device/loudness.hpp.  hop: frames per hop (rate / 10); cap: hops recorded per stream; frames fixes the hop index
+    struct Loudness : Stage { bool on = false; int64_t hop = 0, cap = 0; } ld;
+    struct TruePeak : Stage {                         // aw_spatializer_set_true_peak, AW_GAIN_TRUE_PEAK_CEILING (either makes d); rules: device/truepeak.hpp
+        bool on = false; PingPong hist;
+        uint32_t pinned_call_bits = 0;                // the single-stream page-locked path under AW_GAIN_TRUE_PEAK_CEILING: the call's true peak, read back
+    } tp;
+    float tp_filter[36] = {}; bool tp_filter_built = false;      // c[p][k] of the true-peak interpolator: built by whichever of the true-peak and limiter setters runs first
+    struct Limiter : Stage {                          // aw_spatializer_set_limiter (d is made anew when attack or hold change the halo); rules: device/limiter.hpp
+        bool on = false; PingPong hist;
+        int attack = 0, hold = 0; float ceiling = 0.0f;
+        float *d_y = nullptr;                         // float32 staging the convolution kernels write y into while the limiter is on (the kernel is
+        size_t y_cap = 0;                             // out of place): one chunk of streams, grow-only like the other staging
+        awlim::Record host;
+        std::vector<float> host_hist;                 // the single-stream path's history while it is the newer one
+        bool hist_on_host = false;
+    } lim;
     int64_t host_chunk_streams = 0;               // streams per staged chunk of the last host call (0: the whole batch in one piece, serial)
     int64_t host_chunk_reserved = 0, host_reserved_frames = 0;   // aw_spatializer_reserve_host: the chunking its buffers were sized for, and up to which call length
     // what the last aw_spatializer_reserve spent where (microseconds): float64 table build on host threads, table upload (hipMalloc +

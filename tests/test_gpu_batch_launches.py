@@ -28,22 +28,23 @@ def recorded(tool, golden_dir):
 
 
 def test_the_record_covers_every_case_axis(tool, recorded):
-    assert set(recorded) == {tool.key(c) for c in tool.cases()}
+    assert set(recorded) == {tool.key(c) for c in tool.cases(later=True)}
     entry, fin, fout, state, dither, shape = (set(v) for v in zip(*recorded))
     assert entry == set(ENTRIES)
     assert {(a, b) for (_, a, b, _, _, _) in recorded} == {("f32", "f32"), ("s16", "f32"), ("f32", "s16"), ("s24", "s24"), ("f32", "s32")}
-    assert state == {"off", "meter", "gain", "ceiling"} and dither == {"none", "tpdf"}
+    assert state == {"off", "meter", "gain", "ceiling", "loudness", "true_peak", "true_peak_ceiling", "limiter"} and dither == {"none", "tpdf"}
     assert shape == {"one_piece", "chunked", "single", "planar", "planar_staged"}
     for e in ("process_pcm", "process_host_pcm"):           # the PCM entries: every format pair, state and dither on both kinds of path
-        for sh in ("one_piece", "chunked"):
-            assert len([k for k in recorded if k[0] == e and k[5] == sh]) == 5 * 4 * 2, (e, sh)
+        for sh in ("one_piece", "chunked"):                 # (the four later stages' states: without dither only)
+            assert len([k for k in recorded if k[0] == e and k[5] == sh]) == 5 * 4 * 2 + 5 * 4, (e, sh)
+            assert len([k for k in recorded if k[0] == e and k[5] == sh and k[3] in ("off", "meter", "gain", "ceiling")]) == 5 * 4 * 2, (e, sh)
     assert all(seq for seq in recorded.values())             # every call launched something
 
 
 @pytest.mark.parametrize("entry", ENTRIES)
 def test_launch_lists_are_the_recorded_ones(tool, recorded, entry):
     want = {k: v for k, v in recorded.items() if k[0] == entry}
-    got = {tool.key(r): r["launches"] for r in tool.run_all(entry=entry)}
+    got = {tool.key(r): r["launches"] for r in tool.run_all(entry=entry, later=True)}
     assert set(got) == set(want), (sorted(set(want) - set(got)), sorted(set(got) - set(want)))
     different = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
     assert not different, different

@@ -27,12 +27,14 @@ def test_no_environment_lookups_on_process_paths():
     for fn in ("sp_process_fused", "sp_process_partitioned", "sp_process_longwin", "sp_run_streams", "sp_begin_call", "aw_spatializer_process",
                "aw_spatializer_process_host", "aw_spatializer_process_planar", "aw_realtime_process", "aw_engine_process", "part_plan",
                "part_ensure_scratch", "host_chunk_streams", "host_stage_buffers", "aw_spatializer_reserve", "aw_spatializer_reserve_host",
-               "batch_args", "batch_formats", "batch_begin", "batch_chunk", "batch_run_pinned", "host_process_pinned"):
+               "batch_args", "batch_formats", "batch_begin", "batch_chunk", "batch_run_pinned", "host_process_pinned",
+               "stage_zero", "ld_begin_call"):
         assert "getenv" not in _body(rt, fn), fn
     eq = open(os.path.join(ROOT, "airwave_amd", "csrc", "eq_runtime.cpp")).read()
     assert "getenv" not in eq
     # the planner those entries call is pure: the knobs come to it as arguments
     assert "getenv" not in open(os.path.join(ROOT, "airwave_amd", "csrc", "host", "path_policy.hpp")).read()
+    assert "getenv" not in open(os.path.join(ROOT, "airwave_amd", "csrc", "host", "stage_records.hpp")).read()      # (the stages' layouts likewise)
     for f in ("kernels.hip", "march_kernels.hip", "eq_kernels.hip"):
         src = open(os.path.join(ROOT, "airwave_amd", "csrc", "device", f)).read()
         for m in re.finditer(r"getenv", src):       # only inside prepare_kernels (context creation)

@@ -5,6 +5,7 @@ frames go through the chunk loops and 6 streams of 1777 frames through the one-p
 
     python tools/batch_launches.py            # JSON: the launch lists (tests/golden/batch_launch_sequences.json is this output)
     python tools/batch_launches.py --hash     # ... plus, per case: sha256 of the output bytes, clipped count, integer fields of levels()
+                                              #     and, in the NEW_STATES, of loudness() / true_peak() / limiter() (+ sha256 of the hop energies)
 
 tests/test_gpu_batch_launches.py loads this file by path and holds the lists against the recorded ones.  Run on the GPU box."""
 import ctypes
@@ -21,7 +22,9 @@ TAPS = 300
 FORMATS = {"f32": 0, "s16": 1, "s24": 2, "s32": 3}
 PAIRS = (("f32", "f32"), ("s16", "f32"), ("f32", "s16"), ("s24", "s24"), ("f32", "s32"))
 STATES = ("off", "meter", "gain", "ceiling")
+NEW_STATES = ("loudness", "true_peak", "true_peak_ceiling", "limiter")          # the later stages: recorded without dither only
 DITHERS = ("none", "tpdf")
+LOUDNESS_SECONDS = 1.0                                                          # 10 hops of 4800 frames per stream
 # shape name -> (streams, frames, channels, reserve first)
 SHAPES = {"one_piece": (6, 1777, 8, False),           # every entry's unchunked path
           "chunked": (24, 9001, 8, False),            # 288 KB per float32 stream: 3 streams per chunk, 8 chunks (s16 input: 7 and 4)
@@ -31,19 +34,21 @@ SHAPES = {"one_piece": (6, 1777, 8, False),           # every entry's unchunked 
 KEY = ("entry", "in", "out", "state", "dither", "shape")
 
 
-def cases():
-    """Every recorded case, as dicts over KEY."""
+def cases(later=False):
+    """The recorded cases, as dicts over KEY: STATES x DITHERS — the matrix of the first recording, which a caller that knows no other
+    still gets — and, with later, NEW_STATES behind them (appended, so the earlier cases keep their lines)."""
     out = []
-    for entry, pairs, shapes in (("process", PAIRS[:1], ("one_piece", "chunked")),
-                                 ("process_host", PAIRS[:1], ("one_piece", "chunked", "single")),
-                                 ("process_pcm", PAIRS, ("one_piece", "chunked")),
-                                 ("process_host_pcm", PAIRS, ("one_piece", "chunked", "single")),
-                                 ("process_planar", PAIRS[:1], ("planar", "planar_staged"))):
-        for fin, fout in pairs:
-            for shape in shapes:
-                for state in STATES:
-                    for dither in DITHERS:
-                        out.append(dict(zip(KEY, (entry, fin, fout, state, dither, shape))))
+    for states, dithers in ((STATES, DITHERS), (NEW_STATES, DITHERS[:1]))[:2 if later else 1]:
+        for entry, pairs, shapes in (("process", PAIRS[:1], ("one_piece", "chunked")),
+                                     ("process_host", PAIRS[:1], ("one_piece", "chunked", "single")),
+                                     ("process_pcm", PAIRS, ("one_piece", "chunked")),
+                                     ("process_host_pcm", PAIRS, ("one_piece", "chunked", "single")),
+                                     ("process_planar", PAIRS[:1], ("planar", "planar_staged"))):
+            for fin, fout in pairs:
+                for shape in shapes:
+                    for state in states:
+                        for dither in dithers:
+                            out.append(dict(zip(KEY, (entry, fin, fout, state, dither, shape))))
     return out
 
 
@@ -85,8 +90,27 @@ def make_context(aw):
                 os.environ[k] = v
 
 
+def _records(sp, state, S):
+    """The order-independent fields of the later stages' records (sums that atomics add up in floating point are left out)."""
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32).ravel().tolist()
+    if state == "loudness":
+        ld = sp.loudness()
+        hops = np.stack([sp.loudness_hops(s, 0, int(round(10 * LOUDNESS_SECONDS))) for s in range(S)])
+        return {"loudness": {k: ld[k].tolist() for k in ("blocks", "blocks_above_absolute", "blocks_gated", "frames", "frames_dropped", "nonfinite")},
+                "hops_sha256": hashlib.sha256(hops.tobytes()).hexdigest()}
+    if state in ("true_peak", "true_peak_ceiling"):
+        tp = sp.true_peak()
+        return {"true_peak": {"true_peak_bits": bits(tp["true_peak"]), "call_true_peak_bits": bits(tp["call_true_peak"]),
+                              "frames": tp["frames"].tolist(), "nonfinite": tp["nonfinite"].tolist()}}
+    if state == "limiter":
+        lm = sp.limiter()
+        return {"limiter": {"min_gain_bits": bits(lm["min_gain"]), "frames": lm["frames"].tolist(),
+                            "limited_frames": lm["limited_frames"].tolist(), "nonfinite": lm["nonfinite"].tolist()}}
+    return None
+
+
 def run_case(aw, ctx, hrirs, case, want_hash=False):
-    """One call of the case on a fresh handle -> {"launches": [[name, n], ...]} (+ "sha256", "clipped", "levels" with want_hash)."""
+    """One call of the case on a fresh handle -> {"launches": [[name, n], ...]} (+ "sha256", "clipped", "levels", "records" with want_hash)."""
     from airwave_amd.api import _check
     S, F, C, reserve = SHAPES[case["shape"]]
     if C not in hrirs:
@@ -103,6 +127,15 @@ def run_case(aw, ctx, hrirs, case, want_hash=False):
         sp.set_gain("fixed", gains=np.linspace(0.3, 1.1, S).astype(np.float32))
     elif case["state"] == "ceiling":
         sp.set_gain("peak_ceiling", ceiling=0.5)
+    elif case["state"] == "loudness":
+        sp.set_loudness(True, max_seconds=LOUDNESS_SECONDS)
+    elif case["state"] == "true_peak":
+        sp.set_true_peak(True)
+    elif case["state"] == "true_peak_ceiling":
+        sp.set_gain("true_peak_ceiling", ceiling=0.5)
+    elif case["state"] == "limiter":
+        sp.set_gain("fixed", gains=np.linspace(0.3, 1.1, S).astype(np.float32))
+        sp.set_limiter(True, ceiling=0.5, attack_frames=64, hold_frames=128)
     if reserve:
         sp.reserve(F)
     x, y = _input(case["in"], S, F, C), _output(case["out"], S, F)
@@ -144,30 +177,31 @@ def run_case(aw, ctx, hrirs, case, want_hash=False):
         res["sha256"] = hashlib.sha256(np.ascontiguousarray(y).view(np.uint8).tobytes()).hexdigest()
         res["clipped"] = clipped
         res["levels"] = None
-        if case["state"] != "off":                           # (energy left out: its atomic adds have no fixed order)
+        if case["state"] in ("meter", "gain", "ceiling", "true_peak_ceiling", "limiter"):      # (energy left out: its atomic adds have no fixed order)
             lv = sp.levels()
             res["levels"] = {"peak_bits": lv["peak"].view(np.uint32).tolist(), "gain_bits": lv["gain"].view(np.uint32).tolist(),
                              "frames": lv["frames"].tolist(), "clipped": lv["clipped"].tolist(), "nonfinite": lv["nonfinite"].tolist()}
+        res["records"] = _records(sp, case["state"], S)
     return res
 
 
-def run_all(want_hash=False, entry=None):
-    """[case + result] for every case (of one entry, if named), in cases() order."""
+def run_all(want_hash=False, entry=None, later=False):
+    """[case + result] for every case (of one entry, if named; with the later stages' states, if asked), in cases() order."""
     sys.path.insert(0, ROOT) if ROOT not in sys.path else None
     import airwave_amd as aw
     ctx = make_context(aw)
     hrirs = {}
-    return [dict(c, **run_case(aw, ctx, hrirs, c, want_hash)) for c in cases() if entry in (None, c["entry"])]
+    return [dict(c, **run_case(aw, ctx, hrirs, c, want_hash)) for c in cases(later) if entry in (None, c["entry"])]
 
 
 def dumps(rows):
     """The recorded form: every distinct launch list once, then one line per case — its key, the index of its list and, from a --hash
-    run, [sha256, clipped, levels]."""
+    run, [sha256, clipped, levels] (+ the later stages' records in the NEW_STATES)."""
     seqs, lines = [], []
     for r in rows:
         if r["launches"] not in seqs:
             seqs.append(r["launches"])
-        extra = [[r["sha256"], r["clipped"], r["levels"]]] if "sha256" in r else []
+        extra = [[r["sha256"], r["clipped"], r["levels"]] + ([r["records"]] if r["records"] else [])] if "sha256" in r else []
         lines.append(json.dumps(list(key(r)) + [seqs.index(r["launches"])] + extra))
     return ('{"env": ' + json.dumps(ENV) + ', "key": ' + json.dumps(list(KEY)) + ',\n"sequences": [\n' + ",\n".join(json.dumps(s) for s in seqs) +
             '\n],\n"cases": [\n' + ",\n".join(lines) + "\n]}")
@@ -181,4 +215,4 @@ def loads(text):
 
 
 if __name__ == "__main__":
-    print(dumps(run_all("--hash" in sys.argv[1:])))
+    print(dumps(run_all("--hash" in sys.argv[1:], later=True)))
