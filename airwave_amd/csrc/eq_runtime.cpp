@@ -29,13 +29,7 @@ struct EqState {
     int n_streams = 0;
     double sample_rate = 0;
     awk::EqTables t{};
-    double *d_tables = nullptr;
-    double *d_z = nullptr;
-    size_t z_count = 0;
-    ~EqState() {
-        if (d_tables) (void)hipFree(d_tables);
-        if (d_z) (void)hipFree(d_z);
-    }
+    awr::Buf<double> d_tables, d_z;          // (neither counts in device_allocs)
 };
 using EqStatePtr = std::shared_ptr<EqState>;
 
@@ -47,6 +41,11 @@ const char *biquad_error_text(int kind) {   // BiquadCoefficientError.errorDescr
         case 4: return "Filter parameters must be finite.";
         default: return "Filter coefficients must be finite.";
     }
+}
+
+aw_status state_reset(EqState &s) {
+    AW_HIP_TRY(hipMemsetAsync(s.d_z.get(), 0, s.d_z.bytes(), s.ctx->stream));
+    return AW_OK;
 }
 
 aw_status prepare_state(aw_context *ctx, const awh::EqDefinition *def, double sample_rate, int n_streams, EqStatePtr &out) {
@@ -72,25 +71,20 @@ aw_status prepare_state(aw_context *ctx, const awh::EqDefinition *def, double sa
     st->ctx = ctx; st->n_streams = n_streams; st->sample_rate = sample_rate;
     const int K = prep.n_filters;
     const size_t n_tab = prep.tab.size(), n_pl = prep.plane.size();
-    AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&st->d_tables), std::max<size_t>(n_tab + n_pl, 1) * sizeof(double)));
+    AW_HIP_TRY(st->d_tables.alloc(std::max<size_t>(n_tab + n_pl, 1), nullptr));
     if (K > 0) {
         std::vector<double> all(prep.tab);
         all.insert(all.end(), prep.plane.begin(), prep.plane.end());
-        AW_HIP_TRY(hipMemcpy(st->d_tables, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice));
+        AW_HIP_TRY(hipMemcpy(st->d_tables.get(), all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    st->t.tab = st->d_tables;
-    st->t.plane = st->d_tables + n_tab;
+    st->t.tab = st->d_tables.get();
+    st->t.plane = st->d_tables.get() + n_tab;
     st->t.preamp = prep.preamp;
     st->t.n_filters = K;
-    st->z_count = std::max<size_t>((size_t)n_streams * K * 4, 1);
-    AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&st->d_z), st->z_count * sizeof(double)));
-    AW_HIP_TRY(hipMemsetAsync(st->d_z, 0, st->z_count * sizeof(double), ctx->stream));
+    AW_HIP_TRY(st->d_z.alloc(std::max<size_t>((size_t)n_streams * K * 4, 1), nullptr));
+    const aw_status zeroed = state_reset(*st);
+    if (zeroed != AW_OK) return zeroed;
     out = std::move(st);
-    return AW_OK;
-}
-
-aw_status state_reset(EqState &s) {
-    AW_HIP_TRY(hipMemsetAsync(s.d_z, 0, s.z_count * sizeof(double), s.ctx->stream));
     return AW_OK;
 }
 
@@ -103,7 +97,7 @@ aw_status state_process(EqState &s, const float *in, long long in_stride, float 
         in = out;
     }
     awk::EqParams p{};
-    p.z = s.d_z; p.t = s.t; p.stride_frames = out_stride;
+    p.z = s.d_z.get(); p.t = s.t; p.stride_frames = out_stride;
     p.cus = s.ctx->cfg.cus; p.ear_split = s.ctx->cfg.eq_ear_split;
     const long long body = frames - frames % awk::kEqChunk;
     if (body > 0) {
@@ -134,11 +128,10 @@ struct aw_eq {
     std::mutex target_lock, retirement_lock, reset_lock;
     EqStatePtr published, retired;
     bool reset_requested = false;
-    float *d_old = nullptr, *d_new = nullptr;   // [stream][transition_length][2] crossfade scratch (oldScratch/newScratch :137-140)
-    float *d_stage = nullptr;                   // planar host entry staging
-    float *h_pin = nullptr;                     // ... and its page-locked form for callback-sized calls: [2 F] interleaved, processed IN PLACE by the kernels over PCIe
-    size_t pin_cap = 0;                         // floats
-    size_t stage_cap = 0;
+    // (none of these counts in the context's device_allocs)
+    awr::Buf<float> d_old, d_new;               // [stream][transition_length][2] crossfade scratch (oldScratch/newScratch :137-140)
+    awr::Buf<float> d_stage;                    // planar host entry staging
+    awr::Buf<float, awr::Kind::pinned> h_pin;   // ... and its page-locked form for callback-sized calls: [2 F] interleaved, processed IN PLACE by the kernels over PCIe
 };
 
 extern "C" {
@@ -304,16 +297,14 @@ aw_status aw_eq_create(aw_context *ctx, double sample_rate, int32_t n_streams, i
     eq->active = eq->unity;
     eq->transition_length = std::max<long long>(1, (long long)std::round(sample_rate * 0.020));   // :155 (.rounded(): half away from zero)
     const size_t n = (size_t)n_streams * eq->transition_length * 2;
-    hipError_t he = hipMalloc(reinterpret_cast<void **>(&eq->d_old), n * sizeof(float));
-    if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void **>(&eq->d_new), n * sizeof(float));
+    hipError_t he = eq->d_old.alloc(n, nullptr);
+    if (he == hipSuccess) he = eq->d_new.alloc(n, nullptr);
     // the planar (plug-in) entry's staging buffer for the largest callback: process never allocates afterwards
     if (he == hipSuccess && n_streams == 1 && max_frames > 0) {
-        he = hipMalloc(reinterpret_cast<void **>(&eq->d_stage), (size_t)max_frames * 4 * sizeof(float));
-        if (he == hipSuccess) eq->stage_cap = (size_t)max_frames * 4;
-        if (he == hipSuccess) he = hipHostMalloc(reinterpret_cast<void **>(&eq->h_pin), (size_t)max_frames * 2 * sizeof(float), hipHostMallocDefault);
-        if (he == hipSuccess) eq->pin_cap = (size_t)max_frames * 2;
+        he = eq->d_stage.alloc((size_t)max_frames * 4, nullptr);
+        if (he == hipSuccess) he = eq->h_pin.alloc((size_t)max_frames * 2, nullptr);
     }
-    if (he != hipSuccess) {                      // a failed later allocation must not leak the earlier ones: destroy frees whatever exists
+    if (he != hipSuccess) {                      // (the handle goes as any other does: device current, stream idle, then its members)
         aw_eq_destroy(eq.release());
         return awr::hip_fail(he, "crossfade / staging scratch");
     }
@@ -325,10 +316,6 @@ void aw_eq_destroy(aw_eq *eq) {
     if (!eq) return;
     (void)hipSetDevice(eq->ctx->device);
     (void)hipStreamSynchronize(eq->ctx->stream);
-    if (eq->d_old) (void)hipFree(eq->d_old);
-    if (eq->d_new) (void)hipFree(eq->d_new);
-    if (eq->d_stage) (void)hipFree(eq->d_stage);
-    if (eq->h_pin) (void)hipHostFree(eq->h_pin);
     delete eq;
 }
 
@@ -451,10 +438,10 @@ aw_status aw_eq_process(aw_eq *eq, const float *in, float *out, int64_t frames) 
         if (!eq->from || !eq->to)
             return state_process(*eq->active, in + offset * 2, frames, out + offset * 2, frames, frames - offset);
         const long long seg = std::min<long long>(eq->transition_length - eq->transition_frame, frames - offset);
-        aw_status st = state_process(*eq->from, in + offset * 2, frames, eq->d_old, seg, seg);
-        if (st == AW_OK) st = state_process(*eq->to, in + offset * 2, frames, eq->d_new, seg, seg);
+        aw_status st = state_process(*eq->from, in + offset * 2, frames, eq->d_old.get(), seg, seg);
+        if (st == AW_OK) st = state_process(*eq->to, in + offset * 2, frames, eq->d_new.get(), seg, seg);
         if (st != AW_OK) return st;
-        AW_HIP_TRY(awk::launch_eq_blend(eq->d_old, eq->d_new, out + offset * 2, eq->n_streams, seg, frames, eq->transition_frame,
+        AW_HIP_TRY(awk::launch_eq_blend(eq->d_old.get(), eq->d_new.get(), out + offset * 2, eq->n_streams, seg, frames, eq->transition_frame,
                                         eq->transition_length, stream));
         eq->transition_frame += seg;
         offset += seg;
@@ -469,11 +456,11 @@ aw_status aw_eq_process_planar(aw_eq *eq, const float *in_l, const float *in_r, 
     if (frames <= 0) return frames == 0 ? AW_OK : fail(AW_ERR_INVALID_ARGUMENT, "frameCount must be >= 0");
     AW_HIP_TRY(hipSetDevice(eq->ctx->device));
     hipStream_t s = eq->ctx->stream;
-    if (eq->pin_cap >= (size_t)frames * 2) {
+    if (eq->h_pin.capacity() >= (size_t)frames * 2) {
         // the render-callback shape: interleave into the page-locked staging (left duplicated when there is no right, :68), let the
         // kernels filter it in place over PCIe, deinterleave on the way out — no copy engine, no (de)interleave kernels
         const float *r_src = in_r ? in_r : in_l;
-        float *px = eq->h_pin;
+        float *px = eq->h_pin.get();
         for (int i = 0; i < frames; ++i) { px[2 * (size_t)i] = in_l[i]; px[2 * (size_t)i + 1] = r_src[i]; }
         const aw_status st0 = aw_eq_process(eq, px, px, frames);
         if (st0 != AW_OK) return st0;
@@ -481,14 +468,8 @@ aw_status aw_eq_process_planar(aw_eq *eq, const float *in_l, const float *in_r, 
         for (int i = 0; i < frames; ++i) { out_l[i] = px[2 * (size_t)i]; out_r[i] = px[2 * (size_t)i + 1]; }
         return AW_OK;
     }
-    const size_t need = (size_t)frames * 4;   // [interleaved 2F | planar L F | planar R F]
-    if (eq->stage_cap < need) {
-        if (eq->d_stage) AW_HIP_TRY(hipFree(eq->d_stage));
-        eq->d_stage = nullptr; eq->stage_cap = 0;
-        AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&eq->d_stage), need * sizeof(float)));
-        eq->stage_cap = need;
-    }
-    float *d_x = eq->d_stage, *d_l = d_x + 2 * (size_t)frames, *d_r = d_l + frames;
+    AW_HIP_TRY(eq->d_stage.grow((size_t)frames * 4, nullptr));   // [interleaved 2F | planar L F | planar R F]
+    float *d_x = eq->d_stage.get(), *d_l = d_x + 2 * (size_t)frames, *d_r = d_l + frames;
     AW_HIP_TRY(hipMemcpyAsync(d_l, in_l, sizeof(float) * frames, hipMemcpyHostToDevice, s));
     AW_HIP_TRY(hipMemcpyAsync(d_r, in_r ? in_r : in_l, sizeof(float) * frames, hipMemcpyHostToDevice, s));   // :68
     AW_HIP_TRY(awk::launch_interleave2(d_l, d_r, d_x, frames, s));

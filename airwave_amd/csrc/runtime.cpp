@@ -153,18 +153,9 @@ aw_status caught() noexcept {
 
 using awr::fail;
 
-// Grows one of the grow-only buffers to `need` elements of T (free, then allocate; nothing happens while the capacity suffices): device
-// memory, or — PINNED — page-locked host memory.  Every allocation counts in device_allocs.
-template <bool PINNED = false, typename T>
-static aw_status sp_grow(aw_spatializer *sp, T **buf, size_t *cap, size_t need) {
-    if (*cap >= need) return AW_OK;
-    if (*buf) AW_HIP_TRY(PINNED ? hipHostFree(*buf) : hipFree(*buf));
-    *buf = nullptr; *cap = 0;
-    void *p = nullptr;
-    AW_HIP_TRY(PINNED ? hipHostMalloc(&p, need * sizeof(T), hipHostMallocDefault) : hipMalloc(&p, need * sizeof(T)));
-    *buf = static_cast<T *>(p);
-    sp->ctx->device_allocs += 1;
-    *cap = need;
+// awr::Buf::grow of one of a spatializer's grow-only buffers as a status; every such allocation counts in device_allocs.
+template <class B> static aw_status grow_buf(aw_spatializer *sp, B *buf, size_t need) {
+    AW_HIP_TRY(buf->grow(need, &sp->ctx->device_allocs));
     return AW_OK;
 }
 
@@ -234,8 +225,8 @@ static aw_status context_create_impl(int32_t device, void *ext_stream, bool use_
         if (e != hipSuccess) { c->stream = nullptr; return awr::hip_fail(e, "hipStreamCreate"); }
         c->owns_stream = true;
     }
-    hipError_t e = hipEventCreate(&c->t0);
-    if (e == hipSuccess) e = hipEventCreate(&c->t1);
+    hipError_t e = c->t0.create();
+    if (e == hipSuccess) e = c->t1.create();
     if (e == hipSuccess) e = awk::prepare_kernels(&c->cfg);
     if (e == hipSuccess) e = awk::prepare_ola_kernels();
     if (e == hipSuccess) e = awk::prepare_lw_kernels();
@@ -246,16 +237,11 @@ static aw_status context_create_impl(int32_t device, void *ext_stream, bool use_
     if (e == hipSuccess) e = awk::prepare_prep_kernels();
     awh::Twiddles tw;
     awh::build_twiddles(tw);
-    auto upload = [&](const std::vector<awk::cf> &v, awk::cf **d) -> hipError_t {
-        hipError_t r = hipMalloc(reinterpret_cast<void **>(d), v.size() * sizeof(awk::cf));
-        if (r != hipSuccess) return r;
-        return hipMemcpy(*d, v.data(), v.size() * sizeof(awk::cf), hipMemcpyHostToDevice);
-    };
-    if (e == hipSuccess) e = upload(tw.tw1, &c->d_tw1);
-    if (e == hipSuccess) e = upload(tw.twa, &c->d_twa);
-    if (e == hipSuccess) e = upload(tw.twb, &c->d_twb);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->d_zeros), 4096);
-    if (e == hipSuccess) e = hipMemset(c->d_zeros, 0, 4096);
+    if (e == hipSuccess) e = c->d_tw1.upload(tw.tw1.data(), tw.tw1.size(), nullptr, nullptr);
+    if (e == hipSuccess) e = c->d_twa.upload(tw.twa.data(), tw.twa.size(), nullptr, nullptr);
+    if (e == hipSuccess) e = c->d_twb.upload(tw.twb.data(), tw.twb.size(), nullptr, nullptr);
+    if (e == hipSuccess) e = c->d_zeros.alloc(4096 / sizeof(float), nullptr);
+    if (e == hipSuccess) e = hipMemset(c->d_zeros.get(), 0, 4096);
     if (e != hipSuccess) return awr::hip_fail(e, "context setup");
     *out = owner.release();
     return AW_OK;
@@ -269,24 +255,12 @@ aw_status aw_context_create_on_stream(int32_t device, void *hip_stream, aw_conte
 void aw_context_destroy(aw_context *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->d_tw1) (void)hipFree(c->d_tw1);
-    if (c->d_twa) (void)hipFree(c->d_twa);
-    if (c->d_twb) (void)hipFree(c->d_twb);
-    if (c->d_zeros) (void)hipFree(c->d_zeros);
-    if (c->d_pool) (void)hipFree(c->d_pool);
     delete c->copy_pool;
     delete c->copy_pool_out;
     if (c->s_h2d) (void)hipStreamDestroy(c->s_h2d);
     if (c->s_d2h) (void)hipStreamDestroy(c->s_d2h);
-    for (int i = 0; i < 2; ++i) {
-        if (c->ev_h2d[i]) (void)hipEventDestroy(c->ev_h2d[i]);
-        if (c->ev_run[i]) (void)hipEventDestroy(c->ev_run[i]);
-        if (c->ev_d2h[i]) (void)hipEventDestroy(c->ev_d2h[i]);
-    }
-    if (c->t0) (void)hipEventDestroy(c->t0);
-    if (c->t1) (void)hipEventDestroy(c->t1);
     if (c->owns_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;          // (the buffers and events: their owners' destructors)
 }
 
 aw_status aw_context_synchronize(aw_context *c) try {
@@ -305,15 +279,15 @@ void *aw_context_stream(aw_context *c) { return c ? reinterpret_cast<void *>(c->
 
 aw_status aw_context_timer_start(aw_context *c) try {
     if (!c) return fail(AW_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    AW_HIP_TRY(hipEventRecord(c->t0, c->stream));
+    AW_HIP_TRY(hipEventRecord(c->t0.get(), c->stream));
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 
 aw_status aw_context_timer_stop(aw_context *c, float *ms) try {
     if (!c || !ms) return fail(AW_ERR_INVALID_ARGUMENT, "NULL argument");
-    AW_HIP_TRY(hipEventRecord(c->t1, c->stream));
-    AW_HIP_TRY(hipEventSynchronize(c->t1));
-    AW_HIP_TRY(hipEventElapsedTime(ms, c->t0, c->t1));
+    AW_HIP_TRY(hipEventRecord(c->t1.get(), c->stream));
+    AW_HIP_TRY(hipEventSynchronize(c->t1.get()));
+    AW_HIP_TRY(hipEventElapsedTime(ms, c->t0.get(), c->t1.get()));
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 
@@ -322,23 +296,12 @@ aw_status aw_context_timer_stop(aw_context *c, float *ms) try {
 // again before the error is returned — if even that fails the pool is empty and the next process call of any handle allocates again (or
 // reports the same error).  hipFree waits for the device: launches of other handles that still read the old buffer have finished.
 static aw_status pool_grow(aw_context *c, size_t need) {
-    const size_t old = c->pool_capacity;
-    if (c->d_pool) AW_HIP_TRY(hipFree(c->d_pool));
-    c->d_pool = nullptr; c->pool_capacity = 0;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&c->d_pool), need * sizeof(awk::cf));
-    if (e != hipSuccess) {
-        c->d_pool = nullptr;
-        if (old > 0 && hipMalloc(reinterpret_cast<void **>(&c->d_pool), old * sizeof(awk::cf)) == hipSuccess) {
-            c->device_allocs += 1;
-            c->pool_capacity = old;
-        } else {
-            c->d_pool = nullptr;
-        }
-        return awr::hip_fail(e, "scratch pool");
-    }
-    c->device_allocs += 1;
-    c->pool_capacity = need;
-    return AW_OK;
+    const size_t old = c->d_pool.capacity();
+    AW_HIP_TRY(c->d_pool.reset());
+    const hipError_t e = c->d_pool.alloc(need, &c->device_allocs);
+    if (e == hipSuccess) return AW_OK;
+    if (old > 0) (void)c->d_pool.alloc(old, &c->device_allocs);
+    return awr::hip_fail(e, "scratch pool");
 }
 
 /* The context's scratch pool (runtime.hpp), sized ahead of time: a host that knows its largest batch pays the one large hipMalloc at
@@ -349,10 +312,10 @@ aw_status aw_context_reserve_scratch(aw_context *c, size_t bytes) try {
     AW_HIP_TRY(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->launch_mu);
     const size_t need = (bytes + sizeof(awk::cf) - 1) / sizeof(awk::cf);
-    if (c->pool_capacity >= need) return AW_OK;
+    if (c->d_pool.capacity() >= need) return AW_OK;
     return pool_grow(c, need);
 } AW_NOEXCEPT_TAIL
-size_t aw_context_scratch_bytes(const aw_context *c) { return c ? c->pool_capacity * sizeof(awk::cf) : 0; }
+size_t aw_context_scratch_bytes(const aw_context *c) { return c ? c->d_pool.bytes() : 0; }
 
 /* Measured ceilings of the device the context runs on ("confirm on the box and also quote a measured copy-kernel
  * ceiling"; bench.py's roofline.measured).  Own buffers, freed before returning; blocks; never on a process path. */
@@ -360,10 +323,11 @@ aw_status aw_context_bandwidth_probe(aw_context *c, size_t bytes, int32_t repeti
     if (!c || !read_gbs || !write_gbs || !copy_gbs) return fail(AW_ERR_INVALID_ARGUMENT, "NULL argument");
     if (bytes < ((size_t)64 << 20) || repetitions < 1) return fail(AW_ERR_INVALID_ARGUMENT, "probe needs >= 64 MiB and >= 1 repetition");
     AW_HIP_TRY(hipSetDevice(c->device));
-    void *a = nullptr, *b = nullptr; float *sink = nullptr;
-    hipError_t e = hipMalloc(&a, bytes);
-    if (e == hipSuccess) e = hipMalloc(&b, bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&sink), 64);
+    awr::Buf<unsigned char> buf_a, buf_b; awr::Buf<float> buf_sink;
+    hipError_t e = buf_a.alloc(bytes, nullptr);
+    if (e == hipSuccess) e = buf_b.alloc(bytes, nullptr);
+    if (e == hipSuccess) e = buf_sink.alloc(64 / sizeof(float), nullptr);
+    void *const a = buf_a.get(), *const b = buf_b.get(); float *const sink = buf_sink.get();
     // the source holds pseudo-random samples, not zeros (all-zero data draws less power and can read faster than real data does)
     if (e == hipSuccess) e = awk::launch_synth_fill(reinterpret_cast<float *>(a), 1, (long long)(bytes / sizeof(float)), 0xA17AEull, 0, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(b, 0, bytes, c->stream);
@@ -373,18 +337,15 @@ aw_status aw_context_bandwidth_probe(aw_context *c, size_t bytes, int32_t repeti
             size_t moved = 0;
             e = awk::launch_bw_probe(what, nt != 0, a, b, bytes, c->cfg.cus, sink, c->stream, &moved);       // warm-up (clocks, TLB)
             for (int r = 0; r < repetitions && e == hipSuccess; ++r) {
-                e = hipEventRecord(c->t0, c->stream);
+                e = hipEventRecord(c->t0.get(), c->stream);
                 if (e == hipSuccess) e = awk::launch_bw_probe(what, nt != 0, a, b, bytes, c->cfg.cus, sink, c->stream, &moved);
-                if (e == hipSuccess) e = hipEventRecord(c->t1, c->stream);
-                if (e == hipSuccess) e = hipEventSynchronize(c->t1);
+                if (e == hipSuccess) e = hipEventRecord(c->t1.get(), c->stream);
+                if (e == hipSuccess) e = hipEventSynchronize(c->t1.get());
                 float ms = 0.f;
-                if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->t0, c->t1);
+                if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->t0.get(), c->t1.get());
                 if (e == hipSuccess && ms > 0.f) best[what] = std::max(best[what], (double)moved / (ms * 1e-3) / 1e9);
             }
         }
-    if (a) (void)hipFree(a);
-    if (b) (void)hipFree(b);
-    if (sink) (void)hipFree(sink);
     if (e != hipSuccess) return awr::hip_fail(e, "bandwidth probe");
     *read_gbs = best[0]; *write_gbs = best[1]; *copy_gbs = best[2];
     return AW_OK;
@@ -396,12 +357,13 @@ aw_status aw_context_pcie_probe(aw_context *c, size_t bytes, int32_t repetitions
     if (!c || !h2d_gbs || !d2h_gbs || !duplex_gbs) return fail(AW_ERR_INVALID_ARGUMENT, "NULL argument");
     if (bytes < ((size_t)16 << 20) || repetitions < 1) return fail(AW_ERR_INVALID_ARGUMENT, "probe needs >= 16 MiB and >= 1 repetition");
     AW_HIP_TRY(hipSetDevice(c->device));
-    void *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
+    awr::Buf<unsigned char, awr::Kind::pinned> buf_h_in, buf_h_out; awr::Buf<unsigned char> buf_d_in, buf_d_out;
     hipStream_t s2 = nullptr;
-    hipError_t e = hipHostMalloc(&h_in, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(&h_out, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc(&d_in, bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_out, bytes);
+    hipError_t e = buf_h_in.alloc(bytes, nullptr);
+    if (e == hipSuccess) e = buf_h_out.alloc(bytes, nullptr);
+    if (e == hipSuccess) e = buf_d_in.alloc(bytes, nullptr);
+    if (e == hipSuccess) e = buf_d_out.alloc(bytes, nullptr);
+    void *const h_in = buf_h_in.get(), *const h_out = buf_h_out.get(), *const d_in = buf_d_in.get(), *const d_out = buf_d_out.get();
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
     if (e == hipSuccess) { std::memset(h_in, 0, bytes); std::memset(h_out, 0, bytes); e = hipMemsetAsync(d_out, 0, bytes, c->stream); }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -417,10 +379,6 @@ aw_status aw_context_pcie_probe(aw_context *c, size_t bytes, int32_t repetitions
             if (r > 0 && sec > 0.0) best[what] = std::max(best[what], (double)bytes * (what == 2 ? 2.0 : 1.0) / sec / 1e9);
         }
     if (s2) (void)hipStreamDestroy(s2);
-    if (h_in) (void)hipHostFree(h_in);
-    if (h_out) (void)hipHostFree(h_out);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
     if (e != hipSuccess) return awr::hip_fail(e, "pcie probe");
     *h2d_gbs = best[0]; *d2h_gbs = best[1]; *duplex_gbs = best[2];
     return AW_OK;
@@ -475,8 +433,8 @@ static aw_status sp_alloc_hist(aw_spatializer *sp) {
     // + 4 floats: whole-frame vector loads of layouts whose frames are not float4s run up to 3 floats past a frame
     const size_t n = (size_t)sp->n_streams * sp->hist_len * sp->n_channels + 4;
     for (int i = 0; i < 2; ++i) {
-        AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sp->d_hist[i]), n * sizeof(float)));
-        AW_HIP_TRY(hipMemsetAsync(sp->d_hist[i], 0, n * sizeof(float), sp->ctx->stream));
+        AW_HIP_TRY(sp->d_hist[i].alloc(n, nullptr));
+        AW_HIP_TRY(hipMemsetAsync(sp->d_hist[i].get(), 0, n * sizeof(float), sp->ctx->stream));
     }
     sp->hist_cur = 0;
     return AW_OK;
@@ -551,8 +509,8 @@ aw_status aw_spatializer_create(aw_context *ctx, const aw_hrir *hrir, int32_t n_
         sp->lw_tracks = hrir->tracks; sp->lw_n_tracks = hrir->n_tracks;
         sp->lw_left.assign(left_track, left_track + n_in); sp->lw_right.assign(right_track, right_track + n_in);
         if (n_in > 8) {                  // 32 floats for the wide split kernel's padded copy of a call's very last frame (tile_lw.hpp)
-            hipError_t et = hipMalloc(reinterpret_cast<void **>(&sp->d_tail), 32 * sizeof(float));
-            if (et == hipSuccess) et = hipMemsetAsync(sp->d_tail, 0, 32 * sizeof(float), ctx->stream);
+            hipError_t et = sp->d_tail.alloc(32, nullptr);
+            if (et == hipSuccess) et = hipMemsetAsync(sp->d_tail.get(), 0, 32 * sizeof(float), ctx->stream);
             if (et != hipSuccess) return awr::hip_fail(et, "spatializer setup");
         }
     }
@@ -587,13 +545,12 @@ aw_status aw_spatializer_create(aw_context *ctx, const aw_hrir *hrir, int32_t n_
         tables_ok = false;
     }
     if (!tables_ok) return fail(AW_ERR_OUT_OF_MEMORY, "filter tables: host memory");
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&sp->d_tab), all.size() * sizeof(awk::cf2));
-    if (e == hipSuccess) e = hipMemcpy(sp->d_tab, all.data(), all.size() * sizeof(awk::cf2), hipMemcpyHostToDevice);
+    hipError_t e = sp->d_tab.upload(all.data(), all.size(), nullptr, nullptr);
     if (e != hipSuccess) return awr::hip_fail(e, "filter tables");
     aw_status st = sp_alloc_hist(sp);
     if (st != AW_OK) return st;
-    e = hipEventCreate(&sp->k0);
-    if (e == hipSuccess) e = hipEventCreate(&sp->k1);
+    e = sp->k0.create();
+    if (e == hipSuccess) e = sp->k1.create();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return awr::hip_fail(e, "spatializer setup");
     *out = owner.release();
@@ -604,42 +561,10 @@ void aw_spatializer_destroy(aw_spatializer *sp) {
     if (!sp) return;
     (void)hipSetDevice(sp->ctx->device);
     (void)hipStreamSynchronize(sp->ctx->stream);
-    if (sp->d_tab) (void)hipFree(sp->d_tab);
-    for (int i = 0; i < 2; ++i)
-        if (sp->d_hist[i]) (void)hipFree(sp->d_hist[i]);
-    if (sp->d_tail) (void)hipFree(sp->d_tail);
-    if (sp->d_lw_tracks) (void)hipFree(sp->d_lw_tracks);
-    if (sp->d_lw_left) (void)hipFree(sp->d_lw_left);
-    if (sp->d_lw_right) (void)hipFree(sp->d_lw_right);
-    for (auto &pl : sp->lw_plans) {
-        if (pl.d_tab) (void)hipFree(pl.d_tab);
-        if (pl.d_tab16) (void)hipFree(pl.d_tab16);
-        if (pl.d_tw2) (void)hipFree(pl.d_tw2);
-        if (pl.d_coarse) (void)hipFree(pl.d_coarse);
-        if (pl.d_fine) (void)hipFree(pl.d_fine);
-        if (pl.d_tw_r) (void)hipFree(pl.d_tw_r);
-        if (pl.d_step) (void)hipFree(pl.d_step);
-        if (pl.d_tw1m) (void)hipFree(pl.d_tw1m);
-    }
-    if (sp->d_dbg) (void)hipFree(sp->d_dbg);
-    if (sp->d_stage_in) (void)hipFree(sp->d_stage_in);
-    if (sp->d_stage_out) (void)hipFree(sp->d_stage_out);
-    if (sp->h_pin_in) (void)hipHostFree(sp->h_pin_in);
-    if (sp->h_pin_out) (void)hipHostFree(sp->h_pin_out);
-    if (sp->h_bounce_in) (void)hipHostFree(sp->h_bounce_in);
-    if (sp->h_bounce_out) (void)hipHostFree(sp->h_bounce_out);
-    if (sp->d_pcm_in) (void)hipFree(sp->d_pcm_in);
-    if (sp->d_pcm_out) (void)hipFree(sp->d_pcm_out);
-    if (sp->d_clip) (void)hipFree(sp->d_clip);
-    for (unsigned char *d : {sp->lv.d, sp->ld.d, sp->tp.d, sp->lim.d})      // the output stages' records
-        if (d) (void)hipFree(d);
-    if (sp->lim.d_y) (void)hipFree(sp->lim.d_y);
-    if (sp->k0) (void)hipEventDestroy(sp->k0);
-    if (sp->k1) (void)hipEventDestroy(sp->k1);
     for (auto &pr : sp->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     for (auto &r : sp->stage_pending) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
     for (auto ev : sp->event_pool) (void)hipEventDestroy(ev);
-    delete sp;
+    delete sp;          // (every buffer and the two named events: their owners' destructors)
 }
 
 int32_t aw_spatializer_stream_count(const aw_spatializer *sp) { return sp ? sp->n_streams : 0; }
@@ -656,7 +581,7 @@ int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what) {
         case 7: return sp->last_lw_R;         // long-window path: rows R of the last call's windows (N = R x 4096); 0 = the partitioned kernels ran
         case 8: return sp->last_lw_R2;        // rows of the last call's remainder window when it ran as two groups of windows (0: one group)
         case 9: return (int64_t)sp->lw_plans.size();   // long-window table sets built so far (one per window length; reserve builds those of its plan)
-        case 6: return (int64_t)(sp->ctx->pool_capacity * sizeof(awk::cf) + (sp->stage_in_cap + sp->stage_out_cap + sp->lim.y_cap) * sizeof(float) + sp->pcm_in_cap + sp->pcm_out_cap);   // grow-only device buffers, bytes (the context's scratch pool + this handle's staging)
+        case 6: return (int64_t)(sp->ctx->d_pool.bytes() + sp->d_stage_in.bytes() + sp->d_stage_out.bytes() + sp->lim.d_y.bytes() + sp->d_pcm_in.bytes() + sp->d_pcm_out.bytes());   // grow-only device buffers, bytes (the context's scratch pool + this handle's staging)
         case 10: return sp->reserve_tables_us;    // last aw_spatializer_reserve: float64 table build on host threads, microseconds
         case 11: return sp->reserve_upload_us;    //   table upload (hipMalloc + hipMemcpy)
         case 12: return sp->reserve_scratch_us;   //   scratch pool growth (hipMalloc)
@@ -766,7 +691,7 @@ aw_status aw_spatializer_debug_stamps(aw_spatializer *sp, uint64_t *host_out, in
     if (!sp->d_dbg || words <= 0) return fail(AW_ERR_INVALID_ARGUMENT, "no launch recorded");
     if (capacity_words < words) return fail(AW_ERR_INVALID_ARGUMENT, "capacity too small");
     AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
-    AW_HIP_TRY(hipMemcpy(host_out, sp->d_dbg, (size_t)words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    AW_HIP_TRY(hipMemcpy(host_out, sp->d_dbg.get(), (size_t)words * sizeof(uint64_t), hipMemcpyDeviceToHost));
     *n_workgroups = sp->dbg_nwg;
     return AW_OK;
 #else
@@ -786,8 +711,8 @@ static void sp_fill_cfg(const aw_spatializer *sp, awk::TileParams &p) {
 // stream s_base's frames (the caller's whole batch with s_base = 0, or one staged chunk of the host-entry pipeline).
 static aw_status sp_process_fused(aw_spatializer *sp, int s_base, int ns_total, const float *in, float *out, int64_t frames) {
     awk::TileParams p{};
-    p.in = in; p.out = out; p.hist = sp->d_hist[sp->hist_cur] + (size_t)s_base * sp->hist_len * sp->n_channels;
-    p.tab = sp->d_tab; p.tw1 = sp->ctx->d_tw1; p.twa = sp->ctx->d_twa; p.twb = sp->ctx->d_twb; p.zeros = sp->ctx->d_zeros;
+    p.in = in; p.out = out; p.hist = sp->d_hist[sp->hist_cur].get() + (size_t)s_base * sp->hist_len * sp->n_channels;
+    p.tab = sp->d_tab.get(); p.tw1 = sp->ctx->d_tw1.get(); p.twa = sp->ctx->d_twa.get(); p.twb = sp->ctx->d_twb.get(); p.zeros = sp->ctx->d_zeros.get();
     p.frames = frames; p.n_channels = sp->n_channels; p.n_pairs = sp->n_pairs;
     p.hop = sp->hop; p.hist_len = sp->hist_len;
     p.tiles_per_stream = (int)((frames + sp->hop - 1) / sp->hop);
@@ -798,16 +723,11 @@ static aw_status sp_process_fused(aw_spatializer *sp, int s_base, int ns_total, 
     {
         const long long nwg = (long long)ns_total * p.tiles_per_stream;
         const size_t need = (size_t)nwg * awk::kStamps;
-        if (sp->dbg_cap < need) {
-            if (sp->d_dbg) AW_HIP_TRY(hipFree(sp->d_dbg));
-            sp->d_dbg = nullptr; sp->dbg_cap = 0;
-            AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sp->d_dbg), need * sizeof(unsigned long long)));
-            sp->ctx->device_allocs += 1;
-            sp->dbg_cap = need;
-        }
-        AW_HIP_TRY(hipMemsetAsync(sp->d_dbg, 0, need * sizeof(unsigned long long), sp->ctx->stream));
+        const aw_status st = grow_buf(sp, &sp->d_dbg, need);
+        if (st != AW_OK) return st;
+        AW_HIP_TRY(hipMemsetAsync(sp->d_dbg.get(), 0, need * sizeof(unsigned long long), sp->ctx->stream));
         sp->dbg_nwg = nwg;
-        p.dbg = sp->d_dbg;
+        p.dbg = sp->d_dbg.get();
     }
 #endif
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -873,11 +793,11 @@ static size_t part_budget(aw_spatializer *sp) {
 // The scratch is the CONTEXT's pool (runtime.hpp): grow-only, the largest need of any spatializer created on the context.
 static aw_status part_ensure_scratch(aw_spatializer *sp, size_t need) {
     aw_context *c = sp->ctx;
-    if (c->pool_capacity >= need) return AW_OK;
+    if (c->d_pool.capacity() >= need) return AW_OK;
     return pool_grow(c, need);
 }
 // the buffer a call inside what aw_spatializer_reserve() sized may count on (its stream chunk is clamped to it: never a reallocation)
-static size_t sp_held_scratch(const aw_spatializer *sp, int64_t frames) { return frames <= sp->reserved_frames ? sp->ctx->pool_capacity : 0; }
+static size_t sp_held_scratch(const aw_spatializer *sp, int64_t frames) { return frames <= sp->reserved_frames ? sp->ctx->d_pool.capacity() : 0; }
 
 static aw_status sp_process_partitioned(aw_spatializer *sp, int s_base, int ns_total, const float *in, float *out, int64_t frames) {
     const int N = awk::kN, B = sp->hop, P = sp->partitions;
@@ -886,15 +806,15 @@ static aw_status sp_process_partitioned(aw_spatializer *sp, int s_base, int ns_t
     const long long chunk = pl.chunk;
     aw_status st = part_ensure_scratch(sp, pl.need);
     if (st != AW_OK) return st;
-    awk::cf *const d_spec = sp->ctx->d_pool;
+    awk::cf *const d_spec = sp->ctx->d_pool.get();
     sp->dominant_frames = 0;
     for (long long s0 = 0; s0 < ns_total; s0 += chunk) {
         const int ns = (int)std::min<long long>(chunk, ns_total - s0);
         awk::TileParams p{};
         p.in = in + (size_t)s0 * frames * sp->n_channels;
         p.out = out + (size_t)s0 * frames * 2;
-        p.hist = sp->d_hist[sp->hist_cur] + (size_t)(s_base + s0) * sp->hist_len * sp->n_channels;
-        p.tab = sp->d_tab; p.tw1 = sp->ctx->d_tw1; p.twa = sp->ctx->d_twa; p.twb = sp->ctx->d_twb; p.zeros = sp->ctx->d_zeros;
+        p.hist = sp->d_hist[sp->hist_cur].get() + (size_t)(s_base + s0) * sp->hist_len * sp->n_channels;
+        p.tab = sp->d_tab.get(); p.tw1 = sp->ctx->d_tw1.get(); p.twa = sp->ctx->d_twa.get(); p.twb = sp->ctx->d_twb.get(); p.zeros = sp->ctx->d_zeros.get();
         p.frames = frames; p.n_channels = sp->n_channels; p.n_pairs = sp->n_pairs;
         p.hop = B; p.hist_len = sp->hist_len; p.tiles_per_stream = n_blocks;
         p.spec = d_spec; p.wspec = d_spec + pl.per_stream * (size_t)chunk;
@@ -957,60 +877,47 @@ static aw_status lw_get_plan(aw_spatializer *sp, int R, const aw_spatializer::Lw
     sp->reserve_tables_us += std::chrono::duration_cast<std::chrono::microseconds>(t_up - t_build).count();
     aw_spatializer::LwPlan pl;
     pl.R = R;
-    auto up = [&](const void *src, size_t bytes, void **d) -> hipError_t {
-        hipError_t r = hipMalloc(d, bytes);
-        if (r != hipSuccess) { *d = nullptr; return r; }
-        sp->ctx->device_allocs += 1; sp->ctx->sync_copies += 1;
-        r = hipMemcpy(*d, src, bytes, hipMemcpyHostToDevice);
-        if (r != hipSuccess) { (void)hipFree(*d); *d = nullptr; }        // a buffer that was never written is not left behind as if it had been
-        return r;
-    };
+    awr::Counter *const allocs = &sp->ctx->device_allocs, *const copies = &sp->ctx->sync_copies;
+    auto up = [&](auto &buf, const auto &host) { return buf.upload(host.data(), host.size(), allocs, copies); };
     hipError_t e = hipSuccess;
     if (on_gpu) {
         const int n_pairs = (sp->n_channels + 1) / 2;
         if (!sp->d_lw_tracks || !sp->d_lw_left || !sp->d_lw_right) {     // the impulse responses and the channel map, once per spatializer
             // all three or none: a failure part way (out of memory) frees what was uploaded, so that the next long call uploads again
             // instead of handing the prep kernel a null or never-written channel map (round-5 advice)
-            for (void **d : {reinterpret_cast<void **>(&sp->d_lw_tracks), reinterpret_cast<void **>(&sp->d_lw_left), reinterpret_cast<void **>(&sp->d_lw_right)})
-                if (*d) { (void)hipFree(*d); *d = nullptr; }
-            e = up(sp->lw_tracks.data(), sp->lw_tracks.size() * sizeof(float), reinterpret_cast<void **>(&sp->d_lw_tracks));
-            if (e == hipSuccess) e = up(sp->lw_left.data(), sp->lw_left.size() * sizeof(int32_t), reinterpret_cast<void **>(&sp->d_lw_left));
-            if (e == hipSuccess) e = up(sp->lw_right.data(), sp->lw_right.size() * sizeof(int32_t), reinterpret_cast<void **>(&sp->d_lw_right));
-            if (e != hipSuccess)
-                for (void **d : {reinterpret_cast<void **>(&sp->d_lw_tracks), reinterpret_cast<void **>(&sp->d_lw_left), reinterpret_cast<void **>(&sp->d_lw_right)})
-                    if (*d) { (void)hipFree(*d); *d = nullptr; }
+            e = up(sp->d_lw_tracks, sp->lw_tracks);
+            if (e == hipSuccess) e = up(sp->d_lw_left, sp->lw_left);
+            if (e == hipSuccess) e = up(sp->d_lw_right, sp->lw_right);
+            if (e != hipSuccess) { (void)sp->d_lw_tracks.reset(); (void)sp->d_lw_left.reset(); (void)sp->d_lw_right.reset(); }
         }
-        void *d_tmp = nullptr;
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&pl.d_tab16), (size_t)(R / 2) * n_pairs * 2 * awk::kLwM * sizeof(awk::LwTab2));
-        if (e == hipSuccess) e = hipMalloc(&d_tmp, awk::lw_prep_scratch_bytes(sp->n_channels, R));
+        awr::Buf<unsigned char> d_tmp;
+        if (e == hipSuccess) e = pl.d_tab16.alloc((size_t)(R / 2) * n_pairs * 2 * awk::kLwM, nullptr);
+        if (e == hipSuccess) e = d_tmp.alloc(awk::lw_prep_scratch_bytes(sp->n_channels, R), nullptr);
         if (e == hipSuccess) {
-            sp->ctx->device_allocs += 2;
-            e = awk::launch_lw_prep(sp->d_lw_tracks, sp->lw_n_tracks, sp->taps, sp->n_channels, sp->d_lw_left, sp->d_lw_right, R, d_tmp, pl.d_tab16, sp->ctx->stream);
+            sp->ctx->device_allocs += 2;          // (the two above, counted once both are there)
+            e = awk::launch_lw_prep(sp->d_lw_tracks.get(), sp->lw_n_tracks, sp->taps, sp->n_channels, sp->d_lw_left.get(), sp->d_lw_right.get(), R, d_tmp.get(), pl.d_tab16.get(), sp->ctx->stream);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(sp->ctx->stream);
-        if (d_tmp) (void)hipFree(d_tmp);
+        (void)d_tmp.reset();
         const auto t_gpu = std::chrono::steady_clock::now();
         sp->reserve_tables_us += std::chrono::duration_cast<std::chrono::microseconds>(t_gpu - t_up).count();
         t_up = t_gpu;
-        if (e == hipSuccess) e = up(t.tw2.data(), t.tw2.size() * sizeof(awk::cf), reinterpret_cast<void **>(&pl.d_tw2));
+        if (e == hipSuccess) e = up(pl.d_tw2, t.tw2);
     } else if (form == 16) {
-        e = up(t.tab16.data(), t.tab16.size() * sizeof(awk::LwTab2), reinterpret_cast<void **>(&pl.d_tab16));
-        if (e == hipSuccess) e = up(t.tw2.data(), t.tw2.size() * sizeof(awk::cf), reinterpret_cast<void **>(&pl.d_tw2));
+        e = up(pl.d_tab16, t.tab16);
+        if (e == hipSuccess) e = up(pl.d_tw2, t.tw2);
     } else {
-        e = up(t.tab.data(), t.tab.size() * sizeof(awk::LwTab), reinterpret_cast<void **>(&pl.d_tab));
+        e = up(pl.d_tab, t.tab);
     }
-    if (e == hipSuccess) e = up(t.coarse.data(), t.coarse.size() * sizeof(awk::cf), reinterpret_cast<void **>(&pl.d_coarse));
-    if (e == hipSuccess) e = up(t.fine.data(), t.fine.size() * sizeof(awk::cf), reinterpret_cast<void **>(&pl.d_fine));
-    if (e == hipSuccess) e = up(t.step.data(), t.step.size() * sizeof(awk::cf), reinterpret_cast<void **>(&pl.d_step));
-    if (e == hipSuccess) e = up(t.tw_r.data(), t.tw_r.size() * sizeof(awk::cf), reinterpret_cast<void **>(&pl.d_tw_r));
-    if (e == hipSuccess) e = up(t.tw1m.data(), t.tw1m.size() * sizeof(awk::cf), reinterpret_cast<void **>(&pl.d_tw1m));
-    if (e != hipSuccess) {                  // nothing half-built stays behind: the next call tries again (or takes the partitioned kernels)
-        for (void *d : {(void *)pl.d_tab, (void *)pl.d_tab16, (void *)pl.d_tw2, (void *)pl.d_coarse, (void *)pl.d_fine, (void *)pl.d_step, (void *)pl.d_tw_r, (void *)pl.d_tw1m})
-            if (d) (void)hipFree(d);
-        return awr::hip_fail(e, "long-window tables");
-    }
+    if (e == hipSuccess) e = up(pl.d_coarse, t.coarse);
+    if (e == hipSuccess) e = up(pl.d_fine, t.fine);
+    if (e == hipSuccess) e = up(pl.d_step, t.step);
+    if (e == hipSuccess) e = up(pl.d_tw_r, t.tw_r);
+    if (e == hipSuccess) e = up(pl.d_tw1m, t.tw1m);
+    // nothing half-built stays behind (pl goes out of scope): the next call tries again (or takes the partitioned kernels)
+    if (e != hipSuccess) return awr::hip_fail(e, "long-window tables");
     sp->reserve_upload_us += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_up).count();
-    sp->lw_plans.push_back(pl);
+    sp->lw_plans.push_back(std::move(pl));
     *out = &sp->lw_plans.back();
     return AW_OK;
 }
@@ -1055,7 +962,7 @@ static aw_status sp_process_longwin(aw_spatializer *sp, const LwCallPlan &call, 
     const LwScratch sc = lw_plan_scratch(sp, call, part_budget(sp), sp_held_scratch(sp, frames), per_group);
     aw_status st = part_ensure_scratch(sp, sc.need);
     if (st != AW_OK) return st;
-    awk::cf *const d_spec = sp->ctx->d_pool;
+    awk::cf *const d_spec = sp->ctx->d_pool.get();
     sp->dominant_frames = 0;
     for (long long s0 = 0; s0 < ns_total; s0 += sc.chunk) {
         const int ns = (int)std::min<long long>(sc.chunk, ns_total - s0);
@@ -1067,7 +974,7 @@ static aw_status sp_process_longwin(aw_spatializer *sp, const LwCallPlan &call, 
         SpStageTimer tm(sp);
         awk::StageTimer *tmp = sp->profiling ? &tm : nullptr;
         if (sp->n_channels > 8)          // the wide split kernel reads the last frame of the last stream from a padded copy (allocated at create)
-            AW_HIP_TRY(hipMemcpyAsync(sp->d_tail, in + ((size_t)(s0 + ns) * frames - 1) * sp->n_channels, sp->n_channels * sizeof(float),
+            AW_HIP_TRY(hipMemcpyAsync(sp->d_tail.get(), in + ((size_t)(s0 + ns) * frames - 1) * sp->n_channels, sp->n_channels * sizeof(float),
                                       hipMemcpyDefault, sp->ctx->stream));          // (`in` is device memory, or the page-locked staging of a one-stream call)
         for (int gi = 0; gi < call.n_groups; ++gi) {
             const LwGroup &g = call.g[gi];
@@ -1076,23 +983,23 @@ static aw_status sp_process_longwin(aw_spatializer *sp, const LwCallPlan &call, 
             awk::LwParams p{};
             p.in = in + (size_t)s0 * frames * sp->n_channels;
             p.out = out + (size_t)s0 * frames * 2;
-            p.hist = sp->d_hist[sp->hist_cur] + (size_t)(s_base + s0) * sp->hist_len * sp->n_channels;
+            p.hist = sp->d_hist[sp->hist_cur].get() + (size_t)(s_base + s0) * sp->hist_len * sp->n_channels;
             // the tail carry rides along in the split kernel of the LAST group: its last window spans the last hist_len frames of the call
-            p.hist_out = gi == call.n_groups - 1 ? sp->d_hist[sp->hist_cur ^ 1] + (size_t)(s_base + s0) * sp->hist_len * sp->n_channels : nullptr;
-            p.zeros = sp->ctx->d_zeros;
+            p.hist_out = gi == call.n_groups - 1 ? sp->d_hist[sp->hist_cur ^ 1].get() + (size_t)(s_base + s0) * sp->hist_len * sp->n_channels : nullptr;
+            p.zeros = sp->ctx->d_zeros.get();
             p.frames = frames; p.frame0 = g.frame0; p.frame_end = g.frame_end;
             p.n_channels = sp->n_channels; p.n_pairs = (sp->n_channels + 1) / 2; p.real_last = sp->n_channels & 1;
             p.hist_len = sp->hist_len; p.hop = (int)(N - sp->hist_len); p.n_windows = g.n_windows;
             p.R = g.R; p.N = (int)N;
             p.spec = d_spec; p.spec_per_sw = per_group[gi].spec_per_sw;
             p.wrows = d_spec + (size_t)sc.chunk * g.n_windows * per_group[gi].spec_per_sw;
-            p.tab = plan->d_tab; p.tw_coarse = plan->d_coarse; p.tw_fine = plan->d_fine; p.tw_step = plan->d_step; p.tw_r = plan->d_tw_r; p.tw1m = plan->d_tw1m;
-            p.twa = sp->ctx->d_twa; p.twb = sp->ctx->d_twb;
+            p.tab = plan->d_tab.get(); p.tw_coarse = plan->d_coarse.get(); p.tw_fine = plan->d_fine.get(); p.tw_step = plan->d_step.get(); p.tw_r = plan->d_tw_r.get(); p.tw1m = plan->d_tw1m.get();
+            p.twa = sp->ctx->d_twa.get(); p.twb = sp->ctx->d_twb.get();
             p.persistent_wgs = sp->ctx->cfg.persistent_wgs;
             p.rows_pairs_per_batch = sp->ctx->cfg.lw_rows_pb;
-            p.rows_form = plan->d_tab16 ? 16 : 8; p.tab16 = plan->d_tab16; p.tw2 = plan->d_tw2; p.rows16_wgs = sp->ctx->cfg.lw_rows16_wgs;
+            p.rows_form = plan->d_tab16 ? 16 : 8; p.tab16 = plan->d_tab16.get(); p.tw2 = plan->d_tw2.get(); p.rows16_wgs = sp->ctx->cfg.lw_rows16_wgs;
             p.n_streams = ns;
-            p.tail = sp->n_channels > 8 ? sp->d_tail : nullptr;
+            p.tail = sp->n_channels > 8 ? sp->d_tail.get() : nullptr;
             AW_HIP_TRY(awk::launch_lw_split(p, ns, sp->ctx->stream, tmp));
             AW_HIP_TRY(awk::launch_lw_rows(p, ns, sp->ctx->stream, tmp));
             AW_HIP_TRY(awk::launch_lw_merge(p, ns, sp->ctx->stream, tmp));
@@ -1110,7 +1017,7 @@ static aw_status sp_process_longwin(aw_spatializer *sp, const LwCallPlan &call, 
 // longer calls move by DMA (a fused tile reads every input line about twice: not over PCIe).
 static constexpr int64_t kZeroCopyFrames = 16384;
 static bool sp_zero_copy(const aw_spatializer *sp, int64_t frames) {
-    return sp->n_streams == 1 && frames <= kZeroCopyFrames && sp->pin_in_cap >= (size_t)frames * sp->n_channels && sp->pin_out_cap >= (size_t)frames * 2;
+    return sp->n_streams == 1 && frames <= kZeroCopyFrames && sp->h_pin_in.capacity() >= (size_t)frames * sp->n_channels && sp->h_pin_out.capacity() >= (size_t)frames * 2;
 }
 
 // The longest call of at most max_frames frames that the policy (lw_choose with every window length available) leaves to the partitioned
@@ -1177,17 +1084,17 @@ aw_status aw_spatializer_reserve(aw_spatializer *sp, int64_t max_frames) try {
     }
     if (sp->n_streams == 1) {       // plug-in shaped use (host / planar entries): their staging buffers too
         const size_t n = (size_t)max_frames * std::max(sp->n_channels, 4);
-        aw_status st = sp_grow(sp, &sp->d_stage_in, &sp->stage_in_cap, n);
-        if (st == AW_OK) st = sp_grow(sp, &sp->d_stage_out, &sp->stage_out_cap, (size_t)max_frames * 4);
+        aw_status st = grow_buf(sp, &sp->d_stage_in, n);
+        if (st == AW_OK) st = grow_buf(sp, &sp->d_stage_out, (size_t)max_frames * 4);
         // callback-sized calls: page-locked staging the kernels address directly
         const size_t zf = (size_t)std::min<int64_t>(max_frames, kZeroCopyFrames);
-        if (st == AW_OK) st = sp_grow<true>(sp, &sp->h_pin_in, &sp->pin_in_cap, zf * sp->n_channels);
-        if (st == AW_OK) st = sp_grow<true>(sp, &sp->h_pin_out, &sp->pin_out_cap, zf * 2);
+        if (st == AW_OK) st = grow_buf(sp, &sp->h_pin_in, zf * sp->n_channels);
+        if (st == AW_OK) st = grow_buf(sp, &sp->h_pin_out, zf * 2);
         if (st != AW_OK) return st;
     }
     sp->reserved_frames = std::max<int64_t>(sp->reserved_frames, max_frames);
     if (sp->lim.on) {              // the float32 staging in front of the limiter: every stream of the longest call
-        const aw_status st = sp_grow(sp, &sp->lim.d_y, &sp->lim.y_cap, (size_t)sp->n_streams * (size_t)max_frames * 2);
+        const aw_status st = grow_buf(sp, &sp->lim.d_y, (size_t)sp->n_streams * (size_t)max_frames * 2);
         if (st != AW_OK) return st;
     }
     return AW_OK;
@@ -1214,7 +1121,7 @@ static aw_status sp_run_streams(aw_spatializer *sp, const LwCallPlan &lw, int s_
     // carry the convolution tail: next call's history = last hist_len frames of (history ++ input)
     if (!lw_ran) {    // (the long-window split kernel has written it on the way)
         const size_t off = (size_t)s_base * sp->hist_len * sp->n_channels;
-        float *h_old = sp->d_hist[sp->hist_cur] + off, *h_new = sp->d_hist[sp->hist_cur ^ 1] + off;
+        float *h_old = sp->d_hist[sp->hist_cur].get() + off, *h_new = sp->d_hist[sp->hist_cur ^ 1].get() + off;
         SpStageTimer tm(sp);
         if (sp->profiling) tm.begin();
         AW_HIP_TRY(awk::launch_hist_update(in, h_old, h_new, frames, sp->n_channels, sp->hist_len, ns, sp->ctx->stream));
@@ -1240,13 +1147,12 @@ static_assert(AW_GAIN_TRUE_PEAK_CEILING == 3, "aw_gain_mode");
 static_assert(sizeof(aw_stream_levels) == 56 && sizeof(awl::Record) == 40, "aw_stream_levels");
 // Every output stage (levels lv_, loudness ld_, true peak tp_, limiter lim_) answers the same calls: its setter makes its one allocation
 // (stage_alloc: never the process path), X_begin_call runs once per call before its first launch, PingPong::end_call flips its history
-// after a call that ran, lv_reset zeroes the reset range of each, and aw_spatializer_destroy frees `d`.  Where its bytes lie: X_layout.
+// after a call that ran, lv_reset zeroes the reset range of each, and `d` (an awr::Buf) frees itself with the handle.  Where its bytes lie: X_layout.
 static awst::Levels lv_layout(const aw_spatializer *sp) { return awst::Levels{{(size_t)sp->n_streams}}; }
 static aw_status stage_zero(aw_spatializer *sp, void *p, size_t bytes) { AW_HIP_TRY(hipMemsetAsync(p, 0, bytes, sp->ctx->stream)); return AW_OK; }
-static aw_status stage_alloc(aw_spatializer *sp, unsigned char **d, size_t bytes, size_t zeroed) {       // (the first `zeroed` bytes start as zeros)
-    AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(d), bytes));
-    sp->ctx->device_allocs += 1;
-    return zeroed ? stage_zero(sp, *d, zeroed) : AW_OK;
+static aw_status stage_alloc(aw_spatializer *sp, awr::Buf<unsigned char> *d, size_t bytes, size_t zeroed) {       // (the first `zeroed` bytes start as zeros)
+    AW_HIP_TRY(d->alloc(bytes, &sp->ctx->device_allocs));
+    return zeroed ? stage_zero(sp, d->get(), zeroed) : AW_OK;
 }
 // a batch call has anything to do here; while this is false every entry launches what it always has
 static bool lv_active(const aw_spatializer *sp) { return sp->lv.metering || sp->lv.gain_mode != AW_GAIN_NONE; }
@@ -1263,7 +1169,7 @@ static aw_status lv_begin_call(aw_spatializer *sp, int64_t frames, bool device) 
     sp->lv.applied_on_host = !device;
     if (sp->lv.gain_mode == AW_GAIN_FIXED) sp->lv.applied_gains = sp->lv.gains;
     if (sp->lv.metering) sp->lv.frames += (uint64_t)frames;
-    return device && lv_measures(sp) ? stage_zero(sp, lv_layout(sp).call_peaks.at(sp->lv.d), lv_layout(sp).call_peaks.bytes()) : AW_OK;
+    return device && lv_measures(sp) ? stage_zero(sp, lv_layout(sp).call_peaks.at(sp->lv.d.get()), lv_layout(sp).call_peaks.bytes()) : AW_OK;
 }
 
 // the true-peak kernel runs (below): the measurement is on, or the gain wants the call's true peaks
@@ -1273,9 +1179,9 @@ static awst::TruePeak tp_layout(const aw_spatializer *sp) { return awst::TruePea
 // AW_GAIN_TRUE_PEAK_CEILING is the kernels' peak-ceiling gain over the call-local TRUE peaks
 static awk::PcmGain lv_gain_launch(const aw_spatializer *sp, int64_t s0) {
     const awst::Levels L = lv_layout(sp);
-    awk::PcmGain g{sp->lv.gain_mode, sp->lv.gain_ceiling, L.gains.at(sp->lv.d, s0), L.call_peaks.at(sp->lv.d, s0), sp->lv.metering ? L.records.at(sp->lv.d, s0) : nullptr};
+    awk::PcmGain g{sp->lv.gain_mode, sp->lv.gain_ceiling, L.gains.at(sp->lv.d.get(), s0), L.call_peaks.at(sp->lv.d.get(), s0), sp->lv.metering ? L.records.at(sp->lv.d.get(), s0) : nullptr};
     if (sp->lim.on) { g.mode = awl::kGainNone; g.ceiling = 0.0f; }      // (the limiter has applied the fixed gain)
-    else if (sp->lv.gain_mode == AW_GAIN_TRUE_PEAK_CEILING) { g.mode = awl::kGainPeakCeiling; g.call_peak = tp_layout(sp).call_peaks.at(sp->tp.d, s0); }
+    else if (sp->lv.gain_mode == AW_GAIN_TRUE_PEAK_CEILING) { g.mode = awl::kGainPeakCeiling; g.call_peak = tp_layout(sp).call_peaks.at(sp->tp.d.get(), s0); }
     return g;
 }
 
@@ -1288,7 +1194,7 @@ static aw_status lv_after_run(aw_spatializer *sp, float *f_out, int64_t s0, int 
         SpStageTimer tm(sp);
         if (sp->profiling) tm.begin();
         const awst::Levels L = lv_layout(sp);
-        AW_HIP_TRY(awk::launch_levels(f_out, n, frames, sp->lv.metering ? L.records.at(sp->lv.d, s0) : nullptr, L.call_peaks.at(sp->lv.d, s0), sp->ctx->stream));
+        AW_HIP_TRY(awk::launch_levels(f_out, n, frames, sp->lv.metering ? L.records.at(sp->lv.d.get(), s0) : nullptr, L.call_peaks.at(sp->lv.d.get(), s0), sp->ctx->stream));
         if (sp->profiling) tm.end("aw_levels_kernel");
     }
     if (float_out && sp->lv.gain_mode != AW_GAIN_NONE) {
@@ -1339,8 +1245,8 @@ static aw_status ld_measure(aw_spatializer *sp, const float *y, int64_t s0, int 
     if (sp->profiling) tm.begin();
     awk::LoudnessParams p{};
     const awst::Loudness L = ld_layout(sp);
-    p.z = L.state.at(sp->ld.d, s0); p.hops = L.hops.at(sp->ld.d, s0); p.nonfinite = L.nonfinite.at(sp->ld.d, s0);
-    p.tab = L.tables.at(sp->ld.d); p.plane = p.tab + kLdTabDoubles;
+    p.z = L.state.at(sp->ld.d.get(), s0); p.hops = L.hops.at(sp->ld.d.get(), s0); p.nonfinite = L.nonfinite.at(sp->ld.d.get(), s0);
+    p.tab = L.tables.at(sp->ld.d.get()); p.plane = p.tab + kLdTabDoubles;
     p.in = y; p.frames = frames; p.stride_frames = frames; p.frame0 = (long long)frame0;
     p.hop = sp->ld.hop; p.cap_hops = sp->ld.cap;
     AW_HIP_TRY(awk::launch_loudness(p, ns, sp->ctx->stream));
@@ -1358,13 +1264,13 @@ static void tp_filter_once(aw_spatializer *sp) { if (!sp->tp_filter_built) { awt
 static aw_status tp_buffers(aw_spatializer *sp) {
     const awst::TruePeak L = tp_layout(sp);
     tp_filter_once(sp);
-    return sp->tp.d ? stage_zero(sp, L.history.at(sp->tp.d), 2 * L.history.bytes()) : stage_alloc(sp, &sp->tp.d, L.total, L.total);
+    return sp->tp.d ? stage_zero(sp, L.history.at(sp->tp.d.get()), 2 * L.history.bytes()) : stage_alloc(sp, &sp->tp.d, L.total, L.total);
 }
 
 // once per call that runs the kernel, before its first launch
 static aw_status tp_begin_call(aw_spatializer *sp, int64_t frames) {
     if (sp->tp.on) sp->tp.frames += (uint64_t)frames;
-    return stage_zero(sp, tp_layout(sp).call_peaks.at(sp->tp.d), tp_layout(sp).call_peaks.bytes());
+    return stage_zero(sp, tp_layout(sp).call_peaks.at(sp->tp.d.get()), tp_layout(sp).call_peaks.bytes());
 }
 
 // The float32 output y of the streams [s0, s0 + ns) of a call (dense: `frames` apart), before any gain.  A workgroup's tile lies in one
@@ -1375,10 +1281,10 @@ static aw_status tp_measure(aw_spatializer *sp, const float *y, int64_t s0, int 
     awk::TruePeakParams p{};
     p.in = y; p.frames = frames; p.n_streams = ns;
     const awst::TruePeak L = tp_layout(sp);
-    p.hist_in = L.history.at(sp->tp.d, s0, sp->tp.hist.cur);
-    p.hist_out = L.history.at(sp->tp.d, s0, sp->tp.hist.cur ^ 1);
-    if (sp->tp.on) { p.tp_bits = L.peaks.at(sp->tp.d, s0); p.nonfinite = L.nonfinite.at(sp->tp.d, s0); }
-    p.call_tp = L.call_peaks.at(sp->tp.d, s0);
+    p.hist_in = L.history.at(sp->tp.d.get(), s0, sp->tp.hist.cur);
+    p.hist_out = L.history.at(sp->tp.d.get(), s0, sp->tp.hist.cur ^ 1);
+    if (sp->tp.on) { p.tp_bits = L.peaks.at(sp->tp.d.get(), s0); p.nonfinite = L.nonfinite.at(sp->tp.d.get(), s0); }
+    p.call_tp = L.call_peaks.at(sp->tp.d.get(), s0);
     std::memcpy(p.c, sp->tp_filter, sizeof(p.c));
     AW_HIP_TRY(awk::launch_truepeak(p, sp->ctx->stream));
     sp->tp.hist.ran = true;
@@ -1398,12 +1304,12 @@ static aw_status lim_reset(aw_spatializer *sp, bool records) {
     if (records) {
         sp->lim.frames = 0;
         sp->lim.host = awlim::Record{};
-        AW_HIP_TRY(hipMemsetAsync(sp->lim.d, 0, L.reset_bytes, sp->ctx->stream));
-        AW_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(L.min_gain.at(sp->lim.d)), (int)awlim::kOneBits, (size_t)sp->n_streams, sp->ctx->stream));
+        AW_HIP_TRY(hipMemsetAsync(sp->lim.d.get(), 0, L.reset_bytes, sp->ctx->stream));
+        AW_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(L.min_gain.at(sp->lim.d.get())), (int)awlim::kOneBits, (size_t)sp->n_streams, sp->ctx->stream));
     }
     sp->lim.host_hist.assign(L.hist_floats, 0.0f);
     sp->lim.hist_on_host = false;
-    return stage_zero(sp, L.history.at(sp->lim.d), 2 * L.history.bytes());
+    return stage_zero(sp, L.history.at(sp->lim.d.get()), 2 * L.history.bytes());
 }
 
 // once per call that runs the kernel, before its first launch: where the single-stream path ran last, its history is the newer one
@@ -1411,7 +1317,7 @@ static aw_status lim_begin_call(aw_spatializer *sp, int64_t frames) {
     sp->lim.frames += (uint64_t)frames;
     if (sp->lim.hist_on_host) {
         const awst::Limiter L = lim_layout(sp);
-        AW_HIP_TRY(hipMemcpyAsync(L.history.at(sp->lim.d, 0, sp->lim.hist.cur), sp->lim.host_hist.data(), L.hist_floats * sizeof(float), hipMemcpyHostToDevice, sp->ctx->stream));
+        AW_HIP_TRY(hipMemcpyAsync(L.history.at(sp->lim.d.get(), 0, sp->lim.hist.cur), sp->lim.host_hist.data(), L.hist_floats * sizeof(float), hipMemcpyHostToDevice, sp->ctx->stream));
         AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
         sp->lim.hist_on_host = false;
     }
@@ -1426,10 +1332,10 @@ static aw_status lim_run(aw_spatializer *sp, const float *y, float *z, int64_t s
     awk::LimiterParams p{};
     p.in = y; p.out = z; p.frames = frames; p.n_streams = ns;
     const awst::Limiter L = lim_layout(sp);
-    p.gain = sp->lv.gain_mode == AW_GAIN_FIXED ? lv_layout(sp).gains.at(sp->lv.d, s0) : nullptr;
-    p.hist_in = L.history.at(sp->lim.d, s0, sp->lim.hist.cur);
-    p.hist_out = L.history.at(sp->lim.d, s0, sp->lim.hist.cur ^ 1);
-    p.min_gain = L.min_gain.at(sp->lim.d, s0); p.limited = L.limited.at(sp->lim.d, s0); p.nonfinite = L.nonfinite.at(sp->lim.d, s0);
+    p.gain = sp->lv.gain_mode == AW_GAIN_FIXED ? lv_layout(sp).gains.at(sp->lv.d.get(), s0) : nullptr;
+    p.hist_in = L.history.at(sp->lim.d.get(), s0, sp->lim.hist.cur);
+    p.hist_out = L.history.at(sp->lim.d.get(), s0, sp->lim.hist.cur ^ 1);
+    p.min_gain = L.min_gain.at(sp->lim.d.get(), s0); p.limited = L.limited.at(sp->lim.d.get(), s0); p.nonfinite = L.nonfinite.at(sp->lim.d.get(), s0);
     p.L = sp->lim.attack; p.H = sp->lim.hold; p.ceiling = sp->lim.ceiling;
     std::memcpy(p.c, sp->tp_filter, sizeof(p.c));
     AW_HIP_TRY(awk::launch_limiter(p, sp->ctx->stream));
@@ -1444,7 +1350,7 @@ static aw_status lim_host_call(aw_spatializer *sp, float *y, int64_t frames, flo
     aw_spatializer::Limiter &lim = sp->lim;
     if (!lim.hist_on_host) {
         const awst::Limiter L = lim_layout(sp);
-        AW_HIP_TRY(hipMemcpy(lim.host_hist.data(), L.history.at(lim.d, 0, lim.hist.cur), L.hist_floats * sizeof(float), hipMemcpyDeviceToHost));
+        AW_HIP_TRY(hipMemcpy(lim.host_hist.data(), L.history.at(lim.d.get(), 0, lim.hist.cur), L.hist_floats * sizeof(float), hipMemcpyDeviceToHost));
         lim.hist_on_host = true;
     }
     lim.frames += (uint64_t)frames;
@@ -1488,13 +1394,13 @@ static aw_status host_pipeline_objects(aw_context *c) {
         c->copy_pool_out = new (std::nothrow) aw_context::CopyPool((int)std::min(4u, std::max(1u, hw / 8)));
         if (!c->copy_pool_out) return fail(AW_ERR_OUT_OF_MEMORY, "copy threads");
     }
-    // (a failure half-way leaves what exists in place: the next call makes the rest, aw_context_destroy frees whatever is there)
+    // (a failure half-way leaves what exists in place: the next call makes the rest, the context's destructor frees whatever is there)
     if (!c->s_h2d) AW_HIP_TRY(hipStreamCreateWithFlags(&c->s_h2d, hipStreamNonBlocking));
     if (!c->s_d2h) AW_HIP_TRY(hipStreamCreateWithFlags(&c->s_d2h, hipStreamNonBlocking));
     for (int i = 0; i < 2; ++i) {
-        if (!c->ev_h2d[i]) AW_HIP_TRY(hipEventCreateWithFlags(&c->ev_h2d[i], hipEventDisableTiming));
-        if (!c->ev_run[i]) AW_HIP_TRY(hipEventCreateWithFlags(&c->ev_run[i], hipEventDisableTiming));
-        if (!c->ev_d2h[i]) AW_HIP_TRY(hipEventCreateWithFlags(&c->ev_d2h[i], hipEventDisableTiming));
+        if (!c->ev_h2d[i]) AW_HIP_TRY(c->ev_h2d[i].create(hipEventDisableTiming));
+        if (!c->ev_run[i]) AW_HIP_TRY(c->ev_run[i].create(hipEventDisableTiming));
+        if (!c->ev_d2h[i]) AW_HIP_TRY(c->ev_d2h[i].create(hipEventDisableTiming));
     }
     return AW_OK;
 }
@@ -1502,8 +1408,7 @@ static aw_status host_pipeline_objects(aw_context *c) {
 // the clipped-sample counter of the host entry (made once, with the first integer output)
 static aw_status sp_clip_counter(aw_spatializer *sp) {
     if (sp->d_clip) return AW_OK;
-    AW_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sp->d_clip), sizeof(unsigned long long)));
-    sp->ctx->device_allocs += 1;
+    AW_HIP_TRY(sp->d_clip.alloc(1, &sp->ctx->device_allocs));
     return AW_OK;
 }
 
@@ -1515,13 +1420,13 @@ static aw_status host_stage_buffers(aw_spatializer *sp, int64_t frames, int64_t 
     const size_t streams = cs > 0 ? 2 * (size_t)cs : (size_t)sp->n_streams;           // two chunks in flight each way, or the whole batch
     const size_t in_n = streams * frames * sp->n_channels, out_n = streams * frames * 2;   // elements
     const size_t in_b = (size_t)awp::format_bytes(in_fmt), out_b = (size_t)awp::format_bytes(out_fmt);
-    aw_status st = sp_grow(sp, &sp->d_stage_in, &sp->stage_in_cap, in_n);
-    if (st == AW_OK) st = sp_grow(sp, &sp->d_stage_out, &sp->stage_out_cap, out_n);
-    if (st == AW_OK && host && in_fmt != AW_SAMPLE_F32) st = sp_grow(sp, &sp->d_pcm_in, &sp->pcm_in_cap, in_n * in_b);
-    if (st == AW_OK && host && out_fmt != AW_SAMPLE_F32) st = sp_grow(sp, &sp->d_pcm_out, &sp->pcm_out_cap, out_n * out_b);
+    aw_status st = grow_buf(sp, &sp->d_stage_in, in_n);
+    if (st == AW_OK) st = grow_buf(sp, &sp->d_stage_out, out_n);
+    if (st == AW_OK && host && in_fmt != AW_SAMPLE_F32) st = grow_buf(sp, &sp->d_pcm_in, in_n * in_b);
+    if (st == AW_OK && host && out_fmt != AW_SAMPLE_F32) st = grow_buf(sp, &sp->d_pcm_out, out_n * out_b);
     if (st == AW_OK && host && out_fmt != AW_SAMPLE_F32) st = sp_clip_counter(sp);
-    if (st == AW_OK && host && cs > 0 && bounce_in) st = sp_grow<true>(sp, &sp->h_bounce_in, &sp->bounce_in_cap, in_n * in_b);
-    if (st == AW_OK && host && cs > 0 && bounce_out) st = sp_grow<true>(sp, &sp->h_bounce_out, &sp->bounce_out_cap, out_n * out_b);
+    if (st == AW_OK && host && cs > 0 && bounce_in) st = grow_buf(sp, &sp->h_bounce_in, in_n * in_b);
+    if (st == AW_OK && host && cs > 0 && bounce_out) st = grow_buf(sp, &sp->h_bounce_out, out_n * out_b);
     return st;
 }
 
@@ -1659,8 +1564,8 @@ static aw_status batch_chunk(aw_spatializer *sp, const BatchCall &call, int64_t 
     const float *x = call.dec ? f_in : static_cast<const float *>(pcm_src);
     float *dst = call.enc ? f_out : static_cast<float *>(pcm_dst);
     const bool lim = call.metered && sp->lim.on;
-    if (st == AW_OK && lim) st = sp_grow(sp, &sp->lim.d_y, &sp->lim.y_cap, (size_t)ns * call.out_ps);      // (reserved for: nothing happens)
-    float *y = lim ? sp->lim.d_y : dst;
+    if (st == AW_OK && lim) st = grow_buf(sp, &sp->lim.d_y, (size_t)ns * call.out_ps);      // (reserved for: nothing happens)
+    float *y = lim ? sp->lim.d_y.get() : dst;
     if (st == AW_OK) st = sp_run_streams(sp, call.lw, (int)s0, ns, x, y, call.frames);
     if (st == AW_OK && call.metered && sp->ld.on) st = ld_measure(sp, y, s0, ns, call.frames, call.loud0);      // (before the gain)
     if (st == AW_OK && call.metered && tp_runs(sp)) st = tp_measure(sp, y, s0, ns, call.frames);                   // (the gain may read its result)
@@ -1675,17 +1580,17 @@ static aw_status batch_chunk(aw_spatializer *sp, const BatchCall &call, int64_t 
 static aw_status batch_run_pinned(aw_spatializer *sp, int64_t frames, bool metered, uint64_t *pos0) {
     const LwCallPlan lw = sp_begin_call(sp, frames, pos0);
     aw_status st = metered ? lv_begin_call(sp, frames, false) : AW_OK;
-    if (st == AW_OK) st = sp_run_streams(sp, lw, 0, 1, sp->h_pin_in, sp->h_pin_out, frames);
+    if (st == AW_OK) st = sp_run_streams(sp, lw, 0, 1, sp->h_pin_in.get(), sp->h_pin_out.get(), frames);
     if (st == AW_OK && metered && sp->ld.on)             // the loudness kernels read the page-locked output as the convolution kernels wrote it
-        st = ld_measure(sp, sp->h_pin_out, 0, 1, frames, ld_begin_call(sp, frames));
+        st = ld_measure(sp, sp->h_pin_out.get(), 0, 1, frames, ld_begin_call(sp, frames));
     const bool tp = metered && tp_runs(sp);
     if (st == AW_OK && tp) st = tp_begin_call(sp, frames);
-    if (st == AW_OK && tp) st = tp_measure(sp, sp->h_pin_out, 0, 1, frames);
+    if (st == AW_OK && tp) st = tp_measure(sp, sp->h_pin_out.get(), 0, 1, frames);
     if (st != AW_OK) { sp->tp.hist.end_call(false); return st; }       // (the limiter runs on the CPU here: lim_host_call)
     batch_end(sp);
     AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
     if (tp && sp->lv.gain_mode == AW_GAIN_TRUE_PEAK_CEILING)    // the CPU gains this call: it needs the call's true peak
-        AW_HIP_TRY(hipMemcpy(&sp->tp.pinned_call_bits, tp_layout(sp).call_peaks.at(sp->tp.d), sizeof(uint32_t), hipMemcpyDeviceToHost));
+        AW_HIP_TRY(hipMemcpy(&sp->tp.pinned_call_bits, tp_layout(sp).call_peaks.at(sp->tp.d.get()), sizeof(uint32_t), hipMemcpyDeviceToHost));
     return AW_OK;
 }
 
@@ -1710,15 +1615,16 @@ aw_status aw_spatializer_process(aw_spatializer *sp, const float *in, float *out
 static aw_status host_process_pinned(aw_spatializer *sp, const BatchCall &call, const unsigned char *in, unsigned char *out, uint64_t *clipped) {
     const int out_fmt = call.out_fmt;
     const size_t out_b = call.out_b, out_ps = call.out_ps;
-    if (call.dec) for (size_t i = 0; i < call.in_ps; ++i) sp->h_pin_in[i] = awp::decode_at(call.in_fmt, in + i * call.in_b);
-    else std::memcpy(sp->h_pin_in, in, call.in_psb);
+    float *const h_in = sp->h_pin_in.get(), *const h_out = sp->h_pin_out.get();
+    if (call.dec) for (size_t i = 0; i < call.in_ps; ++i) h_in[i] = awp::decode_at(call.in_fmt, in + i * call.in_b);
+    else std::memcpy(h_in, in, call.in_psb);
     uint64_t pos0 = 0;
     const aw_status st = batch_run_pinned(sp, call.frames, true, &pos0);
     if (st != AW_OK) return st;
     const bool lv = lv_active(sp);
-    float gain = lv ? lv_host_call(sp, sp->h_pin_out, out_ps) : 1.0f;
+    float gain = lv ? lv_host_call(sp, h_out, out_ps) : 1.0f;
     if (sp->lim.on) {                   // z replaces y in the staging; the fixed gain went in with it
-        const aw_status sl = lim_host_call(sp, sp->h_pin_out, call.frames, gain);
+        const aw_status sl = lim_host_call(sp, h_out, call.frames, gain);
         if (sl != AW_OK) return sl;
         gain = 1.0f;
     }
@@ -1728,17 +1634,17 @@ static aw_status host_process_pinned(aw_spatializer *sp, const BatchCall &call, 
         const uint64_t key = awp::dither_key(sp->dither_seed, sp->dither_first_stream);
         for (size_t i = 0; i < out_ps; ++i) {
             unsigned k = 0;
-            if (lv) awl::encode_gained_at(out_fmt, mode, sp->h_pin_out[i], gain, key, pos0 + i / 2, (int)(i & 1), out + i * out_b, &k);
-            else awp::encode_dithered_at(out_fmt, mode, sp->h_pin_out[i], key, pos0 + i / 2, (int)(i & 1), out + i * out_b, &k);
+            if (lv) awl::encode_gained_at(out_fmt, mode, h_out[i], gain, key, pos0 + i / 2, (int)(i & 1), out + i * out_b, &k);
+            else awp::encode_dithered_at(out_fmt, mode, h_out[i], key, pos0 + i / 2, (int)(i & 1), out + i * out_b, &k);
             n_clip += k;
         }
         if (sp->lv.metering) sp->lv.host.clipped += n_clip;
         if (clipped) *clipped = n_clip;
     } else if (sp->lv.gain_mode != AW_GAIN_NONE) {
         float *o = reinterpret_cast<float *>(out);
-        for (size_t i = 0; i < out_ps; ++i) o[i] = awl::apply_gain(sp->h_pin_out[i], gain);
+        for (size_t i = 0; i < out_ps; ++i) o[i] = awl::apply_gain(h_out[i], gain);
     } else {
-        std::memcpy(out, sp->h_pin_out, call.out_psb);
+        std::memcpy(out, h_out, call.out_psb);
     }
     sp->host_chunk_streams = 0;
     return AW_OK;
@@ -1762,23 +1668,24 @@ static aw_status host_process(aw_spatializer *sp, const void *in_v, int in_fmt, 
     if (st == AW_OK && cs > 0) st = host_pipeline_objects(c);
     if (st != AW_OK) return st;
     sp->host_chunk_streams = cs;
-    unsigned char *pcm_in = call.dec ? sp->d_pcm_in : reinterpret_cast<unsigned char *>(sp->d_stage_in);
-    unsigned char *pcm_out = enc ? sp->d_pcm_out : reinterpret_cast<unsigned char *>(sp->d_stage_out);
-    if ((st = batch_begin(sp, &call, enc ? sp->d_clip : nullptr, enc, true)) != AW_OK) return st;
+    float *const stage_in = sp->d_stage_in.get(), *const stage_out = sp->d_stage_out.get();
+    unsigned char *pcm_in = call.dec ? sp->d_pcm_in.get() : reinterpret_cast<unsigned char *>(stage_in);
+    unsigned char *pcm_out = enc ? sp->d_pcm_out.get() : reinterpret_cast<unsigned char *>(stage_out);
+    if ((st = batch_begin(sp, &call, enc ? sp->d_clip.get() : nullptr, enc, true)) != AW_OK) return st;
     uint64_t n_clip = 0;
     if (cs == 0) {                       // one piece: H2D -> kernels -> D2H on the context's stream
         AW_HIP_TRY(hipMemcpyAsync(pcm_in, in, in_psb * sp->n_streams, hipMemcpyHostToDevice, c->stream));
-        if ((st = batch_chunk(sp, call, 0, sp->n_streams, pcm_in, sp->d_stage_in, sp->d_stage_out, pcm_out)) != AW_OK) return st;
+        if ((st = batch_chunk(sp, call, 0, sp->n_streams, pcm_in, stage_in, stage_out, pcm_out)) != AW_OK) return st;
         batch_end(sp);
         AW_HIP_TRY(hipMemcpyAsync(out, pcm_out, out_psb * sp->n_streams, hipMemcpyDeviceToHost, c->stream));
-        if (enc) AW_HIP_TRY(hipMemcpyAsync(&n_clip, sp->d_clip, sizeof(n_clip), hipMemcpyDeviceToHost, c->stream));
+        if (enc) AW_HIP_TRY(hipMemcpyAsync(&n_clip, sp->d_clip.get(), sizeof(n_clip), hipMemcpyDeviceToHost, c->stream));
         AW_HIP_TRY(hipStreamSynchronize(c->stream));
         if (clipped) *clipped = n_clip;
         return AW_OK;
     }
     // whatever the context's stream still holds (an earlier device-buffer call of this spatializer) comes first
-    AW_HIP_TRY(hipEventRecord(c->ev_run[0], c->stream));
-    AW_HIP_TRY(hipStreamWaitEvent(c->s_h2d, c->ev_run[0], 0));
+    AW_HIP_TRY(hipEventRecord(c->ev_run[0].get(), c->stream));
+    AW_HIP_TRY(hipStreamWaitEvent(c->s_h2d, c->ev_run[0].get(), 0));
     // Pageable caller memory is bounced through page-locked chunks by the context's copy threads: the copy INTO slot k & 1 runs while the
     // DMA engines move chunk k-1, the copy OUT of chunk k-1 while the kernels of chunk k run (round 5; before: hipMemcpyAsync on the
     // pageable pointers themselves, which the HIP runtime stages on one thread).
@@ -1789,9 +1696,9 @@ static aw_status host_process(aw_spatializer *sp, const void *in_v, int in_fmt, 
     // the bounce slot is waited for before a later D2H is queued into it, and once more at the end)
     auto drain_prev = [&](int slot_prev) {
         if (!page_out || prev_s0 < 0 || he != hipSuccess) return;
-        he = hipEventSynchronize(c->ev_d2h[slot_prev]);
+        he = hipEventSynchronize(c->ev_d2h[slot_prev].get());
         if (he != hipSuccess) return;
-        unsigned char *d = out + (size_t)prev_s0 * out_psb; const unsigned char *b = sp->h_bounce_out + (size_t)slot_prev * cs * out_psb;
+        unsigned char *d = out + (size_t)prev_s0 * out_psb; const unsigned char *b = sp->h_bounce_out.get() + (size_t)slot_prev * cs * out_psb;
         const size_t n = (size_t)prev_ns * out_psb;
         if (c->cfg.host_out_async) c->copy_pool_out->start(d, b, n);
         else c->copy_pool->copy(d, b, n);            // AW_HOST_OUT_ASYNC=0 (A/B): round 5's form, on the driver thread
@@ -1799,32 +1706,32 @@ static aw_status host_process(aw_spatializer *sp, const void *in_v, int in_fmt, 
     for (int64_t s0 = 0; s0 < sp->n_streams && he == hipSuccess; s0 += cs, ++k) {
         const int ns = (int)std::min<int64_t>(cs, sp->n_streams - s0), slot = k & 1;
         unsigned char *d_in = pcm_in + (size_t)slot * cs * in_psb, *d_out = pcm_out + (size_t)slot * cs * out_psb;
-        float *f_in = sp->d_stage_in + (size_t)slot * cs * in_ps, *f_out = sp->d_stage_out + (size_t)slot * cs * out_ps;   // (float32: d_in / d_out)
+        float *f_in = stage_in + (size_t)slot * cs * in_ps, *f_out = stage_out + (size_t)slot * cs * out_ps;   // (float32: d_in / d_out)
         const unsigned char *src = in + (size_t)s0 * in_psb;
         if (page_in) {
-            unsigned char *b = sp->h_bounce_in + (size_t)slot * cs * in_psb;
-            if (k >= 2) he = hipEventSynchronize(c->ev_h2d[slot]);                              // chunk k-2's H2D has read this bounce slot
+            unsigned char *b = sp->h_bounce_in.get() + (size_t)slot * cs * in_psb;
+            if (k >= 2) he = hipEventSynchronize(c->ev_h2d[slot].get());                              // chunk k-2's H2D has read this bounce slot
             if (he != hipSuccess) break;
             c->copy_pool->copy(b, src, (size_t)ns * in_psb);
             src = b;
         }
-        if (k >= 2) he = hipStreamWaitEvent(c->s_h2d, c->ev_run[slot], 0);                      // chunk k-2's kernels have read this device slot
+        if (k >= 2) he = hipStreamWaitEvent(c->s_h2d, c->ev_run[slot].get(), 0);                      // chunk k-2's kernels have read this device slot
         if (he == hipSuccess) he = hipMemcpyAsync(d_in, src, (size_t)ns * in_psb, hipMemcpyHostToDevice, c->s_h2d);
-        if (he == hipSuccess) he = hipEventRecord(c->ev_h2d[slot], c->s_h2d);
-        if (he == hipSuccess) he = hipStreamWaitEvent(c->stream, c->ev_h2d[slot], 0);
-        if (he == hipSuccess && k >= 2) he = hipStreamWaitEvent(c->stream, c->ev_d2h[slot], 0); // chunk k-2's output has left this device slot
+        if (he == hipSuccess) he = hipEventRecord(c->ev_h2d[slot].get(), c->s_h2d);
+        if (he == hipSuccess) he = hipStreamWaitEvent(c->stream, c->ev_h2d[slot].get(), 0);
+        if (he == hipSuccess && k >= 2) he = hipStreamWaitEvent(c->stream, c->ev_d2h[slot].get(), 0); // chunk k-2's output has left this device slot
         if (he != hipSuccess) break;
         if ((st = batch_chunk(sp, call, s0, ns, d_in, f_in, f_out, d_out)) != AW_OK) break;
-        he = hipEventRecord(c->ev_run[slot], c->stream);
-        if (he == hipSuccess) he = hipStreamWaitEvent(c->s_d2h, c->ev_run[slot], 0);
+        he = hipEventRecord(c->ev_run[slot].get(), c->stream);
+        if (he == hipSuccess) he = hipStreamWaitEvent(c->s_d2h, c->ev_run[slot].get(), 0);
         if (page_out) c->copy_pool_out->wait();          // chunk k-2's copy-out has left this bounce slot (it had a whole chunk's time)
-        unsigned char *dst = page_out ? sp->h_bounce_out + (size_t)slot * cs * out_psb : out + (size_t)s0 * out_psb;
+        unsigned char *dst = page_out ? sp->h_bounce_out.get() + (size_t)slot * cs * out_psb : out + (size_t)s0 * out_psb;
         if (he == hipSuccess) he = hipMemcpyAsync(dst, d_out, (size_t)ns * out_psb, hipMemcpyDeviceToHost, c->s_d2h);
-        if (he == hipSuccess) he = hipEventRecord(c->ev_d2h[slot], c->s_d2h);
+        if (he == hipSuccess) he = hipEventRecord(c->ev_d2h[slot].get(), c->s_d2h);
         drain_prev(slot ^ 1);
         prev_s0 = s0; prev_ns = ns;
     }
-    if (enc && st == AW_OK && he == hipSuccess) he = hipMemcpyAsync(&n_clip, sp->d_clip, sizeof(n_clip), hipMemcpyDeviceToHost, c->stream);
+    if (enc && st == AW_OK && he == hipSuccess) he = hipMemcpyAsync(&n_clip, sp->d_clip.get(), sizeof(n_clip), hipMemcpyDeviceToHost, c->stream);
     const hipError_t e1 = hipStreamSynchronize(c->s_h2d), e2 = hipStreamSynchronize(c->stream), e3 = hipStreamSynchronize(c->s_d2h);
     if (page_out) c->copy_pool_out->wait();               // no copy thread outlives the call, whatever returns below
     if (st != AW_OK) return st;          // (a failed chunk: the streams are drained, the history has not been flipped)
@@ -1876,7 +1783,7 @@ aw_status aw_spatializer_process_pcm(aw_spatializer *sp, const void *in_v, aw_sa
     for (int64_t s0 = 0; s0 < sp->n_streams; s0 += cs) {
         const int ns = (int)std::min<int64_t>(cs, sp->n_streams - s0);
         const unsigned char *src = in + (size_t)s0 * call.in_psb;
-        if ((st = batch_chunk(sp, call, s0, ns, src, sp->d_stage_in, sp->d_stage_out, out + (size_t)s0 * call.out_psb)) != AW_OK) return st;
+        if ((st = batch_chunk(sp, call, s0, ns, src, sp->d_stage_in.get(), sp->d_stage_out.get(), out + (size_t)s0 * call.out_psb)) != AW_OK) return st;
     }
     batch_end(sp);
     return AW_OK;
@@ -1911,25 +1818,26 @@ aw_status aw_spatializer_process_planar(aw_spatializer *sp, const float *in_l, c
         // three kernel launches and one synchronisation per callback (round 4: four copies through the DMA engines and two more kernels).
         std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
         const float *r_src = in_r ? in_r : in_l;
-        float *pi = sp->h_pin_in;
+        float *pi = sp->h_pin_in.get();
         for (int i = 0; i < frames; ++i) { pi[2 * (size_t)i] = in_l[i]; pi[2 * (size_t)i + 1] = r_src[i]; }
         if ((st = batch_run_pinned(sp, frames, /*metered=*/false, nullptr)) != AW_OK) return st;
-        const float *po = sp->h_pin_out;
+        const float *po = sp->h_pin_out.get();
         for (int i = 0; i < frames; ++i) { out_l[i] = po[2 * (size_t)i]; out_r[i] = po[2 * (size_t)i + 1]; }
         return AW_OK;
     }
     // staging layout: [in interleaved 2F | planar L F | planar R F] and [out interleaved 2F | L F | R F]
-    st = sp_grow(sp, &sp->d_stage_in, &sp->stage_in_cap, (size_t)frames * 4);
-    if (st == AW_OK) st = sp_grow(sp, &sp->d_stage_out, &sp->stage_out_cap, (size_t)frames * 4);
+    st = grow_buf(sp, &sp->d_stage_in, (size_t)frames * 4);
+    if (st == AW_OK) st = grow_buf(sp, &sp->d_stage_out, (size_t)frames * 4);
     if (st != AW_OK) return st;
-    float *d_il = sp->d_stage_in + 2 * (size_t)frames, *d_ir = d_il + frames;
-    float *d_ol = sp->d_stage_out + 2 * (size_t)frames, *d_or = d_ol + frames;
+    float *const d_i = sp->d_stage_in.get(), *const d_o = sp->d_stage_out.get();
+    float *d_il = d_i + 2 * (size_t)frames, *d_ir = d_il + frames;
+    float *d_ol = d_o + 2 * (size_t)frames, *d_or = d_ol + frames;
     AW_HIP_TRY(hipMemcpyAsync(d_il, in_l, sizeof(float) * frames, hipMemcpyHostToDevice, s));
     AW_HIP_TRY(hipMemcpyAsync(d_ir, in_r ? in_r : in_l, sizeof(float) * frames, hipMemcpyHostToDevice, s));   // mono dup, RealtimeAudioProcessor.swift:95-107
-    AW_HIP_TRY(awk::launch_interleave2(d_il, d_ir, sp->d_stage_in, frames, s));
-    st = process_device(sp, sp->d_stage_in, sp->d_stage_out, frames, /*metered=*/false);     // (the planar entry is neither metered nor gained)
+    AW_HIP_TRY(awk::launch_interleave2(d_il, d_ir, d_i, frames, s));
+    st = process_device(sp, d_i, d_o, frames, /*metered=*/false);     // (the planar entry is neither metered nor gained)
     if (st != AW_OK) return st;
-    AW_HIP_TRY(awk::launch_deinterleave2(sp->d_stage_out, d_ol, d_or, frames, s));
+    AW_HIP_TRY(awk::launch_deinterleave2(d_o, d_ol, d_or, frames, s));
     AW_HIP_TRY(hipMemcpyAsync(out_l, d_ol, sizeof(float) * frames, hipMemcpyDeviceToHost, s));
     AW_HIP_TRY(hipMemcpyAsync(out_r, d_or, sizeof(float) * frames, hipMemcpyDeviceToHost, s));
     AW_HIP_TRY(hipStreamSynchronize(s));
@@ -1942,9 +1850,9 @@ static aw_status lv_reset(aw_spatializer *sp) {
     sp->lv.applied_mode = AW_GAIN_NONE;
     sp->lv.frames = sp->ld.frames = sp->tp.frames = 0;
     sp->tp.pinned_call_bits = 0;
-    aw_status st = sp->lv.d ? stage_zero(sp, sp->lv.d, lv_layout(sp).reset_bytes) : AW_OK;
-    if (st == AW_OK && sp->ld.d) st = stage_zero(sp, sp->ld.d, ld_layout(sp).reset_bytes);
-    if (st == AW_OK && sp->tp.d) st = stage_zero(sp, sp->tp.d, tp_layout(sp).reset_bytes);
+    aw_status st = sp->lv.d ? stage_zero(sp, sp->lv.d.get(), lv_layout(sp).reset_bytes) : AW_OK;
+    if (st == AW_OK && sp->ld.d) st = stage_zero(sp, sp->ld.d.get(), ld_layout(sp).reset_bytes);
+    if (st == AW_OK && sp->tp.d) st = stage_zero(sp, sp->tp.d.get(), tp_layout(sp).reset_bytes);
     return st == AW_OK && sp->lim.d ? lim_reset(sp, true) : st;
 }
 
@@ -1968,7 +1876,7 @@ aw_status aw_spatializer_reset(aw_spatializer *sp) try {
     AW_HIP_TRY(hipSetDevice(sp->ctx->device));
     const size_t n = (size_t)sp->n_streams * sp->hist_len * sp->n_channels;
     for (int i = 0; i < 2; ++i)
-        AW_HIP_TRY(hipMemsetAsync(sp->d_hist[i], 0, std::max<size_t>(n, 1) * sizeof(float), sp->ctx->stream));
+        AW_HIP_TRY(hipMemsetAsync(sp->d_hist[i].get(), 0, std::max<size_t>(n, 1) * sizeof(float), sp->ctx->stream));
     return lv_reset(sp);
 } AW_NOEXCEPT_TAIL
 
@@ -1992,13 +1900,13 @@ aw_status aw_spatializer_reset_levels(aw_spatializer *sp) try {
 
 aw_status aw_spatializer_get_levels(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_levels *out) try {
     std::unique_lock<std::mutex> lk;
-    aw_status st = get_begin(sp, first_stream, n, out, [](const aw_spatializer *s) { return s->lv.d; }, "no levels: neither aw_spatializer_set_metering nor aw_spatializer_set_gain has been called", &lk);
+    aw_status st = get_begin(sp, first_stream, n, out, [](const aw_spatializer *s) { return s->lv.d.get(); }, "no levels: neither aw_spatializer_set_metering nor aw_spatializer_set_gain has been called", &lk);
     if (st != AW_OK || !lk) return st;
     std::vector<awl::Record> rec;
     std::vector<uint32_t> peaks;
-    if ((st = get_field(lv_layout(sp).records, sp->lv.d, first_stream, n, &rec)) != AW_OK) return st;
-    st = sp->lv.applied_mode == AW_GAIN_TRUE_PEAK_CEILING && sp->tp.d ? get_field(tp_layout(sp).call_peaks, sp->tp.d, first_stream, n, &peaks)
-                                                                      : get_field(lv_layout(sp).call_peaks, sp->lv.d, first_stream, n, &peaks);
+    if ((st = get_field(lv_layout(sp).records, sp->lv.d.get(), first_stream, n, &rec)) != AW_OK) return st;
+    st = sp->lv.applied_mode == AW_GAIN_TRUE_PEAK_CEILING && sp->tp.d ? get_field(tp_layout(sp).call_peaks, sp->tp.d.get(), first_stream, n, &peaks)
+                                                                      : get_field(lv_layout(sp).call_peaks, sp->lv.d.get(), first_stream, n, &peaks);
     if (st != AW_OK) return st;
     for (int32_t i = 0; i < n; ++i) {
         awl::Record r = rec[(size_t)i];
@@ -2042,12 +1950,12 @@ aw_status aw_spatializer_set_loudness(aw_spatializer *sp, int32_t on, double max
             awh::eq_section_tables(awh::Biquad{kw[k][0], kw[k][1], kw[k][2], kw[k][3], kw[k][4]}, &tables[(size_t)k * awk::kEqTabDoubles],
                                    &tables[kLdTabDoubles + (size_t)k * awh::kEqSectionPlaneDoubles]);
         AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));            // whatever still reads the old records
-        if (sp->ld.d) { (void)hipFree(sp->ld.d); sp->ld.d = nullptr; sp->ld.on = false; }
+        if (sp->ld.d) { (void)sp->ld.d.reset(); sp->ld.on = false; }
         sp->ld.hop = hop; sp->ld.cap = cap; sp->ld.frames = 0;
         const awst::Loudness L = ld_layout(sp);
         const aw_status st = stage_alloc(sp, &sp->ld.d, L.total, L.reset_bytes);
         if (st != AW_OK) return st;
-        AW_HIP_TRY(hipMemcpyAsync(L.tables.at(sp->ld.d), tables.data(), tables.size() * sizeof(double), hipMemcpyHostToDevice, sp->ctx->stream));
+        AW_HIP_TRY(hipMemcpyAsync(L.tables.at(sp->ld.d.get()), tables.data(), tables.size() * sizeof(double), hipMemcpyHostToDevice, sp->ctx->stream));
         AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));            // (the upload reads `tables`)
     }
     sp->ld.on = true;
@@ -2056,7 +1964,7 @@ aw_status aw_spatializer_set_loudness(aw_spatializer *sp, int32_t on, double max
 
 aw_status aw_spatializer_get_loudness(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_loudness *out) try {
     std::unique_lock<std::mutex> lk;
-    aw_status st = get_begin(sp, first_stream, n, out, [](const aw_spatializer *s) { return s->ld.d; }, "no loudness: aw_spatializer_set_loudness has not been called", &lk);
+    aw_status st = get_begin(sp, first_stream, n, out, [](const aw_spatializer *s) { return s->ld.d.get(); }, "no loudness: aw_spatializer_set_loudness has not been called", &lk);
     if (st != AW_OK || !lk) return st;
     const awst::Loudness L = ld_layout(sp);
     const uint64_t cap_frames = (uint64_t)sp->ld.cap * (uint64_t)sp->ld.hop;
@@ -2064,8 +1972,8 @@ aw_status aw_spatializer_get_loudness(aw_spatializer *sp, int32_t first_stream, 
     std::vector<double> e((size_t)n * (size_t)std::max<int64_t>(n_hops, 1));
     std::vector<unsigned long long> nf;
     if (n_hops > 0)                                       // (the complete hops of each stream's row, not the whole field)
-        AW_HIP_TRY(hipMemcpy2D(e.data(), (size_t)n_hops * 8, L.hops.at(sp->ld.d, (size_t)first_stream), L.hops.per_stream * 8, (size_t)n_hops * 8, (size_t)n, hipMemcpyDeviceToHost));
-    if ((st = get_field(L.nonfinite, sp->ld.d, first_stream, n, &nf)) != AW_OK) return st;
+        AW_HIP_TRY(hipMemcpy2D(e.data(), (size_t)n_hops * 8, L.hops.at(sp->ld.d.get(), (size_t)first_stream), L.hops.per_stream * 8, (size_t)n_hops * 8, (size_t)n, hipMemcpyDeviceToHost));
+    if ((st = get_field(L.nonfinite, sp->ld.d.get(), first_stream, n, &nf)) != AW_OK) return st;
     for (int32_t i = 0; i < n; ++i) {
         const awlo::Gated g = awlo::gate(e.data() + (size_t)i * (size_t)n_hops, n_hops, sp->ld.hop);
         aw_stream_loudness &o = out[i];
@@ -2088,7 +1996,7 @@ aw_status aw_spatializer_get_loudness_hops(aw_spatializer *sp, int32_t stream, i
     AW_HIP_TRY(hipSetDevice(sp->ctx->device));
     std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
     AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
-    AW_HIP_TRY(hipMemcpy(out, ld_layout(sp).hops.at(sp->ld.d, (size_t)stream) + (size_t)first_hop, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    AW_HIP_TRY(hipMemcpy(out, ld_layout(sp).hops.at(sp->ld.d.get(), (size_t)stream) + (size_t)first_hop, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 
@@ -2113,13 +2021,13 @@ aw_status aw_spatializer_set_true_peak(aw_spatializer *sp, int32_t on) try {
 
 aw_status aw_spatializer_get_true_peak(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_true_peak *out) try {
     std::unique_lock<std::mutex> lk;
-    aw_status st = get_begin(sp, first_stream, n, out, [](const aw_spatializer *s) { return s->tp.d; }, "no true peak: neither aw_spatializer_set_true_peak nor AW_GAIN_TRUE_PEAK_CEILING has been used", &lk);
+    aw_status st = get_begin(sp, first_stream, n, out, [](const aw_spatializer *s) { return s->tp.d.get(); }, "no true peak: neither aw_spatializer_set_true_peak nor AW_GAIN_TRUE_PEAK_CEILING has been used", &lk);
     if (st != AW_OK || !lk) return st;
     const awst::TruePeak L = tp_layout(sp);
     std::vector<unsigned long long> nf;
     std::vector<uint32_t> pk, call;
-    if ((st = get_field(L.nonfinite, sp->tp.d, first_stream, n, &nf)) != AW_OK || (st = get_field(L.peaks, sp->tp.d, first_stream, n, &pk)) != AW_OK ||
-        (st = get_field(L.call_peaks, sp->tp.d, first_stream, n, &call)) != AW_OK) return st;
+    if ((st = get_field(L.nonfinite, sp->tp.d.get(), first_stream, n, &nf)) != AW_OK || (st = get_field(L.peaks, sp->tp.d.get(), first_stream, n, &pk)) != AW_OK ||
+        (st = get_field(L.call_peaks, sp->tp.d.get(), first_stream, n, &call)) != AW_OK) return st;
     for (int32_t i = 0; i < n; ++i) {
         aw_stream_true_peak &o = out[i];
         o.true_peak[0] = awtp::bits_float(pk[2 * (size_t)i]); o.true_peak[1] = awtp::bits_float(pk[2 * (size_t)i + 1]);
@@ -2156,15 +2064,12 @@ aw_status aw_spatializer_set_limiter(aw_spatializer *sp, int32_t on, float ceili
     if (sp->lim.on && same_shape) { sp->lim.ceiling = ceiling; return AW_OK; }
     aw_status st = AW_OK;
     const int64_t longest = std::max(sp->reserved_frames, sp->host_reserved_frames);
-    if (longest > 0 && (st = sp_grow(sp, &sp->lim.d_y, &sp->lim.y_cap, (size_t)sp->n_streams * (size_t)longest * 2)) != AW_OK) return st;
+    if (longest > 0 && (st = grow_buf(sp, &sp->lim.d_y, (size_t)sp->n_streams * (size_t)longest * 2)) != AW_OK) return st;
     if (!same_shape) {
-        unsigned char *d = nullptr;
+        awr::Buf<unsigned char> d;          // the new records are made first, then the old ones dropped
         if ((st = stage_alloc(sp, &d, awst::Limiter{{(size_t)sp->n_streams}, attack_frames, hold_frames}.total, 0)) != AW_OK) return st;
-        if (sp->lim.d) {
-            AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
-            (void)hipFree(sp->lim.d);
-        }
-        sp->lim.d = d;
+        if (sp->lim.d) AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
+        sp->lim.d = std::move(d);
         sp->lim.attack = attack_frames; sp->lim.hold = hold_frames; sp->lim.hist.cur = 0;
     }
     if ((st = lim_reset(sp, !same_shape)) != AW_OK) return st;
@@ -2176,13 +2081,13 @@ aw_status aw_spatializer_set_limiter(aw_spatializer *sp, int32_t on, float ceili
 
 aw_status aw_spatializer_get_limiter(aw_spatializer *sp, int32_t first_stream, int32_t n, aw_stream_limiter *out) try {
     std::unique_lock<std::mutex> lk;
-    aw_status st = get_begin(sp, first_stream, n, out, [](const aw_spatializer *s) { return s->lim.d; }, "no limiter: aw_spatializer_set_limiter has not been called", &lk);
+    aw_status st = get_begin(sp, first_stream, n, out, [](const aw_spatializer *s) { return s->lim.d.get(); }, "no limiter: aw_spatializer_set_limiter has not been called", &lk);
     if (st != AW_OK || !lk) return st;
     const awst::Limiter L = lim_layout(sp);
     std::vector<unsigned long long> lim, nf;
     std::vector<uint32_t> mg;
-    if ((st = get_field(L.limited, sp->lim.d, first_stream, n, &lim)) != AW_OK || (st = get_field(L.nonfinite, sp->lim.d, first_stream, n, &nf)) != AW_OK ||
-        (st = get_field(L.min_gain, sp->lim.d, first_stream, n, &mg)) != AW_OK) return st;
+    if ((st = get_field(L.limited, sp->lim.d.get(), first_stream, n, &lim)) != AW_OK || (st = get_field(L.nonfinite, sp->lim.d.get(), first_stream, n, &nf)) != AW_OK ||
+        (st = get_field(L.min_gain, sp->lim.d.get(), first_stream, n, &mg)) != AW_OK) return st;
     for (int32_t i = 0; i < n; ++i) {
         if (first_stream + i == 0) {     // the single-stream path's share (a handle of one stream)
             mg[(size_t)i] = std::min(mg[(size_t)i], sp->lim.host.min_gain_bits);
@@ -2224,7 +2129,7 @@ aw_status aw_spatializer_set_gain(aw_spatializer *sp, aw_gain_mode mode, const f
         std::vector<float> g((size_t)sp->n_streams);
         for (int32_t s = 0; s < sp->n_streams; ++s) g[(size_t)s] = gains_host[n == 1 ? 0 : s];
         // ordered behind whatever the context's stream still reads the old gains for
-        AW_HIP_TRY(hipMemcpyAsync(lv_layout(sp).gains.at(sp->lv.d), g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice, sp->ctx->stream));
+        AW_HIP_TRY(hipMemcpyAsync(lv_layout(sp).gains.at(sp->lv.d.get()), g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice, sp->ctx->stream));
         AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));
         sp->lv.gains.swap(g);
     } else {

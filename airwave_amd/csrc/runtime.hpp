@@ -11,6 +11,7 @@
 
 #include "../../include/airwave_hip.h"
 #include "device/kernels.hpp"
+#include "host/device_buf.hpp"
 #include "host/stage_records.hpp"
 
 namespace awr {
@@ -41,9 +42,9 @@ struct aw_context {
     int device = 0;
     hipStream_t stream = nullptr;
     bool owns_stream = false;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    awk::cf *d_tw1 = nullptr, *d_twa = nullptr, *d_twb = nullptr;   // twiddle rows (FFTSetupManager analogue)
-    float *d_zeros = nullptr;                                       // page of zeros (frames past the end of a call)
+    awr::Event t0, t1;
+    awr::Buf<awk::cf> d_tw1, d_twa, d_twb;                          // twiddle rows (FFTSetupManager analogue)
+    awr::Buf<float> d_zeros;                                        // page of zeros (frames past the end of a call)
     bool literal_resampler = false;                                 // aw_context_set_resampler: aw_preset_activate resamples HRIRs with the literal vgenp call
     awk::LaunchCfg cfg;                                             // device properties + tuning knobs, read once at creation
     // Scratch pool (round 5): the grow-only HBM scratch of the partitioned and long-window kernels belongs to the CONTEXT and is
@@ -51,8 +52,7 @@ struct aw_context {
     // need serves them all, and a second spatializer (a preset change: HRIRManager.activatePreset builds a new renderer network
     // while the old one still plays, HRIRManager.swift:347-446) pays no second multi-GB hipMalloc.  launch_mu keeps one call's
     // launch sequence contiguous on the stream when two owners drive two handles of one context from two threads.
-    awk::cf *d_pool = nullptr;
-    size_t pool_capacity = 0;                                       // complex elements
+    awr::Buf<awk::cf> d_pool;                                       // (capacity: complex elements)
     std::mutex launch_mu;
     std::atomic<long long> device_allocs{0};                        // hipMalloc / hipHostMalloc calls made on behalf of this context's handles (tests: a reserved process path makes none)
     std::atomic<long long> sync_copies{0};                          // blocking hipMemcpy calls likewise (table uploads)
@@ -61,7 +61,7 @@ struct aw_context {
     CopyPool *copy_pool_out = nullptr;                              // a second, smaller pool for the output direction (copy OUT of chunk k-1 beside copy IN of chunk k+1)
     CopyPool *copy_pool = nullptr;                                  // made with the pipeline objects; pageable caller buffers are bounced through page-locked chunks by it
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
-    hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_run[2] = {nullptr, nullptr}, ev_d2h[2] = {nullptr, nullptr};
+    awr::Event ev_h2d[2], ev_run[2], ev_d2h[2];
 };
 
 struct aw_hrir {
@@ -79,8 +79,8 @@ struct aw_spatializer {
     int ola_h = 0;            // path 0 on 8192-frame windows: calls with enough blocks run the overlap-add tile with blocks of 512 ola_h frames (device/tile_ola.hpp); 0: never
     int last_ola_h = 0;       // ola_h of the last call if it ran that tile, else 0
     int hop = 0, hist_len = 0, partitions = 1;
-    awk::cf2 *d_tab = nullptr;          // [partitions][pairs][N]
-    float *d_hist[2] = {nullptr, nullptr};
+    awr::Buf<awk::cf2> d_tab;           // [partitions][pairs][N]
+    awr::Buf<float> d_hist[2];
     int hist_cur = 0;
     // scratch of the partitioned / long-window kernels: the context's pool (aw_context::d_pool), grow-only; reserved_pool = what
     // aw_spatializer_reserve() asked of it for this spatializer (elements)
@@ -91,33 +91,29 @@ struct aw_spatializer {
     bool herm_ok = true;                // partitioned path, odd channel count: store/read only the non-redundant half of the last pair's spectrum
     // long-window path (device/tile_lw.hpp): chosen per call (awp::lw_choose, host/path_policy.hpp) for long calls of a path-1 spatializer and, past a measured HRIR length,
     // of a path-0 one; tables per window length, built on first use (aw_spatializer_reserve builds those of the plan its max_frames implies)
-    struct LwPlan { int R = 0; awk::LwTab *d_tab = nullptr; awk::LwTab2 *d_tab16 = nullptr; awk::cf *d_tw2 = nullptr; awk::cf *d_coarse = nullptr, *d_fine = nullptr, *d_step = nullptr, *d_tw_r = nullptr, *d_tw1m = nullptr; };
+    struct LwPlan { int R = 0; awr::Buf<awk::LwTab> d_tab; awr::Buf<awk::LwTab2> d_tab16; awr::Buf<awk::cf> d_tw2, d_coarse, d_fine, d_step, d_tw_r, d_tw1m; };      // (move-only)
     std::vector<LwPlan> lw_plans;
     int lw_mode = -1;                   // AW_LW at create: -1 automatic (cost model), 0 never, 32/64/128 force that R where it fits
     std::vector<float> lw_tracks;       // the HRIR and channel map, kept for the lazily built tables
     std::vector<int32_t> lw_left, lw_right;
     int lw_n_tracks = 0;
-    float *d_lw_tracks = nullptr;       // device copies of the same for the prep kernels (device/prep_kernels.hip), made with the first table set
-    int32_t *d_lw_left = nullptr, *d_lw_right = nullptr;
-    float *d_tail = nullptr;            // 32 floats: the last frame of the last stream of a call + zeros (wide split kernel, tile_lw.hpp)
+    awr::Buf<float> d_lw_tracks;        // device copies of the same for the prep kernels (device/prep_kernels.hip), made with the first table set
+    awr::Buf<int32_t> d_lw_left, d_lw_right;
+    awr::Buf<float> d_tail;             // 32 floats: the last frame of the last stream of a call + zeros (wide split kernel, tile_lw.hpp)
     int last_lw_R = 0;                  // R of the last call's (first group of) windows (0: the partitioned kernels ran)
     int last_lw_R2 = 0;                 // R of its remainder window when the call ran as two groups
     int64_t reserved_frames = 0;        // aw_spatializer_reserve(): buffers are sized for calls up to this many frames
     // host-entry staging (grow-only; a multi-stream batch is staged in two chunks of streams each way: aw_spatializer_process_host)
-    float *d_stage_in = nullptr, *d_stage_out = nullptr;
-    size_t stage_in_cap = 0, stage_out_cap = 0;   // floats
+    awr::Buf<float> d_stage_in, d_stage_out;
     // one-stream, callback-sized calls (aw_spatializer_process_planar, aw_engine_*, aw_realtime_*): page-locked staging that the kernels read
     // and write DIRECTLY over PCIe — no copy engine, no (de)interleave kernels: the caller's samples are (de)interleaved by the CPU on the way
-    float *h_pin_in = nullptr, *h_pin_out = nullptr;
-    size_t pin_in_cap = 0, pin_out_cap = 0;       // floats
+    awr::Buf<float, awr::Kind::pinned> h_pin_in, h_pin_out;
     // multi-stream host entry on PAGEABLE caller buffers: page-locked bounce chunks (two each way), filled / drained by the context's copy threads
-    unsigned char *h_bounce_in = nullptr, *h_bounce_out = nullptr;
-    size_t bounce_in_cap = 0, bounce_out_cap = 0; // bytes (both slots)
+    awr::Buf<unsigned char, awr::Kind::pinned> h_bounce_in, h_bounce_out;       // (both slots each)
     // integer PCM entries (aw_spatializer_process_pcm / _process_host_pcm): the host entry's device PCM slots (two chunks each way; the
     // float32 formats use d_stage_in / d_stage_out themselves) and the device counter of its clipped samples
-    unsigned char *d_pcm_in = nullptr, *d_pcm_out = nullptr;
-    size_t pcm_in_cap = 0, pcm_out_cap = 0;       // bytes
-    unsigned long long *d_clip = nullptr;
+    awr::Buf<unsigned char> d_pcm_in, d_pcm_out;
+    awr::Buf<unsigned long long> d_clip;
     // dither of the s16 / s24 encode (aw_spatializer_set_dither) and the frame position that keys it: frames processed since create /
     // reset, advanced once per call by sp_begin_call (aw_spatializer_info 18)
     int dither = 0;                               // aw_dither
@@ -126,7 +122,7 @@ struct aw_spatializer {
     // The output stages of the four batch entries, in pipeline order.  Each has ONE device allocation `d`, made by its setter (never on the
     // process path) and laid out as host/stage_records.hpp states, and counts the frames it saw since the last reset (the same for every
     // stream); `host` is what the single-stream page-locked path did on the CPU instead (added to stream 0's record on read).
-    struct Stage { unsigned char *d = nullptr; uint64_t frames = 0; };
+    struct Stage { awr::Buf<unsigned char> d; uint64_t frames = 0; };
     struct PingPong {                                 // two history slots: a call reads slot cur and writes the other
         int cur = 0; bool ran = false;                // ran: this call queued the stage's kernel, so its history slot is the next call's
         void end_call(bool queued = true) { if (ran && queued) cur ^= 1; ran = false; }
@@ -153,8 +149,8 @@ struct aw_spatializer {
     struct Limiter : Stage {                          // aw_spatializer_set_limiter (d is made anew when attack or hold change the halo); rules: device/limiter.hpp
         bool on = false; PingPong hist;
         int attack = 0, hold = 0; float ceiling = 0.0f;
-        float *d_y = nullptr;                         // float32 staging the convolution kernels write y into while the limiter is on (the kernel is
-        size_t y_cap = 0;                             // out of place): one chunk of streams, grow-only like the other staging
+        awr::Buf<float> d_y;                          // float32 staging the convolution kernels write y into while the limiter is on (the kernel is
+                                                      // out of place): one chunk of streams, grow-only like the other staging
         awlim::Record host;
         std::vector<float> host_hist;                 // the single-stream path's history while it is the newer one
         bool hist_on_host = false;
@@ -164,12 +160,11 @@ struct aw_spatializer {
     // what the last aw_spatializer_reserve spent where (microseconds): float64 table build on host threads, table upload (hipMalloc +
     // hipMemcpy), scratch pool growth (hipMalloc) — bench.py's config.activation
     int64_t reserve_tables_us = 0, reserve_upload_us = 0, reserve_scratch_us = 0;
-    unsigned long long *d_dbg = nullptr;   // AW_STAMPS diagnostic builds only
-    size_t dbg_cap = 0;                     // words
+    awr::Buf<unsigned long long> d_dbg;    // AW_STAMPS diagnostic builds only (capacity: words)
     long long dbg_nwg = 0;
     // profiling of the dominant kernel
     bool profiling = false;
-    hipEvent_t k0 = nullptr, k1 = nullptr;
+    awr::Event k0, k1;
     double kernel_ms_sum = 0.0;
     int kernel_launches = 0;
     long long dominant_frames = 0;         // output frames produced by the timed (dominant) launch of the last call

@@ -294,3 +294,42 @@ def test_capacity_reset_and_nonfinite():
     holed = ~np.isfinite(yn).all(axis=2)[:, : 15 * (RATE // 10)].reshape(2, 15, RATE // 10).all(axis=2)
     assert holed[0].any() and not holed[0, -5:].any() and not holed[1].any()
     check_against_reference(ld, all_hops(sp, 15), want_hops, RATE, "NaN frame", skip=holed)
+
+
+# ---- 6. another capacity on a live handle ------------------------------------------------------------------------------------------------
+
+def test_another_capacity_on_a_live_handle_makes_new_empty_records(oracle):
+    """aw_spatializer_set_loudness with another max_seconds on a handle that has measured: the stream goes idle, the old records are
+    freed, new ones of the new capacity are made, and the measurement starts over (filter state and frame count too)."""
+    import torch
+    import airwave_amd as aw
+    ctx = context(aw, torch)
+    rate, hop = 10000, 1000
+    h = oracle.synth_hrir(2, 64, seed=57)
+    lt, rt = np.array([0, 1], np.int32), np.array([1, 0], np.int32)
+    sp = aw.Spatializer(aw.HRIR(h, sample_rate=float(rate), ctx=ctx), lt, rt, n_streams=2, ctx=ctx)
+    x = np.random.default_rng(57).uniform(-0.5, 0.5, (2, 4000, 2)).astype(np.float32)
+    allocs = sp.info()["device_allocs"]
+    sp.set_loudness(True, 0.1)                                         # one hop per stream
+    y1 = host_call(sp, x[:, :1000])
+    want1, _ = reference_hops(y1, rate)
+    assert want1.shape == (2, 1) and np.all(sp.loudness()["frames"] == 1000)
+    check_against_reference(sp.loudness(), all_hops(sp, 1), want1, rate, "capacity of one hop")
+    with pytest.raises(aw.AirwaveError):
+        sp.loudness_hops(0, 0, 2)
+    sp.set_loudness(True, 0.5)                                         # five hops: new records, nothing measured yet
+    assert sp.info()["loudness"] == 1 and not sp.loudness()["frames"].any() and not all_hops(sp, 5).any()
+    y2 = host_call(sp, x[:, 1000:])
+    want2, _ = reference_hops(y2, rate)                                # (from silent filters: the state started over with the records)
+    ld = sp.loudness()
+    assert want2.shape == (2, 3) and np.all(ld["frames"] == 3000) and not ld["frames_dropped"].any() and not ld["nonfinite"].any()
+    check_against_reference(ld, all_hops(sp, 5), want2, rate, "capacity of five hops")
+    assert not all_hops(sp, 5)[:, 3:].any()
+    y = np.concatenate([y1, y2], axis=1)
+    for s in range(2):
+        assert oracle.peak_rel_error(y[s], oracle.spatialize_f64(x[s], h, lt, rt)) < 1e-5
+    delta = sp.info()["device_allocs"] - allocs
+    print(f"device allocations of the sequence: {delta}")
+    # Measured once on the library as it was before the buffers got an owning type (not derived from the new code): the records twice,
+    # the float staging in and out for 1000 frames and again for 3000.
+    assert delta == 6
