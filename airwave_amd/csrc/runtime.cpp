@@ -241,7 +241,7 @@ static aw_status context_create_impl(int32_t device, void *ext_stream, bool use_
     if (e == hipSuccess) e = c->d_twa.upload(tw.twa.data(), tw.twa.size(), nullptr, nullptr);
     if (e == hipSuccess) e = c->d_twb.upload(tw.twb.data(), tw.twb.size(), nullptr, nullptr);
     if (e == hipSuccess) e = c->d_zeros.alloc(4096 / sizeof(float), nullptr);
-    if (e == hipSuccess) e = hipMemset(c->d_zeros.get(), 0, 4096);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_zeros.get(), 0, 4096, c->stream);      // (ordered on the stream its readers, the tile kernels, run on)
     if (e != hipSuccess) return awr::hip_fail(e, "context setup");
     *out = owner.release();
     return AW_OK;

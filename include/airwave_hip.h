@@ -71,6 +71,20 @@ typedef struct aw_context aw_context;
 AW_API aw_status aw_context_create(int32_t device_ordinal, aw_context **out);
 /* Same, but launches on a caller-owned hipStream_t (e.g. torch.cuda.current_stream().cuda_stream). */
 AW_API aw_status aw_context_create_on_stream(int32_t device_ordinal, void *hip_stream, aw_context **out);
+/* Stream order (tests/test_gpu_stream_order.py, tests/test_stream_order_contract.py).  Every kernel, memset and copy of the device-buffer
+ * entries is queued on the context's stream — the caller's, or the one aw_context_stream returns, on which a caller may queue work of its
+ * own — so a producer queued there before a call and a consumer queued there after it need no host synchronisation, on a non-blocking
+ * side stream as on the legacy default stream.
+ *  - these only enqueue and return while earlier work on the stream is still running: aw_spatializer_process and _process_pcm on a
+ *    reserved handle (every kernel path and every output stage), aw_spatializer_reset, aw_eq_state_process, aw_eq_process, aw_synth_fill.
+ *    Handles of one context, and contexts on different streams, may be interleaved from one host thread; work of one context never waits
+ *    behind another context's stream.
+ *  - these synchronise the context's stream before they return, because the host reads or hands over memory then: aw_memcpy_h2d /
+ *    aw_memcpy_d2h, the record getters (aw_spatializer_get_levels read on a busy stream returns the records of the finished calls), the
+ *    host entries aw_spatializer_process_host / _process_host_pcm (ordered behind what the stream already holds), and the first
+ *    long-window call of a handle that was not reserved, which builds its tables.  aw_spatializer_destroy waits for the stream before it
+ *    frees, so a handle may be destroyed with its calls still queued (the handle first, then its context).
+ *  - a caller's stream is never destroyed by the library. */
 AW_API void aw_context_destroy(aw_context *ctx);
 AW_API aw_status aw_context_synchronize(aw_context *ctx);
 AW_API void *aw_context_stream(aw_context *ctx);          /* the hipStream_t kernels are launched on */
