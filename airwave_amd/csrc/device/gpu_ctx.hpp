@@ -1,5 +1,6 @@
 // gpu_ctx.hpp — the GPU execution context of the tile code (LDS, barriers, fences); the CPU emulation harness has its
-// own (tests/emu/emu_harness.cpp).  Included by kernels.hip only (and by one-kernel probe builds under tools/).
+// own (tests/emu/emu_harness.cpp) — and the XCD-aware workgroup -> work mapping of the kernels.  Included by the kernel
+// translation units only (and by one-kernel probe builds under tools/).
 #pragma once
 #include "tile_ols.hpp"
 
@@ -254,5 +255,28 @@ struct GpuCtx {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
 };
+
+// Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 labels the XCD group).  Give
+// each XCD a contiguous run of tiles so that consecutive tiles of a stream, whose input windows
+// overlap by N - hop frames, share one L2 (MI355X_MICROARCH "Workgroup dispatch"; speed only).
+__device__ __forceinline__ long long xcd_remap(long long bid, long long nwg) {
+    const long long q = nwg / 8, r = nwg % 8;
+    const long long xcd = bid % 8, idx = bid / 8;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
+// The same for persistent workgroups walking a work list of n ids: each XCD group owns a contiguous eighth [lo, hi) of the
+// list and its `wgs` workgroups walk it interleaved (this one: lo + slot, lo + slot + wgs, ... < hi), so the ~32 tiles in
+// flight on one XCD are consecutive tiles of a stream: their overlapping input windows meet in that XCD's L2 (speed only).
+struct XcdShare { long long lo, hi, slot, wgs; };
+__device__ __forceinline__ XcdShare xcd_share(long long n) {
+    const long long g = gridDim.x, b = blockIdx.x;
+    const long long xcd = b % 8, slot = b / 8;
+    const long long per_xcd_wg = (g - xcd + 7) / 8;                       // workgroups in this group
+    const long long q = n / 8, r = n % 8;
+    const long long lo = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+    const long long hi = lo + (xcd < r ? q + 1 : q);
+    return XcdShare{lo, hi, slot, per_xcd_wg};
+}
 
 }  // namespace awk

@@ -15,33 +15,15 @@
 
 namespace awk {
 
-// Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 labels the XCD group).  Give
-// each XCD a contiguous run of tiles so that consecutive tiles of a stream, whose input windows
-// overlap by N - hop frames, share one L2 (MI355X_MICROARCH "Workgroup dispatch"; speed only).
-__device__ __forceinline__ long long xcd_remap(long long bid, long long nwg) {
-    const long long q = nwg / 8, r = nwg % 8;
-    const long long xcd = bid % 8, idx = bid / 8;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-
-// INTERIOR = true : tiles [tile_lo, tile_hi) of every stream (window inside the call's input)
+// INTERIOR = true: tiles [tile_lo, tile_hi) of every stream (window inside the call's input)
 // INTERIOR = false: the remaining boundary tiles (history at the start, zero fill at the end)
 template <int CS, int NP, bool INTERIOR, bool ACC = false>
 __global__ void __launch_bounds__(kThreads) aw_fused_ols_kernel(TileParams p, long long n_tiles) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     GpuCtx ctx{reinterpret_cast<cf *>(smem), p.dbg ? p.dbg + (long long)blockIdx.x * kStamps : nullptr};
     ctx.stamp_thread_ = p.stagger;          // diagnostic builds: which thread's wave is recorded
-    // Persistent workgroups, XCD-aware: workgroups are dealt round-robin over the 8 XCDs, so
-    // blockIdx % 8 labels the XCD group.  Each group owns a contiguous eighth of the tile list and
-    // its workgroups walk it interleaved, so the ~32 tiles in flight on one XCD are consecutive
-    // tiles of a stream: their overlapping input windows meet in that XCD's L2 (speed only).
-    const long long g = gridDim.x, b = blockIdx.x;
-    const long long xcd = b % 8, slot = b / 8;
-    const long long per_xcd_wg = (g - xcd + 7) / 8;                       // workgroups in this group
-    const long long q = n_tiles / 8, r = n_tiles % 8;
-    const long long lo = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const long long hi = lo + (xcd < r ? q + 1 : q);
-    tiles_fused_ols<GpuCtx, CS, NP, INTERIOR, ACC>(ctx, p, lo + slot, per_xcd_wg, hi);
+    const XcdShare x = xcd_share(n_tiles);          // persistent workgroups, XCD-aware (gpu_ctx.hpp)
+    tiles_fused_ols<GpuCtx, CS, NP, INTERIOR, ACC>(ctx, p, x.lo + x.slot, x.wgs, x.hi);
 }
 
 
@@ -60,20 +42,15 @@ __global__ void __launch_bounds__(kThreads) aw_part_forward_kernel(TileParams p,
     const int n_windows = p.n_blocks + p.partitions - 1;
     const int per = MODE == 1 ? p.tile_hi - p.tile_lo : MODE == 2 ? p.tile_lo - head_lo : n_windows - (p.tile_hi - head_lo);
     const int w0 = MODE == 1 ? p.tile_lo : head_lo, skip = p.tile_hi - head_lo;
-    const long long g = gridDim.x, b = blockIdx.x;
-    const long long xcd = b % 8, slot = b / 8;
-    const long long per_xcd_wg = (g - xcd + 7) / 8;
-    const long long q = n_ids / 8, r = n_ids % 8;
-    const long long lo = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const long long hi = lo + (xcd < r ? q + 1 : q);
+    const XcdShare x = xcd_share(n_ids);
 #if AW_FWD_RUNS
     // each workgroup walks a contiguous run of windows: consecutive windows of a stream overlap by half, and the half a
     // workgroup has just read is the likeliest to still be in its XCD's L2
-    const long long run = (hi - lo + per_xcd_wg - 1) / per_xcd_wg;
-    const long long first = lo + slot * run;
-    tiles_part_forward<GpuCtx, CS, MODE>(ctx, p, first, 1, first + run < hi ? first + run : hi, per, w0, skip);
+    const long long run = (x.hi - x.lo + x.wgs - 1) / x.wgs;
+    const long long first = x.lo + x.slot * run;
+    tiles_part_forward<GpuCtx, CS, MODE>(ctx, p, first, 1, first + run < x.hi ? first + run : x.hi, per, w0, skip);
 #else
-    tiles_part_forward<GpuCtx, CS, MODE>(ctx, p, lo + slot, per_xcd_wg, hi, per, w0, skip);
+    tiles_part_forward<GpuCtx, CS, MODE>(ctx, p, x.lo + x.slot, x.wgs, x.hi, per, w0, skip);
 #endif
 }
 

@@ -15,13 +15,8 @@ __global__ void __launch_bounds__(kThreads) aw_fused_ols2_kernel(TileParams p, l
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     GpuCtx ctx{reinterpret_cast<cf *>(smem), p.dbg ? p.dbg + (long long)blockIdx.x * kStamps : nullptr};
     ctx.stamp_thread_ = p.stagger;
-    const long long g = gridDim.x, b = blockIdx.x;
-    const long long xcd = b % 8, slot = b / 8;
-    const long long per_xcd_wg = (g - xcd + 7) / 8;
-    const long long q = n_tiles / 8, r = n_tiles % 8;
-    const long long lo = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    const long long hi = lo + (xcd < r ? q + 1 : q);
-    tiles_fused_ols2<GpuCtx, CS, NB, INTERIOR>(ctx, p, lo + slot, per_xcd_wg, hi);
+    const XcdShare x = xcd_share(n_tiles);
+    tiles_fused_ols2<GpuCtx, CS, NB, INTERIOR>(ctx, p, x.lo + x.slot, x.wgs, x.hi);
 }
 
 // even channel counts (ols2_even_kernels.hip): nullptr for every other layout

@@ -25,6 +25,10 @@
 // State between calls stays what every other path of the runtime keeps: the last `hist_len` INPUT frames (aw_hist_update_kernel), so
 // a spatializer may take this tile for one call and any other kernel family for the next.
 //
+// From tile_ols.hpp, as they are: the pair step (pair_subfft_cmac_h; this tile hangs its mid-block frame prefetch on the step's
+// `after` hook), the inverse row transforms, the final pass's transform (final_pass16) and the prologue (tile_prologue_h).  Its own:
+// the block loads, pass 1 on a zero-padded block, the pair-together step (ola_subfft_cmac2), the output stores and the carry.
+//
 // Shared with the CPU thread-emulation harness (tests/emu/): the Ctx supplies buf() / buf_ld<N>().
 #pragma once
 #include <utility>
@@ -60,7 +64,7 @@ template <int NP> struct OlaEarly { static constexpr bool value = NP >= 7; };
 #define AW_OLA_PAIR2_MAXNP 4
 #endif
 #ifndef AW_OLA_PREFETCH_MID
-#define AW_OLA_PREFETCH_MID 0          // 1: the next block's frames are requested right behind the block's last table request (ola_subfft_cmac)
+#define AW_OLA_PREFETCH_MID 0          // 1: the next block's frames are requested right behind the block's last table request (the `after` hook of pair_subfft_cmac_h)
 #endif
 
 // One block of one stream: frames idx0 + t + 512 j (j < H) of the source behind `src`, every channel, into raw[j][*].
@@ -123,72 +127,22 @@ AW_HD void ola_pass1(const cf (&xin)[H], const cf (&pw)[16], cf *buf, int t) {
     for (int k1 = 0; k1 < 16; ++k1) buf[k1 * kRowStride + t] = v[k1];
 }
 
-// Row transforms + multiply-accumulate of one pair (pair_subfft_cmac_h of tile_ols.hpp) with two hooks for this tile:
-//   TAB_EARLY  the pair's 16 table entries were requested by the caller BEFORE the row transform (64 VGPRs that the overlap-save tile,
-//              with 128 registers of frames, never had): they travel under the transform instead of being waited for after it;
-//   PREFETCH   right behind the pair's LAST table request, the next block's frame loads are queued into `raw` — vector-memory
-//              results return in issue order, so frames requested before a table load would hold that load's consumer up for an HBM
-//              round trip, frames requested after the last one delay nobody.
 template <int N, class F, int... I> AW_HD void ola_static_for_impl(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
 template <int N, class F> AW_HD void ola_static_for(F &&f) { ola_static_for_impl<N>(static_cast<F &&>(f), std::make_integer_sequence<int, N>{}); }
 
 template <class Buf> struct OlaNext { Buf src; int idx0; };     // the next block's source and first row (wave-uniform)
+// The pair step of tile_ols.hpp with this tile's frame prefetch on its `after` hook (PREFETCH: the next block's frames are queued into `raw`
+// right behind the pair's last table request).  The wrapper keeps the parameter list the step had in this file: called directly from
+// the block loop, the 13- and 14-channel kernels change their register and spill counts (see the note at the top of tile_ols.hpp).
 template <int G, bool TAB_EARLY, bool PREFETCH, int CS, int H, class Ctx>
 AW_HD void ola_subfft_cmac(Ctx &ctx, const TileParams &p, int pair, cf *buf, const cf *twa, cf2 (&tab)[16], int lane, int wave, cf (&wacc)[16],
                            const OlaNext<typename Ctx::Buf> &next, int t, float (&raw)[H][2 * ((CS + 1) / 2)]) {
-    static_assert(!TAB_EARLY || G == 16, "early tables come whole");
-    const HLane L = hl_make(ctx, buf, twa, lane, wave);
-    auto after = [&] { if constexpr (PREFETCH) ola_load_block<CS, H>(ctx, next.src, next.idx0, t, raw); };
-    if constexpr (TAB_EARLY) after();
-    cf z[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) z[j] = ctx.ld(L.row + L.h + 32 * j);
-    sub_fft512h_fwd(ctx, z, L);
-    if constexpr (G == 16) { if constexpr (!TAB_EARLY) { load_tab_h(p, pair, wave, lane, tab); after(); } }
-    else load_tab_part_h<G>(p, pair, wave, lane, 0, tab);
-#ifndef AW_ABL_OLA_NOPARTNER    // (timing ablation, wrong results: no publish of Z / no partner reads through LDS)
-#pragma unroll
-    for (int kb = 0; kb < 16; ++kb) L.row[L.col + 32 * kb] = z[kb];
-    ctx.wave_sync();
-#endif
-    if constexpr (G == 16) {
-#pragma unroll
-        for (int kb = 0; kb < 16; ++kb) {
-            int idx = L.pidx - 32 * kb;
-            if (kb == 0) idx &= 511;                               // only (row 0, column 0) wraps: 512 -> 0
-#ifdef AW_ABL_OLA_NOPARTNER
-            const cf zp = z[15 - kb];
-#else
-            const cf zp = ctx.ld(L.prow + idx);
-#endif
-            wacc[kb] = cfma(z[kb], tab[kb].a, wacc[kb]);
-            wacc[kb] = cfmac(zp, tab[kb].b, wacc[kb]);
-        }
-    } else {
-        static_assert(2 * G <= 16, "two parts in flight inside tab[16]");
-#pragma unroll
-        for (int part = 0; part < 16 / G; ++part) {
-            cf2 *cur = tab + G * (part & 1);
-            if (part + 1 < 16 / G) {
-                load_tab_part_h<G>(p, pair, wave, lane, part + 1, tab + G * ((part + 1) & 1));
-                if (part + 2 == 16 / G) after();
-            }
-#pragma unroll
-            for (int i = 0; i < G; ++i) {
-                const int kb = G * part + i;
-                int idx = L.pidx - 32 * kb;
-                if (kb == 0) idx &= 511;
-                const cf zp = ctx.ld(L.prow + idx);
-                wacc[kb] = cfma(z[kb], cur[i].a, wacc[kb]);
-                wacc[kb] = cfmac(zp, cur[i].b, wacc[kb]);
-            }
-        }
-    }
-    ctx.wave_sync();    // partner reads done before this wave reuses its rows as scratch
+    pair_subfft_cmac_h<G, TAB_EARLY>(ctx, p, pair, buf, twa, tab, lane, wave, wacc,
+                                     [&] { if constexpr (PREFETCH) ola_load_block<CS, H>(ctx, next.src, next.idx0, t, raw); });
 }
 
 // Two pairs of a batch through the row transforms and the multiply-accumulate TOGETHER (AW_OLA_PAIR2): the same instruction sequence as
-// ola_subfft_cmac, with every step issued for both pairs before the wave waits — pair p in buf0, pair p + 1 in buf1, so the exchanges do
+// pair_subfft_cmac_h (tile_ols.hpp), with every step issued for both pairs before the wave waits — pair p in buf0, pair p + 1 in buf1, so the exchanges do
 // not collide — which halves the number of LDS round trips a wave sits through per pair (the tile is bound by that chain, not by its
 // butterflies: tools/ubench/ola_bench with AW_ABL_NOFFT runs no faster) and shares the row twiddles between the two transforms.
 // 32 more VGPRs for the second spectrum and table parts of four entries for both pairs: layouts of up to four pairs only.
@@ -277,11 +231,9 @@ AW_HD void tiles_fused_ola(Ctx &ctx, const TileParams &p, long long first, long 
     const int t0 = ctx.tid();
     int t = t0, lane = ctx.lane();
     const int wave = ctx.wave();
-    cf *buf0 = ctx.lds();
-    cf *buf1 = buf0 + kBufElems;
-    cf *twa = buf1 + kBufElems;
-    const cf w1 = p.tw1[t];
-    twa[t] = hl_twiddle(p.twa, t);           // [16][32] row twiddles of the half-wave form; visible after the first barrier
+    const TileLdsH lds = tile_prologue_h(ctx, p, t);
+    cf *const buf0 = lds.buf0, *const buf1 = lds.buf1, *const twa = lds.twa;
+    const cf w1 = lds.w1;
     const int K = p.tiles_per_stream;
     const int warm = (p.hist_len + hop - 1) / hop;        // blocks whose tail reaches into a given block: ceil((taps - 1) / hop)
 
@@ -364,6 +316,9 @@ AW_HD void tiles_fused_ola(Ctx &ctx, const TileParams &p, long long first, long 
             if constexpr (AW_OLA_PAIR2 != 0 && two && NP <= AW_OLA_PAIR2_MAXNP) {
                 ola_subfft_cmac2<AW_OLA_PAIR2_G>(ctx, p, pair0, buf0, buf1, twa, lane, wave, wacc);
             } else {
+                // the shared pair step with this tile's two options: the tables requested BEFORE the row transform (64 VGPRs that the
+                // overlap-save tile, with 128 registers of frames, never had), and (mid) the next block's frames queued into `raw`
+                // right behind the block's last table request
                 cf2 tab[16];
                 if constexpr (kTabEarly) load_tab_h(p, pair0, wave, lane, tab);
                 ola_subfft_cmac<kTabG, kTabEarly, kMid && last_batch && !two, CS, H>(ctx, p, pair0, buf0, twa, tab, lane, wave, wacc, nsrc, t, raw);
@@ -380,15 +335,7 @@ AW_HD void tiles_fused_ola(Ctx &ctx, const TileParams &p, long long first, long 
         // radix-16 across rows: y[j] = block position t + 512 j; add the carry; j < H are frames, the rest is the new carry
         ctx.barrier();
         cf y[16];
-#pragma unroll
-        for (int k1 = 0; k1 < 16; ++k1) y[k1] = ctx.ld(buf0 + k1 * kRowStride + t);
-        {
-            cf pw[16];
-            tw_powers(ctx.opaque(w1), pw);
-#pragma unroll
-            for (int k1 = 1; k1 < 16; ++k1) y[k1] = cmulc(y[k1], pw[k1]);
-        }
-        fft16<true>(y);
+        final_pass16(ctx, buf0, w1, t, y);
         const bool store = cur.k >= cur.k_store;                                      // uniform
         float *out_s = p.out + cur.stream * p.frames * 2;
         const long long f0 = (long long)cur.k * hop;

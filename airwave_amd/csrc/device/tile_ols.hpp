@@ -23,15 +23,35 @@
 //
 // FFT_N = 16 x 512:  thread t (512 per workgroup) holds window samples t + 512 j, j < 16.
 //   pass 1 (all threads): radix-16 over j -> k1, twiddle W_N^{t k1}, exchange through LDS
-//   sub-FFT (per wave)  : 512-point DFT over t for a fixed k1 as three radix-8 passes with
-//                         wave-private LDS exchanges.  Wave w owns rows k1 in {w, 16-w}
-//                         ({0, 8} for w = 0), which is closed under k -> N-k: the CMAC and
-//                         the inverse sub-FFT never leave the wave.
+//   sub-FFT (per wave)  : 512-point DFT over t for a fixed k1 with wave-private LDS
+//                         exchanges.  Wave w owns rows k1 in {w, 16-w} ({0, 8} for w = 0),
+//                         which is closed under k -> N-k: the CMAC and the inverse sub-FFT
+//                         never leave the wave.  Two forms: a half-wave per row on the 16-point
+//                         core (sub_fft512h_*: the fused tiles here, in tile_ols2.hpp and in
+//                         tile_ola.hpp) and three radix-8 passes over a whole wave
+//                         (sub_fft512x2: the partitioned path below and the long-window kernels).
 //   inverse             : mirror image; last pass is the radix-16 across rows, so thread t
 //                         ends with output samples t + 512 j: coalesced stores.
 // Two workgroup barriers per batch of two pairs (+1 for the inverse); LDS = 2 x [16][576]
 // complex exchange buffers + 4.5 KiB of sub-FFT twiddles.
+//
+// Shared with tile_ols2.hpp and tile_ola.hpp: the vector frame load (ld_vec), the half-wave pair
+// step (pair_subfft_cmac_h), the inverse row transforms, the final pass's transform
+// (final_pass16) and the tile prologue (tile_prologue_h).
+//
+// A note for whoever moves code here: hipcc optimises every function — AW_HD ones and lambdas
+// included — on its own before it inlines it, so a new function boundary around an array that
+// used to be a local of its caller changes the kernels' instruction order and, in the kernels
+// that sit near 256 VGPRs, their register and spill counts.  Measured, and left as they are:
+//   - pass 1 from the register batch as a helper (either with its own x[16] or the caller's):
+//     aw_fused_ols_kernel<13, 7> / <14, 7> 19 -> 20 spilled VGPRs; written out at its call sites;
+//   - load_batch_head under load_frames: 1-2 more VGPRs in five head forward kernels;
+//   - the call-wrapping lambdas of the batch bodies (load_tab_, subfft_cmac_) and the
+//     overlap-add tile's ola_subfft_cmac, a wrapper with the old parameter list: calling
+//     pair_subfft_cmac_h directly moves aw_fused_ola_kernel<14, 7, 6> from 1 to 3 spilled VGPRs
+//     and <13, 7, 6> from 252 to 253 VGPRs.
 #pragma once
+#include <type_traits>
 #include "cplx.hpp"
 
 namespace awk {
@@ -58,6 +78,12 @@ constexpr bool kPrefetchRawEarly = AW_PREFETCH_RAW_EARLY != 0;
 #endif
 constexpr bool kTabEarly0 = (AW_TAB_EARLY & 1) != 0;   // first pair of a batch: table loads issued before the barrier
 constexpr bool kTabEarly1 = (AW_TAB_EARLY & 2) != 0;   // second pair: issued right after the first pair's CMAC   // issue the next batch's frame loads before pair 1's sub-FFTs
+// The 8192-frame tile's tables after the transform in one go (64 VGPRs) or in two parts of eight bins.  Measured per layout (tools/ols2_ab.py
+// WINDOW=8192, tools/ubench/tile_bench.hip): 13 / 14 channels 22.5 / 21.9 -> 23.9 / 23.2 G frames/s (19 spilled VGPRs either way, fewer live through
+// the multiply-accumulate), 9 / 10 +-0, 11 / 12 channels 28.5 / 29.2 -> 24.0 / 23.0 (!), 8 channels +-0 (parts of four: -5 %) — seven pairs only.
+#ifndef AW_TAB_G7
+#define AW_TAB_G7 8
+#endif
 #ifndef AW_SKIP_PHANTOM
 #define AW_SKIP_PHANTOM 1
 #endif
@@ -210,10 +236,6 @@ AW_HD void sub_fft512x2(Ctx &ctx, cf (&a)[2][8], cf *scr0, cf *scr1, const cf *t
 // One LDS exchange per row instead of two (63 LDS instructions per lane and row pair against 94):
 // tools/ubench/fft_core.hip 3.03 -> 2.56 us per pair transform per CU.
 // Bin order: on return a[kb] = X[hl_col(lane) + 32 kb].
-#ifndef AW_OLS_H
-#define AW_OLS_H 1        // 0: the fused 8192-frame tile on the 8 x 8 x 8 row transforms of rounds 1-3
-#endif
-
 AW_HD int hl_col(int lane) { return (lane & 7) + 8 * ((lane >> 4) & 1) + 16 * ((lane >> 3) & 1); }   // lane & 31 with bits 3 and 4 exchanged
 struct HLane {
     cf *row;        // the lane's row of the exchange buffer (also its half-wave's transpose scratch: 2 x 272 <= 576 elements)
@@ -322,6 +344,29 @@ struct alignas(8) f2 { float x, y; };
 struct __attribute__((packed, aligned(4))) f4u { float x, y, z, w; };   // 16 bytes at dword alignment
 struct __attribute__((packed, aligned(4))) f2u { float x, y; };    // 8 bytes at dword alignment
 
+// One vector load of N floats (16 or 8 bytes) at natural (NATURAL) or dword alignment -> dst[0 .. N-1].
+template <int N, bool NATURAL>
+AW_HD void ld_vec(const float *src, float *dst) {
+    static_assert(N == 4 || N == 2, "16 or 8 bytes");
+    if constexpr (N == 4) {
+        if constexpr (NATURAL) {
+            const f4 v = *reinterpret_cast<const f4 *>(src);
+            dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+        } else {
+            const f4u v = *reinterpret_cast<const f4u *>(src);
+            dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+        }
+    } else {
+        if constexpr (NATURAL) {
+            const f2 v = *reinterpret_cast<const f2 *>(src);
+            dst[0] = v.x; dst[1] = v.y;
+        } else {
+            const f2u v = *reinterpret_cast<const f2u *>(src);
+            dst[0] = v.x; dst[1] = v.y;
+        }
+    }
+}
+
 // One interleaved frame -> registers (channels c0 .. c0+3, zero padded).  Frames before the call
 // come from the history buffer (previous calls' tail; zeros after create/reset), frames past the
 // end read as zero.  CS = compile-time channel count for vector loads (0 = generic scalar path).
@@ -338,11 +383,10 @@ AW_HD void load_frame(const TileParams &p, const float *in_s, const float *hist_
     const bool past = f >= p.frames;
     const float *src = before ? hist_s + ((long long)p.hist_len + f) * C : (past ? p.zeros : in_s + f * C);
     if constexpr (CS > 0 && CS % 4 == 0) {
-        const f4 v = *reinterpret_cast<const f4 *>(src + c0);
-        dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+        ld_vec<4, true>(src + c0, dst);
     } else if constexpr (CS == 2) {
-        const f2 v = *reinterpret_cast<const f2 *>(src);
-        dst[0] = v.x; dst[1] = v.y; dst[2] = 0.0f; dst[3] = 0.0f;
+        ld_vec<2, true>(src, dst);
+        dst[2] = 0.0f; dst[3] = 0.0f;
     } else {
 #pragma unroll
         for (int c = 0; c < kBatchCh; ++c) {
@@ -353,10 +397,82 @@ AW_HD void load_frame(const TileParams &p, const float *in_s, const float *hist_
     }
 }
 
+// Vector loads of the thread's 16 frames (compile-time layouts).  Every loader is one loop over j around ld_vec; what
+// varies is how frame j's source pointer is formed, `addr(j)`:
+//   InteriorFrames  window entirely inside the call's input: a wave-uniform base + one per-lane 32-bit offset, which hipcc
+//                   turns into scalar-base global loads — no per-frame address registers, no clamping arithmetic;
+//   HeadFrames      head windows of the partitioned path (the first P windows of a call: part history, part input,
+//                   nothing past the end): per frame a pointer select between the history buffer and the input.
+//                   Layouts whose frames are not whole float4s read up to 3 floats past a frame: the history allocation
+//                   carries that slack (runtime.cpp), the launch keeps one input frame of slack.
+template <int CS> struct InteriorFrames {
+    const float *lane_base;   // uniform
+    int lane_off;             // per lane, 32-bit
+    AW_HD InteriorFrames(const float *in_s, long long f0, int t, int c0) : lane_base(in_s + f0 * CS + c0), lane_off(t * CS) {}
+    AW_HD const float *operator()(int j) const { return lane_base + (long long)j * 512 * CS + lane_off; }
+};
+template <int CS> struct HeadFrames {
+    const TileParams &p;
+    const float *in_s, *hist_s;
+    long long f0;
+    int t, c0;
+    AW_HD HeadFrames(const TileParams &p_, const float *in_s_, const float *hist_s_, long long f0_, int t_, int c0_)
+        : p(p_), in_s(in_s_), hist_s(hist_s_), f0(f0_), t(t_), c0(c0_) {}
+    AW_HD const float *operator()(int j) const {
+        const long long f = f0 + t + 512 * j;
+        return (f < 0 ? hist_s + ((long long)p.hist_len + f) * CS : in_s + f * CS) + c0;
+    }
+};
+// One batch: channels c0 .. c0+3 (the address rule carries c0), zero padded for stereo.
+template <int CS, class Addr>
+AW_HD void load_frames(const Addr &addr, float (&raw)[16][kBatchCh]) {
+    static_assert(CS > 0, "vector layouts only");
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const float *src = addr(j);
+        if constexpr (CS % 4 == 0) {
+            ld_vec<4, true>(src, raw[j]);
+        } else if constexpr (CS == 2) {
+            ld_vec<2, true>(src, raw[j]);
+            raw[j][2] = 0.f; raw[j][3] = 0.f;
+        } else if constexpr (CS % 2 == 0 && AW_EVEN_F2_LOADS) {
+            // 6, 10, 14 channels: frames are multiples of 8 bytes — two naturally aligned 8-byte loads instead of one
+            // dword-aligned 16-byte load (which the memory pipeline splits)
+            ld_vec<2, true>(src, raw[j]);
+            ld_vec<2, true>(src + 2, raw[j] + 2);
+        } else {
+            // frames that are not whole float4s (6, 7, 14 channels): one dword-aligned 16-B load all the
+            // same.  The last batch of a frame runs up to 3 floats into the next frame; those lanes belong
+            // to channels >= CS, whose filters are zero tables (build_pair_tables / the zero pair), so the
+            // finite stray samples contribute nothing.  The launch keeps one frame of slack at the end, the
+            // history allocation carries the same slack (runtime.cpp).
+            ld_vec<4, false>(src, raw[j]);
+        }
+    }
+}
+// Both four-channel batches of the 16 frames in one go (5 or more channels; the address rule points at the first of the
+// eight channels): the two 16-byte loads of a frame are issued back to back.
+// SECOND: floats of the second batch that are fetched — 4 (all), 2 (a seventh pair is the group's last: 13-14 channels) or
+// 0 (9-12 channels: the last eight-channel group has one batch).  FIRST = false: the second batch alone.
+template <int CS, int SECOND = 4, bool FIRST = true, class Addr>
+AW_HD void load_frames2(const Addr &addr, float (&ra)[16][kBatchCh], float (&rb)[16][kBatchCh]) {
+    static_assert(CS >= 5, "two batches of four channels (the first eight channels from the base pointer; wide layouts shift the base)");
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const float *src = addr(j);
+        if constexpr (FIRST) ld_vec<4, CS % 4 == 0>(src, ra[j]);
+        if constexpr (SECOND == 4) {
+            ld_vec<4, CS % 4 == 0>(src + 4, rb[j]);       // frames that are not whole float4s: runs up to 3 floats into the next frame, zero tables (see load_frames)
+        } else if constexpr (SECOND == 2) {
+            ld_vec<2, CS % 2 == 0>(src + 4, rb[j]);       // odd layouts: .y is the next frame's first sample, zero tables
+            rb[j][2] = 0.f; rb[j][3] = 0.f;
+        }
+    }
+}
+
 // Register batch: 16 frames x 4 channels (two pairs) per thread.
 // INTERIOR tiles (window entirely inside the call's input: every tile but the first one or two
-// and the last of a stream) use wave-uniform frame bases + one per-lane offset, which hipcc turns
-// into scalar-base global loads: no per-frame address registers, no clamping arithmetic.
+// and the last of a stream) take the vector loads, the others load_frame's per-frame selects.
 template <int CS, bool INTERIOR>
 AW_HD void load_batch(const TileParams &p, const float *in_s, const float *hist_s, long long f0, int t, int c0,
                       float (&raw)[16][kBatchCh]) {
@@ -368,32 +484,7 @@ AW_HD void load_batch(const TileParams &p, const float *in_s, const float *hist_
     }
 #endif
     if constexpr (INTERIOR && CS > 0) {
-        const float *lane_base = in_s + f0 * CS + c0;          // uniform
-        const int lane_off = t * CS;                            // per lane, 32-bit
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const float *src = lane_base + (long long)j * 512 * CS + lane_off;
-            if constexpr (CS % 4 == 0) {
-                const f4 v = *reinterpret_cast<const f4 *>(src);
-                raw[j][0] = v.x; raw[j][1] = v.y; raw[j][2] = v.z; raw[j][3] = v.w;
-            } else if constexpr (CS == 2) {
-                const f2 v = *reinterpret_cast<const f2 *>(src);
-                raw[j][0] = v.x; raw[j][1] = v.y; raw[j][2] = 0.f; raw[j][3] = 0.f;
-            } else if constexpr (CS % 2 == 0 && AW_EVEN_F2_LOADS) {
-                // 6, 10, 14 channels: frames are multiples of 8 bytes — two naturally aligned 8-byte loads instead of one
-                // dword-aligned 16-byte load (which the memory pipeline splits)
-                const f2 v0 = *reinterpret_cast<const f2 *>(src);
-                const f2 v1 = *reinterpret_cast<const f2 *>(src + 2);
-                raw[j][0] = v0.x; raw[j][1] = v0.y; raw[j][2] = v1.x; raw[j][3] = v1.y;
-            } else {
-                // frames that are not whole float4s (6, 7, 14 channels): one dword-aligned 16-B load all the
-                // same.  The last batch of a frame runs up to 3 floats into the next frame; those lanes belong
-                // to channels >= CS, whose filters are zero tables (build_pair_tables / the zero pair), so the
-                // finite stray samples contribute nothing.  The launch keeps one frame of slack at the end.
-                const f4u v = *reinterpret_cast<const f4u *>(src);
-                raw[j][0] = v.x; raw[j][1] = v.y; raw[j][2] = v.z; raw[j][3] = v.w;
-            }
-        }
+        load_frames<CS>(InteriorFrames<CS>(in_s, f0, t, c0), raw);
     } else {
 #pragma unroll
         for (int j = 0; j < 16; ++j) load_frame<CS>(p, in_s, hist_s, f0 + t + 512 * j, raw[j], c0);
@@ -410,50 +501,14 @@ AW_HD void load_batch(const TileParams &p, const float *in_s, const float *hist_
 #ifndef AW_WIDE_LATE_B
 #define AW_WIDE_LATE_B 0     // 1: the second batch of a wide layout's second channel group is fetched one pair later (measured: 14 channels 17.1 -> 15.9 G frames/s)
 #endif
-// SECOND: floats of the second batch that are fetched — 4 (all), 2 (a seventh pair is the group's last: 13-14 channels) or
-// 0 (9-12 channels: the last eight-channel group has one batch).
+// (load_frames2 behind the interior address rule, under the name its five call sites use)
 template <int CS, int SECOND = 4, bool FIRST = true>
 AW_HD void load_batch2(const float *in_s, long long f0, int t, float (&ra)[16][kBatchCh], float (&rb)[16][kBatchCh]) {
-    static_assert(CS >= 5, "two batches of four channels (the first eight channels from the base pointer; wide layouts shift the base)");
-    const float *lane_base = in_s + f0 * CS;            // uniform
-    const int lane_off = t * CS;                         // per lane, 32-bit
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const float *src = lane_base + (long long)j * 512 * CS + lane_off;
-        if constexpr (FIRST) {
-            if constexpr (CS % 4 == 0) {
-                const f4 a = *reinterpret_cast<const f4 *>(src);
-                ra[j][0] = a.x; ra[j][1] = a.y; ra[j][2] = a.z; ra[j][3] = a.w;
-            } else {
-                const f4u a = *reinterpret_cast<const f4u *>(src);
-                ra[j][0] = a.x; ra[j][1] = a.y; ra[j][2] = a.z; ra[j][3] = a.w;
-            }
-        }
-        if constexpr (SECOND == 4) {
-            if constexpr (CS % 4 == 0) {
-                const f4 b = *reinterpret_cast<const f4 *>(src + 4);
-                rb[j][0] = b.x; rb[j][1] = b.y; rb[j][2] = b.z; rb[j][3] = b.w;
-            } else {
-                const f4u b = *reinterpret_cast<const f4u *>(src + 4);      // runs up to 3 floats into the next frame: zero tables (see load_batch)
-                rb[j][0] = b.x; rb[j][1] = b.y; rb[j][2] = b.z; rb[j][3] = b.w;
-            }
-        } else if constexpr (SECOND == 2) {
-            if constexpr (CS % 2 == 0) {
-                const f2 b = *reinterpret_cast<const f2 *>(src + 4);
-                rb[j][0] = b.x; rb[j][1] = b.y;
-            } else {
-                const f2u b = *reinterpret_cast<const f2u *>(src + 4);      // .y is the next frame's first sample: zero tables
-                rb[j][0] = b.x; rb[j][1] = b.y;
-            }
-            rb[j][2] = 0.f; rb[j][3] = 0.f;
-        }
-    }
+    load_frames2<CS, SECOND, FIRST>(InteriorFrames<CS>(in_s, f0, t, 0), ra, rb);
 }
 
-// HEAD windows of the partitioned path (the first P windows of a call: part history, part input, nothing past the
-// end): per frame a pointer select between the history buffer and the input, then the same whole-frame vector load as
-// the interior windows.  Layouts whose frames are not whole float4s read up to 3 floats past a frame: the history
-// allocation carries that slack (runtime.cpp), the launch keeps one input frame of slack.
+// One batch of a head window.  The same loop as load_frames<CS>(HeadFrames<CS>(...), raw), written out: through the shared
+// loop the head forward kernels of the 2-, 4-, 12-, 14- and 16-channel layouts take 1-2 more VGPRs (178 -> 179, 208 -> 210).
 template <int CS>
 AW_HD void load_batch_head(const TileParams &p, const float *in_s, const float *hist_s, long long f0, int t, int c0,
                            float (&raw)[16][kBatchCh]) {
@@ -463,37 +518,12 @@ AW_HD void load_batch_head(const TileParams &p, const float *in_s, const float *
         const long long f = f0 + t + 512 * j;
         const float *src = (f < 0 ? hist_s + ((long long)p.hist_len + f) * CS : in_s + f * CS) + c0;
         if constexpr (CS % 4 == 0) {
-            const f4 v = *reinterpret_cast<const f4 *>(src);
-            raw[j][0] = v.x; raw[j][1] = v.y; raw[j][2] = v.z; raw[j][3] = v.w;
+            ld_vec<4, true>(src, raw[j]);
         } else if constexpr (CS == 2) {
-            const f2 v = *reinterpret_cast<const f2 *>(src);
-            raw[j][0] = v.x; raw[j][1] = v.y; raw[j][2] = 0.f; raw[j][3] = 0.f;
+            ld_vec<2, true>(src, raw[j]);
+            raw[j][2] = 0.f; raw[j][3] = 0.f;
         } else {
-            const f4u v = *reinterpret_cast<const f4u *>(src);
-            raw[j][0] = v.x; raw[j][1] = v.y; raw[j][2] = v.z; raw[j][3] = v.w;
-        }
-    }
-}
-
-// Both four-channel batches of a head window's frames back to back (5-8 channels), as load_batch2 does for interior windows.
-template <int CS>
-AW_HD void load_batch2_head(const TileParams &p, const float *in_s, const float *hist_s, long long f0, int t,
-                            float (&ra)[16][kBatchCh], float (&rb)[16][kBatchCh]) {
-    static_assert(CS >= 5 && CS <= 8, "two batches of four channels");
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const long long f = f0 + t + 512 * j;
-        const float *src = f < 0 ? hist_s + ((long long)p.hist_len + f) * CS : in_s + f * CS;
-        if constexpr (CS % 4 == 0) {
-            const f4 a = *reinterpret_cast<const f4 *>(src);
-            const f4 b = *reinterpret_cast<const f4 *>(src + 4);
-            ra[j][0] = a.x; ra[j][1] = a.y; ra[j][2] = a.z; ra[j][3] = a.w;
-            rb[j][0] = b.x; rb[j][1] = b.y; rb[j][2] = b.z; rb[j][3] = b.w;
-        } else {
-            const f4u a = *reinterpret_cast<const f4u *>(src);
-            const f4u b = *reinterpret_cast<const f4u *>(src + 4);      // up to 3 floats into the next frame (history: its allocation's slack)
-            ra[j][0] = a.x; ra[j][1] = a.y; ra[j][2] = a.z; ra[j][3] = a.w;
-            rb[j][0] = b.x; rb[j][1] = b.y; rb[j][2] = b.z; rb[j][3] = b.w;
+            ld_vec<4, false>(src, raw[j]);
         }
     }
 }
@@ -507,77 +537,8 @@ AW_HD void pair_pass1(cf (&x)[16], const cf (&pw)[16], cf *buf, int t) {
     for (int k1 = 0; k1 < 16; ++k1) buf[k1 * kRowStride + t] = x[k1];
 }
 
-// This lane's 16 table entries of one pair (issued early; consumed after the sub-FFTs).
-AW_HD void load_tab(const TileParams &p, int pair, int wave, int lane, cf2 (&tab)[2][8]) {
-#ifdef AW_ABL_NOTAB      // timing ablation only (wrong results): no table traffic
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int kc = 0; kc < 8; ++kc) { tab[s][kc].a = mk(1.0f + pair, 0.5f * lane); tab[s][kc].b = mk(0.25f * kc, 1.0f * wave); }
-    return;
-#endif
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const cf2 *row = p.tab + ((long long)pair * kN + wave_row(wave, s) * kSub + lane);
-#pragma unroll
-        for (int kc = 0; kc < 8; ++kc) tab[s][kc] = row[64 * kc];
-    }
-}
-
-// Per wave: the two 512-point sub-FFTs of its rows, then W += Z A + conj(Z[N-k]) B.
-template <class Ctx>
-AW_HD void pair_subfft_cmac(Ctx &ctx, const TileParams &p, int pair, cf *buf, const cf *twa, const cf *twb,
-                            cf2 (&tab)[2][8], int lane, int wave, cf (&wacc)[2][8], bool tab_loaded) {
-    cf *row0 = buf + wave_row(wave, 0) * kRowStride;
-    cf *row1 = buf + wave_row(wave, 1) * kRowStride;
-    cf z[2][8];
-    ctx.template ld8x2<64>(z[0], row0 + lane, z[1], row1 + lane);
-    ctx.wave_sync();
-    sub_fft512x2<false>(ctx, z, row0, row1, twa, twb, lane);
-#ifdef AW_ABL_NOCMAC          // timing ablation only (wrong results): no tables, no partner exchange, no multiply-accumulate
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int kc = 0; kc < 8; ++kc) wacc[s][kc] = wacc[s][kc] + z[s][kc];
-    return;
-#endif
-    if (!tab_loaded) load_tab(p, pair, wave, lane, tab);
-    ctx.stamp(22);
-#ifdef AW_ABL_NOPARTNER       // timing ablation only (wrong results): no partner exchange through LDS
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int kc = 0; kc < 8; ++kc) {
-            wacc[s][kc] = cfma(z[s][kc], tab[s][kc].a, wacc[s][kc]);
-            wacc[s][kc] = cfmac(z[1 - s][7 - kc], tab[s][kc].b, wacc[s][kc]);
-        }
-    return;
-#endif
-    // publish Z rows inside the wave, then CMAC against the partner bins
-#pragma unroll
-    for (int kc = 0; kc < 8; ++kc) { row0[lane + 64 * kc] = z[0][kc]; row1[lane + 64 * kc] = z[1][kc]; }
-    ctx.wave_sync();
-    // partner of bin (k1, k2): row (16 - k1) & 15 (the wave's other row; itself for k1 in {0, 8}),
-    // column (512 - k2) & 511 for k1 == 0, else 511 - k2.
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const cf *prow = (wave == 0) ? (s == 0 ? row0 : row1) : (s == 0 ? row1 : row0);
-        const int bidx = 511 - lane + ((wave == 0 && s == 0) ? 1 : 0);
-#pragma unroll
-        for (int kc = 0; kc < 8; ++kc) {
-            int idx = bidx - 64 * kc;
-            if (kc == 0) idx &= 511;                       // only (row 0, lane 0, kc 0) wraps: 512 -> 0
-            const cf zp = ctx.ld(prow + idx);
-            wacc[s][kc] = cfma(z[s][kc], tab[s][kc].a, wacc[s][kc]);
-            wacc[s][kc] = cfmac(zp, tab[s][kc].b, wacc[s][kc]);
-        }
-    }
-    ctx.wave_sync();    // partner reads done before this wave reuses its rows as scratch
-    ctx.stamp(23);
-}
-
-// Inverse half of a tile, part 1: per-wave 512-point inverse sub-FFTs of W (scratch = the wave's
-// own rows of buf0, which only it touches until the barrier), results published row-wise.
+// Inverse half of a tile, part 1 on the 8 x 8 x 8 row transforms (partitioned path): per-wave 512-point inverse sub-FFTs
+// of W (scratch = the wave's own rows of buf0, which only it touches until the barrier), results published row-wise.
 template <class Ctx>
 AW_HD void tile_inverse_rows(Ctx &ctx, cf (&wacc)[2][8], cf *buf0, const cf *twa, const cf *twb) {
     const int lane = ctx.lane(), wave = ctx.wave();
@@ -588,19 +549,8 @@ AW_HD void tile_inverse_rows(Ctx &ctx, cf (&wacc)[2][8], cf *buf0, const cf *twa
     for (int kc = 0; kc < 8; ++kc) { row0[lane + 64 * kc] = wacc[0][kc]; row1[lane + 64 * kc] = wacc[1][kc]; }
 }
 
-// The same three steps on the half-wave row transforms (AW_OLS_H): a lane holds 16 bins of ONE row.
-AW_HD void load_tab_h(const TileParams &p, int pair, int wave, int lane, cf2 (&tab)[16]) {
-#ifdef AW_ABL_NOTAB      // timing ablation only (wrong results): no table traffic
-#pragma unroll
-    for (int kb = 0; kb < 16; ++kb) { tab[kb].a = mk(1.0f + pair, 0.5f * lane); tab[kb].b = mk(0.25f * kb, 1.0f * wave); }
-    return;
-#endif
-    const cf2 *row = p.tab + ((long long)pair * kN + wave_row(wave, lane >> 5) * kSub + hl_col(lane));
-#pragma unroll
-    for (int kb = 0; kb < 16; ++kb) tab[kb] = row[32 * kb];          // per half-wave 512 contiguous bytes (whole 128-byte lines per 8 lanes)
-}
-// G: table entries per part when the tables are fetched after the transform (G = 16: all at once, 64 VGPRs; G = 4: two parts of
-// four in flight, 32 VGPRs — the next part travels while the current one is consumed).
+// ---- the pair step of the fused tiles, on the half-wave row transforms: a lane holds 16 bins of ONE row ----------------
+// Part `part` of G of this lane's 16 table entries of one pair (G = 16: all of them).
 template <int G>
 AW_HD void load_tab_part_h(const TileParams &p, int pair, int wave, int lane, int part, cf2 *tab) {
 #ifdef AW_ABL_NOTAB      // timing ablation only (wrong results): no table traffic
@@ -610,47 +560,61 @@ AW_HD void load_tab_part_h(const TileParams &p, int pair, int wave, int lane, in
 #endif
     const cf2 *row = p.tab + ((long long)pair * kN + wave_row(wave, lane >> 5) * kSub + hl_col(lane) + 32 * G * part);
 #pragma unroll
-    for (int i = 0; i < G; ++i) tab[i] = row[32 * i];
+    for (int i = 0; i < G; ++i) tab[i] = row[32 * i];                // per half-wave 512 contiguous bytes (whole 128-byte lines per 8 lanes)
 }
-template <int G = 16, class Ctx>
+AW_HD void load_tab_h(const TileParams &p, int pair, int wave, int lane, cf2 (&tab)[16]) { load_tab_part_h<16>(p, pair, wave, lane, 0, tab); }
+
+// Per wave: the 512-point row transforms of its two rows of one pair, then W += Z A + conj(Z[N-k]) B.
+//   G          table entries per part (G = 16: all at once, 64 VGPRs; G = 8 or 4: two parts in flight inside tab[16], 64 or 32 VGPRs —
+//              the next part travels while the current one is consumed);
+//   TAB_EARLY  the pair's 16 table entries were requested by the caller BEFORE the row transform: they travel under the transform
+//              instead of being waited for after it;
+//   after      called right behind the pair's LAST table request.  Vector-memory results return in issue order, so loads queued
+//              there (the overlap-add tile's next block of frames) delay no table entry's consumer, where loads queued before a
+//              table request would hold that consumer up for an HBM round trip.
+struct NoHook { AW_HD void operator()() const {} };
+template <int G, bool TAB_EARLY, class Ctx, class After = NoHook>
 AW_HD void pair_subfft_cmac_h(Ctx &ctx, const TileParams &p, int pair, cf *buf, const cf *twa, cf2 (&tab)[16], int lane, int wave,
-                              cf (&wacc)[16], bool tab_loaded) {
+                              cf (&wacc)[16], After &&after = After{}) {
+    constexpr int NPART = 16 / G;
+    static_assert(G == 16 || 2 * G <= 16, "two parts in flight inside tab[16]");
+    static_assert(!TAB_EARLY || G == 16, "early tables come whole");
     const HLane L = hl_make(ctx, buf, twa, lane, wave);
+    if constexpr (TAB_EARLY) after();
     cf z[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) z[j] = ctx.ld(L.row + L.h + 32 * j);
     sub_fft512h_fwd(ctx, z, L);
-    if constexpr (G == 16) { if (!tab_loaded) load_tab_h(p, pair, wave, lane, tab); }
-    else load_tab_part_h<G>(p, pair, wave, lane, 0, tab);
+    if constexpr (!TAB_EARLY) {
+        load_tab_part_h<G>(p, pair, wave, lane, 0, tab);
+        if constexpr (NPART == 1) after();
+    }
     ctx.stamp(22);
     // publish Z in natural column order inside the wave, then multiply-accumulate against the partner bins
+#ifndef AW_ABL_OLA_NOPARTNER    // (timing ablation, wrong results: no publish of Z / no partner reads through LDS)
 #pragma unroll
     for (int kb = 0; kb < 16; ++kb) L.row[L.col + 32 * kb] = z[kb];
     ctx.wave_sync();
-    if constexpr (G == 16) {
+#endif
 #pragma unroll
-        for (int kb = 0; kb < 16; ++kb) {
+    for (int part = 0; part < NPART; ++part) {
+        const cf2 *cur = tab + G * (part & 1);
+        if (part + 1 < NPART) {
+            load_tab_part_h<G>(p, pair, wave, lane, part + 1, tab + G * ((part + 1) & 1));
+            if (part + 2 == NPART) after();
+        }
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int kb = G * part + i;
             int idx = L.pidx - 32 * kb;
             if (kb == 0) idx &= 511;                               // only (row 0, column 0) wraps: 512 -> 0
+#ifdef AW_ABL_OLA_NOPARTNER
+            const cf zp = z[15 - kb];
+#else
             const cf zp = ctx.ld(L.prow + idx);
-            wacc[kb] = cfma(z[kb], tab[kb].a, wacc[kb]);
-            wacc[kb] = cfmac(zp, tab[kb].b, wacc[kb]);
-        }
-    } else {
-        static_assert(2 * G <= 16, "two parts in flight inside tab[16]");
-#pragma unroll
-        for (int part = 0; part < 16 / G; ++part) {
-            cf2 *cur = tab + G * (part & 1);
-            if (part + 1 < 16 / G) load_tab_part_h<G>(p, pair, wave, lane, part + 1, tab + G * ((part + 1) & 1));
-#pragma unroll
-            for (int i = 0; i < G; ++i) {
-                const int kb = G * part + i;
-                int idx = L.pidx - 32 * kb;
-                if (kb == 0) idx &= 511;
-                const cf zp = ctx.ld(L.prow + idx);
-                wacc[kb] = cfma(z[kb], cur[i].a, wacc[kb]);
-                wacc[kb] = cfmac(zp, cur[i].b, wacc[kb]);
-            }
+#endif
+            wacc[kb] = cfma(z[kb], cur[i].a, wacc[kb]);
+            wacc[kb] = cfmac(zp, cur[i].b, wacc[kb]);
         }
     }
     ctx.wave_sync();    // partner reads done before this wave reuses its rows as scratch
@@ -664,6 +628,21 @@ AW_HD void tile_inverse_rows_h(Ctx &ctx, cf (&wacc)[16], cf *buf0, const cf *twa
     ctx.wave_sync();
 #pragma unroll
     for (int j = 0; j < 16; ++j) L.row[L.h + 32 * j] = wacc[j];
+}
+
+// The final pass's transform, radix-16 across the rows of buf0: y[j] = window position t + 512 j (after the barrier
+// that publishes the rows).
+template <class Ctx>
+AW_HD void final_pass16(Ctx &ctx, const cf *buf0, cf w1, int t, cf (&y)[16]) {
+#pragma unroll
+    for (int k1 = 0; k1 < 16; ++k1) y[k1] = ctx.ld(buf0 + k1 * kRowStride + t);
+    {
+        cf pw[16];
+        tw_powers(ctx.opaque(w1), pw);
+#pragma unroll
+        for (int k1 = 1; k1 < 16; ++k1) y[k1] = cmulc(y[k1], pw[k1]);
+    }
+    fft16<true>(y);
 }
 
 // Part 2: barrier, radix-16 across rows, then store window positions m >= first_valid whose
@@ -685,15 +664,7 @@ AW_HD void tile_inverse_final(Ctx &ctx, const TileParams &p, cf *buf0, cf w1, in
     ctx.barrier();
     ctx.stamp(12);
     cf y[16];
-#pragma unroll
-    for (int k1 = 0; k1 < 16; ++k1) y[k1] = ctx.ld(buf0 + k1 * kRowStride + t);
-    {
-        cf pw[16];
-        tw_powers(ctx.opaque(w1), pw);
-#pragma unroll
-        for (int k1 = 1; k1 < 16; ++k1) y[k1] = cmulc(y[k1], pw[k1]);
-    }
-    fft16<true>(y);
+    final_pass16(ctx, buf0, w1, t, y);
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         const int m = t + 512 * j;
@@ -709,6 +680,33 @@ AW_HD void tile_inverse_final(Ctx &ctx, const TileParams &p, cf *buf0, cf w1, in
     }
     ctx.stamp(13);
     ctx.flush_stamps();
+}
+
+// Tile prologue: the LDS carve-up (exchange buffers, then the row twiddles), this thread's pass-1 twiddle base and its
+// share of the row-twiddle staging (visible after the tile's first barrier).
+//   half-wave form: two exchange buffers, [16][32] row twiddles, one entry per thread;
+struct TileLdsH { cf *buf0, *buf1, *twa; cf w1; };
+template <class Ctx> AW_HD TileLdsH tile_prologue_h(Ctx &ctx, const TileParams &p, int t) {
+    TileLdsH s;
+    s.buf0 = ctx.lds();
+    s.buf1 = s.buf0 + kBufElems;
+    s.twa = s.buf1 + kBufElems;
+    s.w1 = p.tw1[t];
+    s.twa[t] = hl_twiddle(p.twa, t);
+    return s;
+}
+//   8 x 8 x 8 form: NBUF exchange buffers (buf1 only with two), the [8][64] and [8][8] tables copied as they are.
+struct TileLds888 { cf *buf0, *buf1, *twa, *twb; cf w1; };
+template <int NBUF, class Ctx> AW_HD TileLds888 tile_prologue_888(Ctx &ctx, const TileParams &p, int t) {
+    TileLds888 s;
+    s.buf0 = ctx.lds();
+    s.buf1 = s.buf0 + kBufElems;
+    s.twa = s.buf0 + NBUF * kBufElems;
+    s.twb = s.twa + kTwaElems;
+    s.w1 = p.tw1[t];
+    s.twa[t] = p.twa[t];                                 // 512 entries, one per thread
+    if (t < kTwbElems) s.twb[t] = p.twb[t];
+    return s;
 }
 
 // NP: compile-time pair count (straight-line schedule, no phis around the prefetches); NP = 0 is
@@ -741,20 +739,11 @@ AW_HD void tiles_fused_ols(Ctx &ctx, const TileParams &p, long long first, long 
     const int t0 = ctx.tid();
     int t = t0, lane = ctx.lane();
     const int wave = ctx.wave();
-    cf *buf0 = ctx.lds();
-    cf *buf1 = buf0 + kBufElems;
-    cf *twa = buf1 + kBufElems;        // LDS copies of the sub-FFT twiddles
-    cf *twb = twa + kTwaElems;
     const int Cn = CS > 0 ? CS : p.n_channels;
     if (first >= end) return;
-    const cf w1 = p.tw1[t];
-#if AW_OLS_H
-    twa[t] = hl_twiddle(p.twa, t);                       // [16][32] row twiddles of the half-wave form, one per thread
-    (void)twb;
-#else
-    twa[t] = p.twa[t];                                   // 512 entries, one per thread
-    if (t < kTwbElems) twb[t] = p.twb[t];                // visible after the first barrier below
-#endif
+    const TileLdsH lds = tile_prologue_h(ctx, p, t);
+    cf *const buf0 = lds.buf0, *const buf1 = lds.buf1, *const twa = lds.twa;
+    const cf w1 = lds.w1;
 
     // whole-frame mode: both batches of a tile are loaded together (load_batch2), batch 1 waits in raw_b
     // kWide (9-16 channels in ONE pass, 5-8 compile-time pairs): two groups of eight channels; the second group is fetched
@@ -783,17 +772,9 @@ AW_HD void tiles_fused_ols(Ctx &ctx, const TileParams &p, long long first, long 
     const long long f0 = (long long)cur.tile * p.hop - p.hist_len;     // frame of window position 0
     ctx.stamp(0);
 
-#if AW_OLS_H
     cf wacc[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) wacc[i] = mk(0.f, 0.f);
-#else
-    cf wacc[2][8];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wacc[s][i] = mk(0.f, 0.f);
-#endif
 
     // Schedule per batch of two pairs:
     //   pass 1 of both pairs -> buf0, buf1 ; issue pair 0's table loads ; barrier ;
@@ -821,6 +802,9 @@ AW_HD void tiles_fused_ols(Ctx &ctx, const TileParams &p, long long first, long 
 #pragma unroll
                     for (int j = 0; j < 16; ++j) x[j] = mk(raw[j][0], raw[j][1]);
                     pair_pass1(x, pw, buf0, t);
+                    // NOT under `if (two)`: in whole-frame mode the first batch's second pair runs whether or not the layout has one.
+                    // <9, 5> and <10, 5> reach here as batch(4, false, false) and transform channels 2-3 of the batch into buf1,
+                    // which nothing reads — one wasted pass 1 per tile.  Kept as it is; dropping it is a speed change of its own.
 #pragma unroll
                     for (int j = 0; j < 16; ++j) x[j] = mk(raw[j][2], raw[j][3]);
                     pair_pass1(x, pw, buf1, t);
@@ -836,28 +820,16 @@ AW_HD void tiles_fused_ols(Ctx &ctx, const TileParams &p, long long first, long 
             }
             }
         }
-#if AW_OLS_H
         cf2 tab[16];
-        auto load_tab_ = [&](int pr) { load_tab_h(p, pr, wave, lane, tab); };
-        // tables after the transform in one go (64 VGPRs) or in two parts of eight bins.  Measured per layout (tools/ols2_ab.py WINDOW=8192,
-        // tools/ubench/tile_bench.hip): 13 / 14 channels 22.5 / 21.9 -> 23.9 / 23.2 G frames/s (19 spilled VGPRs either way, fewer live through the
-        // multiply-accumulate), 9 / 10 +-0, 11 / 12 channels 28.5 / 29.2 -> 24.0 / 23.0 (!), 8 channels +-0 (parts of four: -5 %) — seven pairs only.
-#ifndef AW_TAB_G7
-#define AW_TAB_G7 8
-#endif
         constexpr int kTabG = (kTabEarly0 || kTabEarly1) ? 16 : NP == 7 ? AW_TAB_G7 : 16;
-        auto subfft_cmac_ = [&](int pr, cf *bf, bool loaded) { pair_subfft_cmac_h<kTabG>(ctx, p, pr, bf, twa, tab, lane, wave, wacc, loaded); };
-#else
-        cf2 tab[2][8];
-        auto load_tab_ = [&](int pr) { load_tab(p, pr, wave, lane, tab); };
-        auto subfft_cmac_ = [&](int pr, cf *bf, bool loaded) { pair_subfft_cmac(ctx, p, pr, bf, twa, twb, tab, lane, wave, wacc, loaded); };
-#endif
+        auto load_tab_ = [&](int pr) { load_tab_h(p, pr, wave, lane, tab); };
+        auto subfft_cmac_ = [&](auto early, int pr, cf *bf) { pair_subfft_cmac_h<kTabG, decltype(early)::value>(ctx, p, pr, bf, twa, tab, lane, wave, wacc); };
         if (kTabEarly0) load_tab_(pair0);
         ctx.stamp(pair0 > 0 ? 7 : 2);
         ctx.barrier();
         ctx.stagger(wave, p.stagger);
         ctx.stamp(pair0 > 0 ? 8 : 3);
-        subfft_cmac_(pair0, buf0, kTabEarly0);
+        subfft_cmac_(std::bool_constant<kTabEarly0>{}, pair0, buf0);
         ctx.stamp(pair0 > 0 ? 9 : 4);
         const int pair1 = pair0 + 1;     // a phantom second pair (odd pair count, runtime loop) lands on the zero pair after the last one
         if (two && kTabEarly1) load_tab_(pair1);
@@ -865,7 +837,7 @@ AW_HD void tiles_fused_ols(Ctx &ctx, const TileParams &p, long long first, long 
             if (pair0 == 2) load_batch2<CS, (NP == 8 && !AW_WIDE_LATE_B ? 4 : NP == 7 && !AW_WIDE_LATE_B ? 2 : 0)>(in_s + 8, f0, t, raw, raw_b);      // channels 8-15 (a 9-12 channel layout: 8-11 only)
         }
         if (!kWhole && kPrefetchRawEarly && more) load_batch<CS, INTERIOR>(p, in_s, hist_s, f0, t, 2 * (pair0 + 2), raw);
-        if (two) subfft_cmac_(pair1, buf1, kTabEarly1);
+        if (two) subfft_cmac_(std::bool_constant<kTabEarly1>{}, pair1, buf1);
         if constexpr (kWide && AW_WIDE_LATE_B != 0 && NP >= 7) {      // the group's second batch one pair later (an L2 hit): fewer values live through the CMAC
             if (pair0 == 2) load_batch2<CS, (NP == 8 ? 4 : 2), false>(in_s + 8, f0, t, raw, raw_b);
         }
@@ -883,11 +855,7 @@ AW_HD void tiles_fused_ols(Ctx &ctx, const TileParams &p, long long first, long 
             batch(pair0, (kSkipPhantom && !kEvenPairs) ? pair0 + 1 < n_pairs : true, pair0 + 2 < n_pairs);
     }
 
-#if AW_OLS_H
     tile_inverse_rows_h(ctx, wacc, buf0, twa);
-#else
-    tile_inverse_rows(ctx, wacc, buf0, twa, twb);
-#endif
     {   // prefetch the next tile's first batch here, where few registers are live (unconditional:
         // the last iteration re-reads its own batch; a branch would put phis on 64 registers)
         const TileId nx = tile_of<INTERIOR>(p, id + step < end ? id + step : id);
@@ -973,18 +941,14 @@ AW_HD void tiles_part_forward(Ctx &ctx, const TileParams &p, long long first, lo
     const int t0 = ctx.tid();
     int t = t0, lane = ctx.lane();
     const int wave = ctx.wave();
-    cf *buf0 = ctx.lds();
-    cf *buf1 = buf0 + kBufElems;
-    cf *twa = buf1 + kBufElems;
-    cf *twb = twa + kTwaElems;
     const int Cn = CS > 0 ? CS : p.n_channels;
     const int n_windows = p.n_blocks + p.partitions - 1;
-    const cf w1 = p.tw1[t];
-    twa[t] = p.twa[t];
-    if (t < kTwbElems) twb[t] = p.twb[t];
+    const TileLds888 lds = tile_prologue_888<2>(ctx, p, t);
+    cf *const buf0 = lds.buf0, *const buf1 = lds.buf1, *const twa = lds.twa, *const twb = lds.twb;
+    const cf w1 = lds.w1;
 
-    // whole-frame mode (interior windows of 5-8 channel layouts): both four-channel batches of a window are loaded together
-    // (load_batch2: every line crosses the L2 -> L1 path once), the second batch waits in raw_b
+    // whole-frame mode (interior and head windows of 5-8 channel layouts): both four-channel batches of a window are loaded
+    // together (load_frames2 behind either address rule: every line crosses the L2 -> L1 path once), the second batch waits in raw_b
     constexpr bool kWhole = AW_WHOLE_FRAMES != 0 && (MODE == 1 || MODE == 2) && CS >= 5 && CS <= 8;
     float raw[16][kBatchCh];
     float raw_b[kWhole ? 16 : 1][kBatchCh];
@@ -992,7 +956,7 @@ AW_HD void tiles_part_forward(Ctx &ctx, const TileParams &p, long long first, lo
         const float *in_w = p.in + w.stream * p.frames * Cn;
         const long long fw = ((long long)w.w - p.partitions) * p.hop;
         if constexpr (kWhole) {
-            if constexpr (MODE == 2) load_batch2_head<CS>(p, in_w, p.hist + w.stream * (long long)p.hist_len * Cn, fw, t, raw, raw_b);
+            if constexpr (MODE == 2) load_frames2<CS>(HeadFrames<CS>(p, in_w, p.hist + w.stream * (long long)p.hist_len * Cn, fw, t, 0), raw, raw_b);
             else load_batch2<CS>(in_w, fw, t, raw, raw_b);
             if constexpr (CS % 4 != 0) {                    // the padding lanes of the last batch must be real zeros (herm_last; no NaN from the next stream's history)
 #pragma unroll
@@ -1085,9 +1049,6 @@ template <class Ctx, int CS, int MODE>
 AW_HD void tile_part_forward1(Ctx &ctx, const TileParams &p, long long stream, int widx, int pair) {
     const int t = ctx.tid();
     const int lane = ctx.lane(), wave = ctx.wave();
-    cf *buf0 = ctx.lds();
-    cf *twa = buf0 + kBufElems;
-    cf *twb = twa + kTwaElems;
     const int Cn = CS > 0 ? CS : p.n_channels;
     const float *in_s = p.in + stream * p.frames * Cn;
     const float *hist_s = p.hist + stream * (long long)p.hist_len * Cn;
@@ -1102,13 +1063,9 @@ AW_HD void tile_part_forward1(Ctx &ctx, const TileParams &p, long long stream, i
         const long long f = f0 + t + 512 * j;
         if constexpr (MODE != 0 && CS > 0) {
             const float *src = (MODE == 2 && f < 0 ? hist_s + ((long long)p.hist_len + f) * CS : in_s + f * CS) + c0;
-            if constexpr (CS % 2 == 0) {
-                const f2 v = *reinterpret_cast<const f2 *>(src);
-                x[j] = mk(v.x, v.y);
-            } else {
-                const f2u v = *reinterpret_cast<const f2u *>(src);      // the last pair's .y is the next frame's first sample: dropped below
-                x[j] = mk(v.x, v.y);
-            }
+            float v[2];
+            ld_vec<2, CS % 2 == 0>(src, v);                 // odd layouts: the last pair's second float is the next frame's first sample, dropped below
+            x[j] = mk(v[0], v[1]);
         } else {
             const bool before = f < 0, past = f >= p.frames;
             const float *src = before ? hist_s + ((long long)p.hist_len + f) * Cn : (past ? p.zeros : in_s + f * Cn);
@@ -1122,9 +1079,9 @@ AW_HD void tile_part_forward1(Ctx &ctx, const TileParams &p, long long stream, i
             for (int j = 0; j < 16; ++j) x[j].y = 0.f;
         }
     }
-    const cf w1 = p.tw1[t];
-    twa[t] = p.twa[t];
-    if (t < kTwbElems) twb[t] = p.twb[t];
+    const TileLds888 lds = tile_prologue_888<1>(ctx, p, t);      // behind the frame loads
+    cf *const buf0 = lds.buf0, *const twa = lds.twa, *const twb = lds.twb;
+    const cf w1 = lds.w1;
     {
         cf pw[16];
         tw_powers(ctx.opaque(w1), pw);
@@ -1215,12 +1172,9 @@ template <class Ctx>
 AW_HD void tile_part_inverse(Ctx &ctx, const TileParams &p, long long stream, int block) {
     const int t = ctx.tid();
     const int lane = ctx.lane(), wave = ctx.wave();
-    cf *buf0 = ctx.lds();
-    cf *twa = buf0 + kBufElems;
-    cf *twb = twa + kTwaElems;
-    const cf w1 = p.tw1[t];
-    twa[t] = p.twa[t];
-    if (t < kTwbElems) twb[t] = p.twb[t];
+    const TileLds888 lds = tile_prologue_888<1>(ctx, p, t);
+    cf *const buf0 = lds.buf0, *const twa = lds.twa, *const twb = lds.twb;
+    const cf w1 = lds.w1;
     const cf *ws = p.wspec + ((stream * p.n_blocks) + block) * (long long)kN;
     cf wacc[2][8];
 #pragma unroll
