@@ -468,7 +468,9 @@ class Spatializer:
                 "loudness": g(21),              # the loudness measurement is on (set_loudness)
                 "true_peak": g(22),             # the true-peak measurement is on (set_true_peak)
                 "limiter": g(23),               # the limiter is on (set_limiter)
-                "limiter_latency": g(24)}       # its latency in frames (0 while it is off)
+                "limiter_latency": g(24),       # its latency in frames (0 while it is off)
+                "equalizer": g(25),             # presets of the equalizer stage (set_equalizer; 0: the stage is off)
+                "equalizer_filters": g(26)}     # the largest enabled-filter count among them
 
     def process_device(self, in_ptr: int, out_ptr: int, frames: int) -> None:
         _check(self._lib.aw_spatializer_process(self._h, ctypes.c_void_p(in_ptr), ctypes.c_void_p(out_ptr), frames))
@@ -652,6 +654,35 @@ class Spatializer:
         out = np.zeros(n, LIMITER_DTYPE)
         _check(self._lib.aw_spatializer_get_limiter(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
         return out
+
+    def set_equalizer(self, definitions, stream_definition=None) -> None:
+        """aw_spatializer_set_equalizer: the equalizer stage of every later batch call, between the convolution and the first meter.
+        definitions: the presets (EqualizerDefinition; one alone is taken as a list of one; none or an empty list: the stage is off);
+        stream_definition: per stream the index of its preset, -1 = not equalized (None: every stream takes preset 0).  Allocates and
+        uploads here, not on the process path, and starts the filter state from zero.  A preset that cannot be prepared raises
+        ParametricEqualizerPreparationError, as ParametricEqualizerState does; the previous stage then stays."""
+        from .eq import _DefHandle, _check_eq            # (eq.py imports this module)
+        if definitions is None:
+            definitions = []
+        elif not isinstance(definitions, (list, tuple)):
+            definitions = [definitions]
+        sd = None
+        if stream_definition is not None:
+            sd = np.ascontiguousarray(stream_definition, dtype=np.int32)
+            if sd.shape != (self.n_streams,):
+                raise ValueError(f"stream_definition needs one entry per stream ({self.n_streams}), got shape {sd.shape}")
+        handles = []
+        try:
+            for d in definitions:
+                handles.append(_DefHandle(d))
+            if any(h.h is None for h in handles):
+                raise ValueError("a definition is None (map the stream to -1 instead)")
+            arr = (ctypes.c_void_p * max(len(handles), 1))(*[h.h for h in handles])
+            _check_eq(self._lib.aw_spatializer_set_equalizer(self._h, ctypes.cast(arr, _capi.c_void_pp) if handles else None, len(handles),
+                                                             None if sd is None else _i32p(sd)))
+        finally:
+            for h in handles:
+                h.__exit__()
 
     def reset(self) -> None:
         _check(self._lib.aw_spatializer_reset(self._h))

@@ -19,7 +19,7 @@ class RateBucket:
     stream_ids: List[int]            # positions in the caller's stream list, in order
     hrir_taps: int                   # taps of the tracks the spatializer convolves with (HRIR resampled to the rate, equalizer folded in if it was)
     spatializer: Spatializer
-    equalizer: Optional[object] = None      # ParametricEqualizerState that runs AFTER the spatializer (None: no equalizer, or folded into the HRIR)
+    equalizer: Optional[object] = None      # ParametricEqualizerState that runs AFTER the spatializer (None: no equalizer, folded into the HRIR, or the spatializer's own stage)
     eq_response_taps: int = 0        # equalizer folded into the HRIR: samples of its impulse response that were kept (0: not folded)
     eq_tail_bound: float = 0.0       # ... and the bound on what the cut can change, relative to the spatializer output's peak
 
@@ -55,12 +55,20 @@ class MixedRateBatch:
 
     def __init__(self, tracks, hrir_rate: float, layout: InputLayout, stream_rates: Sequence[float],
                  hrirMap: Optional[HRIRChannelMap] = None, ctx: Optional[Context] = None, literal_vgenp: bool = False,
-                 equalizer=None, fold_equalizer: Optional[bool] = None, eq_tail_tolerance: float = 1e-7, eq_max_taps: int = 65536):
+                 equalizer=None, fold_equalizer: Optional[bool] = None, eq_tail_tolerance: float = 1e-7, eq_max_taps: int = 65536,
+                 stream_equalizers=None):
         """equalizer: an EqualizerDefinition applied after the spatializer, as AudioEffectGraph orders the two effects
         (AudioEffectGraph.swift:195-211).  fold_equalizer: True = folded into the HRIR (aw_eq_fold_hrir; raises EqualizerNotFoldable
         if its response is too long), False = the cascade kernel after the spatializer, None = whichever is cheaper (see _fold_pays),
-        the cascade if it cannot be folded."""
+        the cascade if it cannot be folded.
+        stream_equalizers: instead of `equalizer`, one EqualizerDefinition or None per stream, in the caller's order (one headphone
+        preset per output device, DeviceProfileManager): every bucket's spatializer runs them as its equalizer stage
+        (Spatializer.set_equalizer), the bucket's distinct definitions being the presets.  Never folded: the HRIR is shared."""
         from .eq import EqualizerNotFoldable, ParametricEqualizerState, fold_equalizer as fold
+        if equalizer is not None and stream_equalizers is not None:
+            raise ValueError("equalizer= and stream_equalizers= are mutually exclusive")
+        if stream_equalizers is not None and len(stream_equalizers) != len(stream_rates):
+            raise ValueError(f"stream_equalizers needs one entry per stream ({len(stream_rates)}), got {len(stream_equalizers)}")
         self.ctx = ctx or default_context()
         tracks = np.ascontiguousarray(tracks, dtype=np.float32)
         # the reference's chooser: 7-track files take the 7-channel map, everything else the 14-channel one
@@ -83,6 +91,14 @@ class MixedRateBatch:
             if equalizer is not None and folded is None:
                 eq_state = ParametricEqualizerState(equalizer, float(rate), n_streams=len(ids), ctx=self.ctx)
             sp = Spatializer(HRIR(tr, rate, ctx=self.ctx), lt, rt, n_streams=len(ids), ctx=self.ctx)
+            if stream_equalizers is not None:
+                presets, which = [], []
+                for i in ids:
+                    d = stream_equalizers[i]
+                    if d is not None and d not in presets:
+                        presets.append(d)
+                    which.append(-1 if d is None else presets.index(d))
+                sp.set_equalizer(presets, which if presets else None)
             self.buckets[rate] = RateBucket(rate, ids, int(tr.shape[1]), sp, eq_state, folded.responseTaps if folded else 0, folded.tailBound if folded else 0.0)
 
     def process_device(self, in_ptrs: Dict[float, int], out_ptrs: Dict[float, int], frames: Dict[float, int]) -> None:

@@ -24,6 +24,7 @@
 // Shared between hipcc (kernels.hip) and the CPU thread-emulation harness (tests/emu).
 #pragma once
 #include "cplx.hpp"
+#include "eq_stage.hpp"
 
 // Timing ablations (wrong results; tools/archive/eq_ablate.sh only): bit 0 no recurrence, 1 no in-wave scan,
 // 2 no wave chaining, 3 no zero-input correction.
@@ -78,7 +79,9 @@ struct EqParams {
     long long stride_frames;  // distance between streams, in frames
     int cus;                  // compute units of the context's device (LaunchCfg); 0 = 256
     int ear_split;            // LaunchCfg::eq_ear_split: -1 automatic, 0 / 1 forced
+    long long z_stride;       // doubles between the states of two streams; 0 = n_filters x 4, the dense [stream][K][4] above
 };
+AW_HD long long eq_z_stride(const EqParams &p) { return p.z_stride ? p.z_stride : (long long)p.t.n_filters * 4; }
 
 AW_HD double eq_flush(double v) { return (v < 0 ? -v : v) < 1e-30 ? 0.0 : v; }   // flushSubnormal :95-97
 
@@ -145,7 +148,7 @@ template <class Ctx, int E> AW_HD void eq_cascade_stream(Ctx &ctx, const EqParam
     constexpr int kStride = kEqChunk * E + (E == 2 ? 4 : 1);               // floats per chunk row: 68 (16-B units) / 33
     const int wave = ctx.wave();
     const int K = p.t.n_filters;
-    double *zs = p.z + stream * (long long)K * 4 + ear0 * 2;               // [K][4]: this workgroup's S of every 4
+    double *zs = p.z + stream * eq_z_stride(p) + ear0 * 2;                 // [K][4]: this workgroup's S of every 4
     const float *in = p.in + stream * p.stride_frames * 2 + ear0;
     float *out = p.out + stream * p.stride_frames * 2 + ear0;
     const double preamp = p.t.preamp;
@@ -337,7 +340,7 @@ AW_HD void eq_sequential(const EqParams &p, long long stream, int ear) {
 #pragma clang fp contract(off)
 #endif
     const int K = p.t.n_filters;
-    double *zs = p.z + stream * (long long)K * 4 + ear * 2;
+    double *zs = p.z + stream * eq_z_stride(p) + ear * 2;
     const float *in = p.in + (stream * p.stride_frames) * 2 + ear;
     float *out = p.out + (stream * p.stride_frames) * 2 + ear;
     for (long long f = 0; f < p.frames; ++f) {
@@ -353,6 +356,70 @@ AW_HD void eq_sequential(const EqParams &p, long long stream, int ear) {
         }
         out[2 * f] = (float)v;
     }
+}
+
+/* ---- the batch entries' equalizer stage (rules and records: eq_stage.hpp): the two bodies above with ONE preset per stream ---- */
+struct EqStageParams {
+    float *y;                 // [stream][stride_frames][2] interleaved L,R: the convolution's output, equalized in place
+    double *z;                // [stream][kmax][4]
+    const int *map;           // [stream]: the stream's preset, -1 = not equalized
+    const EqStagePreset *presets;
+    const double *tables;     // every preset's tab and plane, at the offsets its header states
+    long long frames;         // frames this launch processes per stream
+    long long stride_frames;  // distance between streams, in frames
+    int kmax;                 // rows of a stream's state
+    int cus, ear_split;       // as EqParams
+};
+
+// A value every lane of the wave holds alike, in a scalar register (so what is loaded through it is loaded by the scalar unit).
+AW_HD int eq_uniform(int v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_readfirstlane(v);
+#else
+    return v;
+#endif
+}
+AW_HD long long eq_uniform(long long v) {
+    const unsigned long long u = (unsigned long long)v;
+    return (long long)(((unsigned long long)(unsigned)eq_uniform((int)(unsigned)(u >> 32)) << 32) | (unsigned)eq_uniform((int)(unsigned)u));
+}
+AW_HD double eq_uniform(double v) { return __builtin_bit_cast(double, eq_uniform(__builtin_bit_cast(long long, v))); }
+
+// The EqParams of a stream of the stage whose map entry is `preset` (>= 0).
+// kUniform: the preset is the same in every lane of the wave (a function of the workgroup's index): the header's values go to scalar
+// registers, and the filter loop reads the tables with scalar loads as aw_eq_cascade_kernel does.  presets / tables are the kernel's
+// own `const __restrict__` arguments (sp's copies are not looked at).
+template <bool kUniform>
+AW_HD void eq_stage_params(const EqStageParams &sp, const EqStagePreset *presets, const double *tables, int preset, EqParams &p) {
+    const EqStagePreset h = presets[preset];
+    p.in = sp.y; p.out = sp.y; p.z = sp.z;
+    p.t.tab = tables + (kUniform ? eq_uniform(h.tab_off) : h.tab_off);
+    p.t.plane = tables + (kUniform ? eq_uniform(h.plane_off) : h.plane_off);
+    p.t.preamp = kUniform ? eq_uniform(h.preamp) : h.preamp;
+    p.t.n_filters = kUniform ? eq_uniform(h.n_filters) : h.n_filters;
+    p.frames = sp.frames; p.stride_frames = sp.stride_frames;
+    p.cus = sp.cus; p.ear_split = sp.ear_split;
+    p.z_stride = (long long)sp.kmax * 4;
+}
+
+// One workgroup, E ears of one stream from ear0 on: eq_cascade_stream of the stream's preset; a stream that is not equalized returns
+// with nothing but its map entry read.  sp.frames must be a multiple of kEqChunk.
+template <class Ctx, int E>
+AW_HD void eq_stage_stream(Ctx &ctx, const EqStageParams &sp, const int *map, const EqStagePreset *presets, const double *tables, long long stream, int ear0) {
+    const int preset = eq_uniform(map[stream]);
+    if (preset < 0) return;
+    EqParams p;
+    eq_stage_params<true>(sp, presets, tables, preset, p);
+    eq_cascade_stream<Ctx, E>(ctx, p, stream, ear0);
+}
+
+// One thread per (stream, ear): eq_sequential of the stream's preset (calls shorter than a chunk, the tail of a call).
+AW_HD void eq_stage_sequential(const EqStageParams &sp, long long stream, int ear) {
+    const int preset = sp.map[stream];
+    if (preset < 0) return;
+    EqParams p;
+    eq_stage_params<false>(sp, sp.presets, sp.tables, preset, p);
+    eq_sequential(p, stream, ear);
 }
 
 }  // namespace awk

@@ -33,6 +33,26 @@ __global__ void aw_eq_sequential_kernel(EqParams p, int n_streams) {
     if (i < n_streams * 2) eq_sequential(p, i >> 1, i & 1);
 }
 
+// The batch entries' equalizer stage: the two kernels above with the stream's preset looked up first (eq_stage_stream).  Same launch
+// bounds, LDS and block -> (stream, ear) map; the map, the headers and the tables are `const __restrict__` arguments for the same reason.
+// A workgroup whose stream is not equalized returns before it loads anything else.
+template <int E>
+__global__ void __launch_bounds__(kEqThreads, E == 2 ? AW_EQ_WAVES : (kEqChunk <= 16 ? 4 : kEqChunk <= 32 ? 3 : 2)) aw_eq_stage_kernel(EqStageParams sp, const int *__restrict__ map,
+                                                                                      const EqStagePreset *__restrict__ presets, const double *__restrict__ tables, int n_streams) {
+    extern __shared__ __align__(16) unsigned char eq_lds[];
+    ScanGpuCtx ctx{reinterpret_cast<cf *>(eq_lds)};
+    if constexpr (E == 2) eq_stage_stream<ScanGpuCtx, 2>(ctx, sp, map, presets, tables, (long long)blockIdx.x, 0);
+    else {
+        const int b = (int)blockIdx.x, stream = (b >> 4) * 8 + (b & 7);
+        if (stream < n_streams) eq_stage_stream<ScanGpuCtx, 1>(ctx, sp, map, presets, tables, (long long)stream, (b >> 3) & 1);
+    }
+}
+
+__global__ void aw_eq_stage_tail_kernel(EqStageParams sp, int n_streams) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < n_streams * 2) eq_stage_sequential(sp, i >> 1, i & 1);
+}
+
 __global__ void aw_eq_blend_kernel(const float *__restrict__ old_seg, const float *__restrict__ new_seg, float *__restrict__ out,
                                    long long seg_frames, long long out_stride, long long t_frame, long long length) {
 #pragma clang fp contract(off)
@@ -60,6 +80,8 @@ __global__ void aw_eq_copy_kernel(const float *__restrict__ src, long long src_s
 hipError_t prepare_eq_kernels() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_eq_cascade_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, eq_lds_bytes(2));
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_eq_cascade_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, eq_lds_bytes(1));
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_eq_stage_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, eq_lds_bytes(2));
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_eq_stage_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, eq_lds_bytes(1));
     return e;
 }
 
@@ -81,6 +103,25 @@ hipError_t launch_eq_sequential(const EqParams &p, int n_streams, hipStream_t st
     if (n_streams <= 0 || p.frames <= 0) return hipSuccess;
     const int n = n_streams * 2;
     hipLaunchKernelGGL(aw_eq_sequential_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, p, n_streams);
+    return hipGetLastError();
+}
+
+// launch_eq_cascade's policy and grids
+hipError_t launch_eq_stage(const EqStageParams &p, int n_streams, hipStream_t stream) {
+    if (n_streams <= 0 || p.frames <= 0) return hipSuccess;
+    const int cus = p.cus > 0 ? p.cus : 256, force = p.ear_split;
+    const bool split = force >= 0 ? force != 0 : 2 * n_streams <= 3 * cus;
+    if (split)
+        hipLaunchKernelGGL(aw_eq_stage_kernel<1>, dim3((unsigned)((n_streams + 7) / 8) * 16), dim3(kEqThreads), eq_lds_bytes(1), stream, p, p.map, p.presets, p.tables, n_streams);
+    else
+        hipLaunchKernelGGL(aw_eq_stage_kernel<2>, dim3((unsigned)n_streams), dim3(kEqThreads), eq_lds_bytes(2), stream, p, p.map, p.presets, p.tables, n_streams);
+    return hipGetLastError();
+}
+
+hipError_t launch_eq_stage_tail(const EqStageParams &p, int n_streams, hipStream_t stream) {
+    if (n_streams <= 0 || p.frames <= 0) return hipSuccess;
+    const int n = n_streams * 2;
+    hipLaunchKernelGGL(aw_eq_stage_tail_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, p, n_streams);
     return hipGetLastError();
 }
 

@@ -8,10 +8,14 @@ namespace awk {
 
 // Chunk-parallel cascade over p.frames (multiple of kEqChunk) frames of every stream: one workgroup
 // of kEqThreads per stream.
-hipError_t prepare_eq_kernels();     // dynamic-LDS attribute of the cascade kernels (more than 64 KB); once per context
+hipError_t prepare_eq_kernels();     // dynamic-LDS attribute of the cascade and stage kernels (more than 64 KB); once per context
 hipError_t launch_eq_cascade(const EqParams &p, int n_streams, hipStream_t stream);
 // The sequential recurrence, one thread per (stream, ear): short calls and tails.
 hipError_t launch_eq_sequential(const EqParams &p, int n_streams, hipStream_t stream);
+// The batch entries' equalizer stage, one preset per stream (eq_stage.hpp): the stage's forms of the two launchers above, in place on
+// p.y.  launch_eq_stage: p.frames is a multiple of kEqChunk; launch_eq_stage_tail: the rest, and the whole of shorter calls.
+hipError_t launch_eq_stage(const EqStageParams &p, int n_streams, hipStream_t stream);
+hipError_t launch_eq_stage_tail(const EqStageParams &p, int n_streams, hipStream_t stream);
 // Crossfade of two rendered segments (ParametricEqualizerProcessor.swift:296-304):
 // out[s][f][e] = Float(Double(old) * (1 - g) + Double(new) * g),  g = (t_frame + f + 1) / length.
 // old_seg/new_seg: [stream][seg_frames][2]; out: [stream][out_stride][2].

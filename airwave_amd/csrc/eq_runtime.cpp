@@ -17,10 +17,6 @@
 
 using awr::fail;
 
-struct aw_eq_definition {
-    awh::EqDefinition def;
-};
-
 namespace {
 
 // ParametricEqualizerState for n_streams streams: tables + per-stream Float64 histories in HBM.
@@ -48,8 +44,9 @@ aw_status state_reset(EqState &s) {
     return AW_OK;
 }
 
-aw_status prepare_state(aw_context *ctx, const awh::EqDefinition *def, double sample_rate, int n_streams, EqStatePtr &out) {
-    awh::EqPrepared prep;
+}  // namespace
+
+aw_status awr::eq_prepare_checked(const awh::EqDefinition *def, double sample_rate, awh::EqPrepared &prep) {
     int bad_index = 0, bad_kind = 0;
     switch (awh::eq_prepare(def, sample_rate, prep, &bad_index, &bad_kind)) {
         case awh::kEqPrepInvalidSampleRate: return fail(AW_ERR_EQ_INVALID_SAMPLE_RATE, "Sample rate must be finite and positive.");
@@ -64,8 +61,16 @@ aw_status prepare_state(aw_context *ctx, const awh::EqDefinition *def, double sa
             return awr::fail_eq_filter(bad_index, bad_kind, line, "Filter " + std::to_string(bad_index + 1) + " is invalid: " + biquad_error_text(bad_kind) +
                                                       " [kind " + std::to_string(bad_kind) + ", line " + std::to_string(line) + "]");
         }
-        default: break;
+        default: return AW_OK;
     }
+}
+
+namespace {
+
+aw_status prepare_state(aw_context *ctx, const awh::EqDefinition *def, double sample_rate, int n_streams, EqStatePtr &out) {
+    awh::EqPrepared prep;
+    const aw_status prepared = awr::eq_prepare_checked(def, sample_rate, prep);
+    if (prepared != AW_OK) return prepared;
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(AW_ERR_NO_DEVICE, "hipSetDevice failed");
     auto st = std::make_shared<EqState>();
     st->ctx = ctx; st->n_streams = n_streams; st->sample_rate = sample_rate;

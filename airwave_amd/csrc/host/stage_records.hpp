@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "../device/eq_stage.hpp"
 #include "../device/levels.hpp"
 #include "../device/limiter.hpp"
 #include "../device/loudness.hpp"
@@ -27,6 +28,24 @@ struct Cursor {
         off += slots * f.bytes();
         return f;
     }
+    // n elements of T that the streams share (tables, headers), on the next multiple of alignof(T)
+    template <class T> Field<T> take_shared(size_t n) {
+        off = (off + alignof(T) - 1) / alignof(T) * alignof(T);
+        const Field<T> f{off, 0, 0};
+        off += n * sizeof(T);
+        return f;
+    }
+};
+
+struct Equalizer {                            // Equalizer{{n_streams}, n_presets, kmax, table_doubles}; rules: device/eq_stage.hpp
+    Cursor c;
+    size_t n_presets, kmax, table_doubles;
+    Field<double> state = c.take<double>(kmax * 4);                           // [kmax][4] per stream: a stream uses the rows of its own preset
+    size_t reset_bytes = c.off;                                               // a reset zeroes the filter state; the presets stay
+    Field<int32_t> map = c.take<int32_t>();                                   // the stream's preset, -1 = not equalized
+    Field<awk::EqStagePreset> presets = c.take_shared<awk::EqStagePreset>(n_presets);      // one header per preset (8-byte aligned behind the map)
+    Field<double> tables = c.take_shared<double>(table_doubles);             // every preset's tab, then its plane
+    size_t total = c.off;
 };
 
 struct Levels {                               // Levels{{n_streams}}; rules: device/levels.hpp

@@ -597,6 +597,8 @@ int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what) {
         case 22: return sp->tp.on ? 1 : 0;        // the true-peak measurement is on (aw_spatializer_set_true_peak)
         case 23: return sp->lim.on ? 1 : 0;       // the limiter is on (aw_spatializer_set_limiter)
         case 24: return sp->lim.on ? awlim::delay(sp->lim.attack) : 0;      // its latency in frames
+        case 25: return sp->eq.n_presets;         // presets of the equalizer stage (aw_spatializer_set_equalizer); 0: the stage is off
+        case 26: return sp->eq.kmax;              // the largest enabled-filter count among them
         default: return -1;
     }
 }
@@ -1254,6 +1256,43 @@ static aw_status ld_measure(aw_spatializer *sp, const float *y, int64_t s0, int 
     return AW_OK;
 }
 
+/* ---- equalizer of the batch entries (aw_spatializer_set_equalizer; rules: device/eq_stage.hpp, kernels: device/eq_cascade.hpp) ---- */
+static awst::Equalizer eq_layout(const aw_spatializer *sp) {
+    return awst::Equalizer{{(size_t)sp->n_streams}, (size_t)sp->eq.n_presets, (size_t)sp->eq.kmax, sp->eq.table_doubles};
+}
+
+static aw_status eq_reset(aw_spatializer *sp) {
+    const size_t bytes = sp->eq.d ? eq_layout(sp).reset_bytes : 0;
+    return bytes ? stage_zero(sp, sp->eq.d.get(), bytes) : AW_OK;
+}
+
+// The float32 output y of the streams [s0, s0 + ns) of a call (dense: `frames` apart), in place, before any meter: the chunk-parallel
+// body over the whole chunks and the sequential tail, the split aw_eq_state_process makes.  A workgroup owns a stream and the state is
+// per stream, so chunks of streams are independent.
+static aw_status eq_run(aw_spatializer *sp, float *y, int64_t s0, int ns, int64_t frames) {
+    SpStageTimer tm(sp);
+    const awst::Equalizer L = eq_layout(sp);
+    unsigned char *const d = sp->eq.d.get();
+    awk::EqStageParams p{};
+    p.z = L.state.at(d, (size_t)s0); p.map = L.map.at(d, (size_t)s0); p.presets = L.presets.at(d); p.tables = L.tables.at(d);
+    p.stride_frames = frames; p.kmax = sp->eq.kmax;
+    p.cus = sp->ctx->cfg.cus; p.ear_split = sp->ctx->cfg.eq_ear_split;
+    const int64_t body = frames - frames % awk::kEqChunk;
+    if (body > 0) {
+        if (sp->profiling) tm.begin();
+        p.y = y; p.frames = body;
+        AW_HIP_TRY(awk::launch_eq_stage(p, ns, sp->ctx->stream));
+        if (sp->profiling) tm.end("aw_eq_stage_kernel");
+    }
+    if (frames > body) {
+        if (sp->profiling) tm.begin();
+        p.y = y + body * 2; p.frames = frames - body;
+        AW_HIP_TRY(awk::launch_eq_stage_tail(p, ns, sp->ctx->stream));
+        if (sp->profiling) tm.end("aw_eq_stage_tail_kernel");
+    }
+    return AW_OK;
+}
+
 /* ---- true peak of the batch entries (aw_spatializer_set_true_peak, AW_GAIN_TRUE_PEAK_CEILING; rules: device/truepeak.hpp, kernel:
  * device/truepeak_tile.hpp) ---- */
 static_assert(sizeof(aw_stream_true_peak) == 32, "aw_stream_true_peak");
@@ -1555,7 +1594,7 @@ static void batch_end(aw_spatializer *sp) {
 }
 
 // The streams [s0, s0 + ns) of a call, on the context's stream: pcm_src -> decode into f_in -> kernels -> meter / gain -> encode of f_out
-// into pcm_dst.  A float32 side has no conversion and no staging: the kernels read pcm_src / write pcm_dst, f_in / f_out is not looked at.
+// into pcm_dst; the equalizer, where one is set, works on the kernels' output in place before the first meter.  A float32 side has no conversion and no staging: the kernels read pcm_src / write pcm_dst, f_in / f_out is not looked at.
 // With the limiter on the kernels write y into the limiter's staging instead, the meters tap it there, and the limiter (which applies
 // the fixed gain) writes z where y would have gone.
 static aw_status batch_chunk(aw_spatializer *sp, const BatchCall &call, int64_t s0, int ns, const void *pcm_src, float *f_in, float *f_out, void *pcm_dst) {
@@ -1567,6 +1606,7 @@ static aw_status batch_chunk(aw_spatializer *sp, const BatchCall &call, int64_t 
     if (st == AW_OK && lim) st = grow_buf(sp, &sp->lim.d_y, (size_t)ns * call.out_ps);      // (reserved for: nothing happens)
     float *y = lim ? sp->lim.d_y.get() : dst;
     if (st == AW_OK) st = sp_run_streams(sp, call.lw, (int)s0, ns, x, y, call.frames);
+    if (st == AW_OK && call.metered && sp->eq.n_presets) st = eq_run(sp, y, s0, ns, call.frames);                 // (every later stage sees the equalized y)
     if (st == AW_OK && call.metered && sp->ld.on) st = ld_measure(sp, y, s0, ns, call.frames, call.loud0);      // (before the gain)
     if (st == AW_OK && call.metered && tp_runs(sp)) st = tp_measure(sp, y, s0, ns, call.frames);                   // (the gain may read its result)
     if (st == AW_OK && call.metered) st = lv_after_run(sp, y, s0, ns, call.frames, !call.enc && !lim);
@@ -1581,6 +1621,7 @@ static aw_status batch_run_pinned(aw_spatializer *sp, int64_t frames, bool meter
     const LwCallPlan lw = sp_begin_call(sp, frames, pos0);
     aw_status st = metered ? lv_begin_call(sp, frames, false) : AW_OK;
     if (st == AW_OK) st = sp_run_streams(sp, lw, 0, 1, sp->h_pin_in.get(), sp->h_pin_out.get(), frames);
+    if (st == AW_OK && metered && sp->eq.n_presets) st = eq_run(sp, sp->h_pin_out.get(), 0, 1, frames);      // in place over PCIe, like the kernels in front of it
     if (st == AW_OK && metered && sp->ld.on)             // the loudness kernels read the page-locked output as the convolution kernels wrote it
         st = ld_measure(sp, sp->h_pin_out.get(), 0, 1, frames, ld_begin_call(sp, frames));
     const bool tp = metered && tp_runs(sp);
@@ -1877,7 +1918,8 @@ aw_status aw_spatializer_reset(aw_spatializer *sp) try {
     const size_t n = (size_t)sp->n_streams * sp->hist_len * sp->n_channels;
     for (int i = 0; i < 2; ++i)
         AW_HIP_TRY(hipMemsetAsync(sp->d_hist[i].get(), 0, std::max<size_t>(n, 1) * sizeof(float), sp->ctx->stream));
-    return lv_reset(sp);
+    const aw_status st = eq_reset(sp);
+    return st == AW_OK ? lv_reset(sp) : st;
 } AW_NOEXCEPT_TAIL
 
 aw_status aw_spatializer_set_metering(aw_spatializer *sp, int32_t on) try {
@@ -1959,6 +2001,67 @@ aw_status aw_spatializer_set_loudness(aw_spatializer *sp, int32_t on, double max
         AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));            // (the upload reads `tables`)
     }
     sp->ld.on = true;
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+// Checks and the presets' tables first (a refusal leaves the stage as it was), then the one allocation and the upload (here, never on
+// the process path).  Every call that installs presets starts the filter state from zero.
+aw_status aw_spatializer_set_equalizer(aw_spatializer *sp, const aw_eq_definition *const *definitions, int32_t n_definitions,
+                                       const int32_t *stream_definition) try {
+    if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
+    if (n_definitions < 0) return fail(AW_ERR_INVALID_ARGUMENT, "n_definitions must be >= 0");
+    if (n_definitions > 0 && !definitions) return fail(AW_ERR_INVALID_ARGUMENT, "definitions is NULL");
+    for (int32_t i = 0; i < n_definitions; ++i)
+        if (!definitions[i]) return fail(AW_ERR_INVALID_ARGUMENT, "definition " + std::to_string(i) + " is NULL");
+    for (int s = 0; stream_definition && n_definitions > 0 && s < sp->n_streams; ++s)
+        if (stream_definition[s] < -1 || stream_definition[s] >= n_definitions)
+            return fail(AW_ERR_INVALID_ARGUMENT, "stream_definition[" + std::to_string(s) + "] = " + std::to_string(stream_definition[s]) + " is outside [-1, n_definitions)");
+    std::vector<awh::EqPrepared> prep((size_t)n_definitions);
+    int kmax = 0;
+    size_t table_doubles = 0;
+    for (int32_t i = 0; i < n_definitions; ++i) {
+        const aw_status st = awr::eq_prepare_checked(&definitions[i]->def, sp->sample_rate, prep[(size_t)i]);
+        if (st != AW_OK) {
+            awr::set_error(std::string(aw_last_error_message()) + " (definition " + std::to_string(i) + ")");
+            return st;
+        }
+        kmax = std::max(kmax, prep[(size_t)i].n_filters);
+        table_doubles += prep[(size_t)i].tab.size() + prep[(size_t)i].plane.size();
+    }
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));                // whatever still reads the old state, tables or image
+    if (n_definitions == 0) {
+        sp->eq.n_presets = sp->eq.kmax = 0; sp->eq.table_doubles = 0;
+        (void)sp->eq.d.reset();
+        sp->eq.image.clear();
+        return AW_OK;
+    }
+    const awst::Equalizer L{{(size_t)sp->n_streams}, (size_t)n_definitions, (size_t)kmax, table_doubles};
+    // what lies behind the state, as the layout states it: the map, the headers, then every preset's tab and plane
+    std::vector<unsigned char> image(L.total - L.map.off, 0);
+    auto at = [&](size_t off) { return image.data() + (off - L.map.off); };          // (every field starts on a multiple of 8 bytes but the map's end)
+    int32_t *const map = reinterpret_cast<int32_t *>(at(L.map.off));
+    awk::EqStagePreset *const headers = reinterpret_cast<awk::EqStagePreset *>(at(L.presets.off));
+    double *const tables = reinterpret_cast<double *>(at(L.tables.off));
+    for (int s = 0; s < sp->n_streams; ++s) map[s] = stream_definition ? stream_definition[s] : 0;
+    long long off = 0;
+    for (int32_t i = 0; i < n_definitions; ++i) {
+        const awh::EqPrepared &q = prep[(size_t)i];
+        awk::EqStagePreset &h = headers[i];
+        h.preamp = q.preamp; h.n_filters = q.n_filters; h.reserved = 0;
+        h.tab_off = off; h.plane_off = off + (long long)q.tab.size();
+        if (!q.tab.empty()) std::memcpy(tables + h.tab_off, q.tab.data(), q.tab.size() * sizeof(double));
+        if (!q.plane.empty()) std::memcpy(tables + h.plane_off, q.plane.data(), q.plane.size() * sizeof(double));
+        off += (long long)(q.tab.size() + q.plane.size());
+    }
+    awr::Buf<unsigned char> d;
+    const aw_status st = stage_alloc(sp, &d, L.total, L.reset_bytes);
+    if (st != AW_OK) return st;
+    AW_HIP_TRY(hipMemcpyAsync(d.get() + L.map.off, image.data(), image.size(), hipMemcpyHostToDevice, sp->ctx->stream));
+    sp->eq.d = std::move(d);
+    sp->eq.image = std::move(image);                                  // (the copy may still read it: it stays until the next setter call has synchronised)
+    sp->eq.n_presets = n_definitions; sp->eq.kmax = kmax; sp->eq.table_doubles = table_doubles;
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 

@@ -12,6 +12,7 @@
 #include "../../include/airwave_hip.h"
 #include "device/kernels.hpp"
 #include "host/device_buf.hpp"
+#include "host/eq.hpp"
 #include "host/stage_records.hpp"
 
 namespace awr {
@@ -20,6 +21,8 @@ void set_error(const std::string &msg);
 aw_status fail(aw_status code, const std::string &msg);
 aw_status fail_eq_filter(int enabled_index, int kind, int source_line, const std::string &msg);      // AW_ERR_EQ_INVALID_FILTER + aw_last_eq_filter_error
 aw_status hip_fail(hipError_t e, const char *what);
+// awh::eq_prepare of a definition (NULL: unity) with its refusals as the statuses and messages aw_eq_state_create gives (eq_runtime.cpp)
+aw_status eq_prepare_checked(const awh::EqDefinition *def, double sample_rate, awh::EqPrepared &prep);
 bool context_literal_resampler(const aw_context *ctx);
 // The C ABI promises "no exceptions": every entry point that can allocate host memory (containers, strings, threads) is a
 // function-try-block whose handler returns caught() — std::bad_alloc / std::length_error become AW_ERR_OUT_OF_MEMORY, anything else
@@ -62,6 +65,10 @@ struct aw_context {
     CopyPool *copy_pool = nullptr;                                  // made with the pipeline objects; pageable caller buffers are bounced through page-locked chunks by it
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     awr::Event ev_h2d[2], ev_run[2], ev_d2h[2];
+};
+
+struct aw_eq_definition {
+    awh::EqDefinition def;
 };
 
 struct aw_hrir {
@@ -127,6 +134,11 @@ struct aw_spatializer {
         int cur = 0; bool ran = false;                // ran: this call queued the stage's kernel, so its history slot is the next call's
         void end_call(bool queued = true) { if (ran && queued) cur ^= 1; ran = false; }
     };
+    // aw_spatializer_set_equalizer: the one stage in front of the meters; rules: device/eq_stage.hpp.  n_presets > 0: the stage is on
+    struct Equalizer : Stage {
+        int n_presets = 0, kmax = 0; size_t table_doubles = 0;
+        std::vector<unsigned char> image;             // what the setter uploads behind the state (map, headers, tables): kept while the copy may read it
+    } eq;
     struct Levels : Stage {                           // aw_spatializer_set_metering / _set_gain (either makes d); rules: device/levels.hpp
         bool metering = false;
         int gain_mode = 0; float gain_ceiling = 1.0f; // aw_gain_mode

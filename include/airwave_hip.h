@@ -427,7 +427,8 @@ AW_API int32_t aw_spatializer_channel_count(const aw_spatializer *sp);
  * 18 frames processed since create / the last aw_spatializer_reset (the dither's frame position, aw_spatializer_set_dither),
  * 19 the level meter is on (aw_spatializer_set_metering), 20 the aw_gain_mode of the batch entries (aw_spatializer_set_gain),
  * 21 the loudness measurement is on (aw_spatializer_set_loudness), 22 the true-peak measurement is on (aw_spatializer_set_true_peak),
- * 23 the limiter is on (aw_spatializer_set_limiter), 24 its latency D in frames (0 while it is off). */
+ * 23 the limiter is on (aw_spatializer_set_limiter), 24 its latency D in frames (0 while it is off),
+ * 25 presets of the equalizer stage (aw_spatializer_set_equalizer; 0: the stage is off), 26 the largest enabled-filter count among them. */
 AW_API int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what);
 /* Average device time of the dominant kernel over the launches since the last call (HIP events
  * on the context stream); used for bench.py's roofline object.  Returns launches counted. */
@@ -603,6 +604,30 @@ AW_API double aw_eq_state_preamp_linear(const aw_eq_state *s);
 AW_API aw_status aw_eq_fold_hrir(const aw_eq_definition *definition_or_null, double sample_rate, const float *tracks, int32_t n_tracks,
                                  int32_t taps, double tail_tolerance, int32_t max_taps, float *out_tracks, int32_t *out_taps,
                                  int32_t *response_taps, double *tail_bound);
+
+/* Equalizer of the batch entries (the reference's graph order: spatializer, then equalizer — AudioEffectGraph.swift:195-211;
+ * one preset per output device — DeviceProfileManager).  definitions[0 .. n_definitions): the presets; stream_definition[s], s < stream count:
+ * the preset of stream s, -1 = this stream is not equalized; NULL = every stream takes preset 0.  n_definitions == 0 switches the stage off.
+ * Runs at the spatializer's sample rate (the HRIR's).
+ *  - arithmetic: both ears of an equalized stream's convolution output go through ParametricEqualizerState.process of its preset
+ *    (:58-91: preamp, the enabled biquads in Float64, one rounding to float32, the subnormal flush), bit for bit what aw_eq_state_process
+ *    over the same calls gives; the Float64 state is carried from call to call.  A stream mapped to -1 keeps its samples.
+ *  - position: in the four batch entries (aw_spatializer_process, _process_pcm, _process_host, _process_host_pcm), between the convolution
+ *    and the first meter, in place — loudness, true peak, levels, every gain mode, the limiter, the dither and the encode see the equalized
+ *    signal.  aw_spatializer_process_planar does not run it: the plug-in path has aw_eq, with its crossfades.
+ *  - with the stage off a call queues what it queued before this entry existed, and every output bit is the same.
+ *  - chunking a batch by streams (AW_HOST_CHUNK_MB), sample formats, pinned or pageable buffers and sharding over handles change no bit;
+ *    splitting calls in time moves the kernel's chunk boundaries and changes the last bit of some samples (reassociation in Float64).
+ *  - state: aw_spatializer_reset zeroes the filter state; every call that installs presets does too.  There is no crossfade between two
+ *    settings: a target that changes while audio plays is aw_eq's business (aw_eq_set_target, below).
+ *  - the definitions are read during the call and not kept.  The call makes the stage's one device allocation (state, map, tables); no
+ *    batch entry allocates for it afterwards, and it needs no staging.  Do not call it while a process call on the same handle is running.
+ * Errors: a preset that cannot be prepared returns what aw_eq_state_create returns for it (AW_ERR_EQ_*; aw_last_eq_filter_error for a bad
+ * filter) and aw_last_error_message() also names the definition's index.  A NULL handle, n_definitions < 0, NULL definitions with
+ * n_definitions > 0, a NULL entry, or a map entry outside [-1, n_definitions) returns AW_ERR_INVALID_ARGUMENT.  A call that fails leaves
+ * the previous stage as it was. */
+AW_API aw_status aw_spatializer_set_equalizer(aw_spatializer *sp, const aw_eq_definition *const *definitions, int32_t n_definitions,
+                                              const int32_t *stream_definition);
 
 /* ParametricEqualizerProcessor  :116-408: starts at unity; aw_eq_set_target prepares and publishes a
  * target that the next process call crossfades to over max(1, round(0.020 * sample_rate)) frames

@@ -150,6 +150,12 @@ class Spatializer {
         check(aw_spatializer_get_limiter(h_, 0, (int32_t)out.size(), out.data()));
         return out;
     }
+    // equalizer stage of the batch entries, one preset per stream (EqualizerDefinition::get(), below); streamDefinition empty: every stream
+    // takes preset 0, else one entry per stream (-1: not equalized); no definitions: the stage is off
+    void setEqualizer(const std::vector<const aw_eq_definition *> &definitions, const std::vector<int32_t> &streamDefinition = {}) {
+        if (!streamDefinition.empty() && streamDefinition.size() != (size_t)aw_spatializer_stream_count(h_)) throw Error(AW_ERR_INVALID_ARGUMENT, "streamDefinition needs one entry per stream");
+        check(aw_spatializer_set_equalizer(h_, definitions.data(), (int32_t)definitions.size(), streamDefinition.empty() ? nullptr : streamDefinition.data()));
+    }
     int64_t info(int32_t what) const { return aw_spatializer_info(h_, what); }
     void reset() { check(aw_spatializer_reset(h_)); }
     aw_spatializer *get() const { return h_; }
