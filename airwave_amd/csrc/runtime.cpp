@@ -21,6 +21,7 @@
 #include "device/truepeak_kernels.hpp"
 #include "host/eq.hpp"
 #include "host/path_policy.hpp"
+#include "host/scratch_plan.hpp"
 #include "host/tables.hpp"
 
 // table sets a spatializer can hold: one per long-window length (awp::kLwRowChoices); lw_plans reserves this many at create
@@ -703,24 +704,40 @@ aw_status aw_spatializer_debug_stamps(aw_spatializer *sp, uint64_t *host_out, in
 #endif
 } AW_NOEXCEPT_TAIL
 
-static void sp_fill_cfg(const aw_spatializer *sp, awk::TileParams &p) {
+// What the fused and the partitioned launches share, for the streams of the spatializer from `first_stream` on (`in` / `out` at its frames).
+static awk::TileParams sp_tile_params(const aw_spatializer *sp, long long first_stream, const float *in, float *out, int64_t frames) {
     const awk::LaunchCfg &c = sp->ctx->cfg;
-    p.persistent_wgs = c.persistent_wgs; p.wide_two_pass = c.wide_two_pass;
-    p.debug_occupancy = c.debug_occupancy;
+    awk::TileParams p{};
+    p.in = in; p.out = out; p.hist = sp->d_hist[sp->hist_cur].get() + (size_t)first_stream * sp->hist_len * sp->n_channels;
+    p.tab = sp->d_tab.get(); p.tw1 = sp->ctx->d_tw1.get(); p.twa = sp->ctx->d_twa.get(); p.twb = sp->ctx->d_twb.get(); p.zeros = sp->ctx->d_zeros.get();
+    p.frames = frames; p.n_channels = sp->n_channels; p.n_pairs = sp->n_pairs;
+    p.hop = sp->hop; p.hist_len = sp->hist_len; p.tiles_per_stream = (int)((frames + sp->hop - 1) / sp->hop);
+    p.persistent_wgs = c.persistent_wgs; p.wide_two_pass = c.wide_two_pass; p.debug_occupancy = c.debug_occupancy;
+    return p;
 }
+
+// The timed unit of the chunked paths is the whole pipeline of one stream chunk: an event pair around its launches (kernel_time) and
+// the timer its launchers stamp every kernel with (stage_times).  Both do nothing while profiling is off.
+struct SpChunkTimer {
+    aw_spatializer *sp; hipEvent_t e0 = nullptr, e1 = nullptr; SpStageTimer tm;
+    explicit SpChunkTimer(aw_spatializer *s) : sp(s), tm(s) {}
+    awk::StageTimer *stages() { return sp->profiling ? &tm : nullptr; }
+    hipError_t begin() {
+        if (sp->profiling) { e0 = sp_get_event(sp); e1 = sp_get_event(sp); }
+        return sp->profiling ? hipEventRecord(e0, sp->ctx->stream) : hipSuccess;
+    }
+    hipError_t end() {
+        const hipError_t e = sp->profiling ? hipEventRecord(e1, sp->ctx->stream) : hipSuccess;
+        if (sp->profiling && e == hipSuccess) sp->pending.emplace_back(e0, e1);
+        return e;
+    }
+};
 
 // Every sp_process_* below runs ONE call's kernels for the streams [s_base, s_base + ns_total) of the spatializer; `in` / `out` point at
 // stream s_base's frames (the caller's whole batch with s_base = 0, or one staged chunk of the host-entry pipeline).
 static aw_status sp_process_fused(aw_spatializer *sp, int s_base, int ns_total, const float *in, float *out, int64_t frames) {
-    awk::TileParams p{};
-    p.in = in; p.out = out; p.hist = sp->d_hist[sp->hist_cur].get() + (size_t)s_base * sp->hist_len * sp->n_channels;
-    p.tab = sp->d_tab.get(); p.tw1 = sp->ctx->d_tw1.get(); p.twa = sp->ctx->d_twa.get(); p.twb = sp->ctx->d_twb.get(); p.zeros = sp->ctx->d_zeros.get();
-    p.frames = frames; p.n_channels = sp->n_channels; p.n_pairs = sp->n_pairs;
-    p.hop = sp->hop; p.hist_len = sp->hist_len;
-    p.tiles_per_stream = (int)((frames + sp->hop - 1) / sp->hop);
-    p.dbg = nullptr;
+    awk::TileParams p = sp_tile_params(sp, s_base, in, out, frames);
     p.stagger = sp->ctx->cfg.stamp_thread;
-    sp_fill_cfg(sp, p);
 #if defined(AW_STAMPS) && AW_STAMPS
     {
         const long long nwg = (long long)ns_total * p.tiles_per_stream;
@@ -757,95 +774,45 @@ static aw_status sp_process_fused(aw_spatializer *sp, int s_base, int ns_total, 
     return AW_OK;
 }
 
-// Scratch of the partitioned path for calls of `frames` frames: window spectra + accumulated W of one stream chunk.
-// Grow-only; aw_spatializer_reserve() sizes it ahead of time so that process never allocates.
-struct PartPlan { int n_blocks; long long n_windows; size_t per_stream, per_stream_w; long long chunk; size_t need; };
-
-// held_elems > 0 (a call inside what aw_spatializer_reserve() sized): the stream chunk is clamped to the buffer that is already
-// there, so that process never reallocates — a short call would otherwise pick a larger chunk whose rounding can exceed it.
-static PartPlan part_plan(const aw_spatializer *sp, int64_t frames, size_t budget_bytes, size_t held_elems = 0) {
-    PartPlan pl{};
-    const int N = awk::kN, B = sp->hop, P = sp->partitions;
-    pl.n_blocks = (int)((frames + B - 1) / B);
-    pl.n_windows = (long long)pl.n_blocks + P - 1;
-    pl.per_stream = (size_t)pl.n_windows * sp->n_pairs * N;          // complex elements of window spectra
-    pl.per_stream_w = (size_t)pl.n_blocks * N;                       // complex elements of accumulated W
-    pl.chunk = (long long)(budget_bytes / ((pl.per_stream + pl.per_stream_w) * sizeof(awk::cf)));
-    const long long held_chunk = (long long)(held_elems / (pl.per_stream + pl.per_stream_w));
-    if (held_chunk >= 1 && pl.chunk > held_chunk) pl.chunk = held_chunk;
-    if (pl.chunk < 1) pl.chunk = 1;
-    if (pl.chunk > sp->n_streams) pl.chunk = sp->n_streams;
-    if (pl.chunk > 65535) pl.chunk = 65535;                          // grid.y / grid.z of the CMAC launches
-    pl.need = (pl.per_stream + pl.per_stream_w) * (size_t)pl.chunk;
-    return pl;
-}
-
-// Budget: AW_SPEC_SCRATCH_MB (read at create), else min(64 GiB, 40 % of the device memory free when first needed) —
-// sized for 288 GB of HBM: cfg 3 (1024 streams x 10 s, 4 pairs, 8 partitions) needs 40 GB and runs as one chunk.
-static size_t part_budget(aw_spatializer *sp) {
+// The scratch of the partitioned and the long-window kernels is the CONTEXT's pool (runtime.hpp): grow-only, the largest need of any
+// spatializer created on the context; aw_spatializer_reserve() sizes it ahead of time so that process never allocates.  What a call needs
+// and its streams per chunk: host/scratch_plan.hpp.  Budget: AW_SPEC_SCRATCH_MB (read at create), else of the memory free when first needed.
+static size_t sp_scratch_budget(aw_spatializer *sp) {
+    size_t free_b = 0, total_b = 0;
     if (sp->scratch_budget == 0) {
-        size_t free_b = 0, total_b = 0;
-        size_t b = (size_t)6 << 30;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) b = std::min<size_t>((size_t)64 << 30, free_b / 5 * 2);
-        sp->scratch_budget = std::max<size_t>(b, (size_t)64 << 20);
+        const bool known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+        sp->scratch_budget = awp::default_budget(known, free_b);
     }
     return sp->scratch_budget;
 }
-
-// The scratch is the CONTEXT's pool (runtime.hpp): grow-only, the largest need of any spatializer created on the context.
-static aw_status part_ensure_scratch(aw_spatializer *sp, size_t need) {
-    aw_context *c = sp->ctx;
-    if (c->d_pool.capacity() >= need) return AW_OK;
-    return pool_grow(c, need);
-}
+static aw_status sp_ensure_scratch(aw_spatializer *sp, size_t need) { return sp->ctx->d_pool.capacity() >= need ? AW_OK : pool_grow(sp->ctx, need); }
 // the buffer a call inside what aw_spatializer_reserve() sized may count on (its stream chunk is clamped to it: never a reallocation)
 static size_t sp_held_scratch(const aw_spatializer *sp, int64_t frames) { return frames <= sp->reserved_frames ? sp->ctx->d_pool.capacity() : 0; }
 
 static aw_status sp_process_partitioned(aw_spatializer *sp, int s_base, int ns_total, const float *in, float *out, int64_t frames) {
-    const int N = awk::kN, B = sp->hop, P = sp->partitions;
-    const PartPlan pl = part_plan(sp, frames, part_budget(sp), sp_held_scratch(sp, frames));
-    const int n_blocks = pl.n_blocks;
-    const long long chunk = pl.chunk;
-    aw_status st = part_ensure_scratch(sp, pl.need);
+    const awp::PartScratch pl = awp::part_scratch(sp_layout(sp), sp_plan(sp), frames, sp_scratch_budget(sp), sp_held_scratch(sp, frames));
+    aw_status st = sp_ensure_scratch(sp, pl.need);
     if (st != AW_OK) return st;
     awk::cf *const d_spec = sp->ctx->d_pool.get();
     sp->dominant_frames = 0;
-    for (long long s0 = 0; s0 < ns_total; s0 += chunk) {
-        const int ns = (int)std::min<long long>(chunk, ns_total - s0);
-        awk::TileParams p{};
-        p.in = in + (size_t)s0 * frames * sp->n_channels;
-        p.out = out + (size_t)s0 * frames * 2;
-        p.hist = sp->d_hist[sp->hist_cur].get() + (size_t)(s_base + s0) * sp->hist_len * sp->n_channels;
-        p.tab = sp->d_tab.get(); p.tw1 = sp->ctx->d_tw1.get(); p.twa = sp->ctx->d_twa.get(); p.twb = sp->ctx->d_twb.get(); p.zeros = sp->ctx->d_zeros.get();
-        p.frames = frames; p.n_channels = sp->n_channels; p.n_pairs = sp->n_pairs;
-        p.hop = B; p.hist_len = sp->hist_len; p.tiles_per_stream = n_blocks;
-        p.spec = d_spec; p.wspec = d_spec + pl.per_stream * (size_t)chunk;
-        p.partitions = P; p.n_blocks = n_blocks; p.first_valid = N - B;
-        p.stagger = 0; p.dbg = nullptr;
-        sp_fill_cfg(sp, p);
+    for (long long s0 = 0; s0 < ns_total; s0 += pl.chunk) {
+        const int ns = (int)std::min<long long>(pl.chunk, ns_total - s0);
+        awk::TileParams p = sp_tile_params(sp, s_base + s0, in + (size_t)s0 * frames * sp->n_channels, out + (size_t)s0 * frames * 2, frames);
+        p.spec = d_spec; p.wspec = d_spec + pl.wspec_at();
+        p.partitions = sp->partitions; p.n_blocks = pl.n_blocks; p.first_valid = awk::kN - sp->hop;
         p.fwd_one_pair = sp->fwd_one_pair ? 1 : 0;
         p.herm_last = (!sp->cmac_group && sp->herm_ok && (sp->n_channels & 1)) ? 1 : 0;
-        // the timed unit of this path is the whole three-kernel pipeline of one stream chunk
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (sp->profiling) {
-            e0 = sp_get_event(sp); e1 = sp_get_event(sp);
-            AW_HIP_TRY(hipEventRecord(e0, sp->ctx->stream));
-        }
-        SpStageTimer tm(sp);
-        awk::StageTimer *tmp = sp->profiling ? &tm : nullptr;
-        AW_HIP_TRY(awk::launch_part_forward(p, ns, sp->ctx->stream, tmp));
-        if (sp->cmac_group) AW_HIP_TRY(awk::launch_part_cmac(p, ns, sp->ctx->stream, tmp));
-        else AW_HIP_TRY(awk::launch_part_march(p, ns, sp->ctx->stream, tmp));
-        AW_HIP_TRY(awk::launch_part_inverse(p, ns, sp->ctx->stream, tmp));
-        if (sp->profiling) {
-            AW_HIP_TRY(hipEventRecord(e1, sp->ctx->stream));
-            sp->pending.emplace_back(e0, e1);
-        }
+        SpChunkTimer timer(sp);          // (the three-kernel pipeline of one stream chunk)
+        AW_HIP_TRY(timer.begin());
+        AW_HIP_TRY(awk::launch_part_forward(p, ns, sp->ctx->stream, timer.stages()));
+        if (sp->cmac_group) AW_HIP_TRY(awk::launch_part_cmac(p, ns, sp->ctx->stream, timer.stages()));
+        else AW_HIP_TRY(awk::launch_part_march(p, ns, sp->ctx->stream, timer.stages()));
+        AW_HIP_TRY(awk::launch_part_inverse(p, ns, sp->ctx->stream, timer.stages()));
+        AW_HIP_TRY(timer.end());
         sp->dominant_frames = (long long)ns * frames;
     }
     return AW_OK;
 }
-
 
 /* ---- long-window path (device/tile_lw.hpp) ---------------------------------------------------- */
 // Per call: windows of N = R x 4096 frames (R = 8 RA rows), hop = N - hist_len; hist_len is the history the spatializer's
@@ -924,57 +891,21 @@ static aw_status lw_get_plan(aw_spatializer *sp, int R, const aw_spatializer::Lw
     return AW_OK;
 }
 
-// scratch of one stream chunk: rows of every (stream, window) + s1/s2
-struct LwScratch { long long n_windows; size_t per_stream; long long chunk; size_t need; long long spec_per_sw; };
-static LwScratch lw_scratch(const aw_spatializer *sp, int R, long long n_windows, size_t budget_bytes, size_t held_elems) {
-    LwScratch r{};
-    const long long N = (long long)R * awk::kLwM;
-    const int real_last = sp->n_channels & 1;
-    r.n_windows = n_windows;
-    const int n_pairs = (sp->n_channels + 1) / 2;                         // (a fused2 spatializer's n_pairs counts pseudo-pairs)
-    r.spec_per_sw = (long long)(n_pairs - real_last) * N + (real_last ? N / 2 : 0);
-    r.per_stream = (size_t)r.n_windows * (size_t)(r.spec_per_sw + N);
-    r.chunk = (long long)(budget_bytes / sizeof(awk::cf) / r.per_stream);
-    const long long held_chunk = (long long)(held_elems / r.per_stream);       // see part_plan
-    if (held_chunk >= 1 && r.chunk > held_chunk) r.chunk = held_chunk;
-    if (r.chunk < 1) r.chunk = 1;
-    if (r.chunk > sp->n_streams) r.chunk = sp->n_streams;
-    r.need = r.per_stream * (size_t)r.chunk;
-    return r;
-}
-// the stream chunk and scratch of a whole call plan: every group of the plan runs on the same chunk of streams
-static LwScratch lw_plan_scratch(const aw_spatializer *sp, const LwCallPlan &plan, size_t budget_bytes, size_t held_elems, LwScratch (&per_group)[2]) {
-    LwScratch all{};
-    all.chunk = sp->n_streams;
-    for (int i = 0; i < plan.n_groups; ++i) {
-        per_group[i] = lw_scratch(sp, plan.g[i].R, plan.g[i].n_windows, budget_bytes, held_elems);
-        all.chunk = std::min(all.chunk, per_group[i].chunk);
-    }
-    for (int i = 0; i < plan.n_groups; ++i) all.need = std::max(all.need, per_group[i].per_stream * (size_t)all.chunk);
-    return all;
-}
-
 static aw_status sp_process_longwin(aw_spatializer *sp, const LwCallPlan &call, int s_base, int ns_total, const float *in, float *out, int64_t frames) {
     const aw_spatializer::LwPlan *tables[2] = {nullptr, nullptr};
     for (int i = 0; i < call.n_groups; ++i) {
         aw_status st = lw_get_plan(sp, call.g[i].R, &tables[i]);
         if (st != AW_OK) return st;
     }
-    LwScratch per_group[2];
-    const LwScratch sc = lw_plan_scratch(sp, call, part_budget(sp), sp_held_scratch(sp, frames), per_group);
-    aw_status st = part_ensure_scratch(sp, sc.need);
+    const auto sc = awp::lw_plan_scratch(sp_layout(sp), call, sp_scratch_budget(sp), sp_held_scratch(sp, frames));
+    aw_status st = sp_ensure_scratch(sp, sc.need);
     if (st != AW_OK) return st;
     awk::cf *const d_spec = sp->ctx->d_pool.get();
     sp->dominant_frames = 0;
     for (long long s0 = 0; s0 < ns_total; s0 += sc.chunk) {
         const int ns = (int)std::min<long long>(sc.chunk, ns_total - s0);
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (sp->profiling) {
-            e0 = sp_get_event(sp); e1 = sp_get_event(sp);
-            AW_HIP_TRY(hipEventRecord(e0, sp->ctx->stream));
-        }
-        SpStageTimer tm(sp);
-        awk::StageTimer *tmp = sp->profiling ? &tm : nullptr;
+        SpChunkTimer timer(sp);
+        AW_HIP_TRY(timer.begin());
         if (sp->n_channels > 8)          // the wide split kernel reads the last frame of the last stream from a padded copy (allocated at create)
             AW_HIP_TRY(hipMemcpyAsync(sp->d_tail.get(), in + ((size_t)(s0 + ns) * frames - 1) * sp->n_channels, sp->n_channels * sizeof(float),
                                       hipMemcpyDefault, sp->ctx->stream));          // (`in` is device memory, or the page-locked staging of a one-stream call)
@@ -983,8 +914,7 @@ static aw_status sp_process_longwin(aw_spatializer *sp, const LwCallPlan &call, 
             const aw_spatializer::LwPlan *plan = tables[gi];
             const long long N = (long long)g.R * awk::kLwM;
             awk::LwParams p{};
-            p.in = in + (size_t)s0 * frames * sp->n_channels;
-            p.out = out + (size_t)s0 * frames * 2;
+            p.in = in + (size_t)s0 * frames * sp->n_channels; p.out = out + (size_t)s0 * frames * 2;
             p.hist = sp->d_hist[sp->hist_cur].get() + (size_t)(s_base + s0) * sp->hist_len * sp->n_channels;
             // the tail carry rides along in the split kernel of the LAST group: its last window spans the last hist_len frames of the call
             p.hist_out = gi == call.n_groups - 1 ? sp->d_hist[sp->hist_cur ^ 1].get() + (size_t)(s_base + s0) * sp->hist_len * sp->n_channels : nullptr;
@@ -993,8 +923,8 @@ static aw_status sp_process_longwin(aw_spatializer *sp, const LwCallPlan &call, 
             p.n_channels = sp->n_channels; p.n_pairs = (sp->n_channels + 1) / 2; p.real_last = sp->n_channels & 1;
             p.hist_len = sp->hist_len; p.hop = (int)(N - sp->hist_len); p.n_windows = g.n_windows;
             p.R = g.R; p.N = (int)N;
-            p.spec = d_spec; p.spec_per_sw = per_group[gi].spec_per_sw;
-            p.wrows = d_spec + (size_t)sc.chunk * g.n_windows * per_group[gi].spec_per_sw;
+            p.spec = d_spec; p.spec_per_sw = sc.g[gi].spec_per_sw;
+            p.wrows = d_spec + sc.g[gi].wrows_at(sc.chunk);
             p.tab = plan->d_tab.get(); p.tw_coarse = plan->d_coarse.get(); p.tw_fine = plan->d_fine.get(); p.tw_step = plan->d_step.get(); p.tw_r = plan->d_tw_r.get(); p.tw1m = plan->d_tw1m.get();
             p.twa = sp->ctx->d_twa.get(); p.twb = sp->ctx->d_twb.get();
             p.persistent_wgs = sp->ctx->cfg.persistent_wgs;
@@ -1002,14 +932,11 @@ static aw_status sp_process_longwin(aw_spatializer *sp, const LwCallPlan &call, 
             p.rows_form = plan->d_tab16 ? 16 : 8; p.tab16 = plan->d_tab16.get(); p.tw2 = plan->d_tw2.get(); p.rows16_wgs = sp->ctx->cfg.lw_rows16_wgs;
             p.n_streams = ns;
             p.tail = sp->n_channels > 8 ? sp->d_tail.get() : nullptr;
-            AW_HIP_TRY(awk::launch_lw_split(p, ns, sp->ctx->stream, tmp));
-            AW_HIP_TRY(awk::launch_lw_rows(p, ns, sp->ctx->stream, tmp));
-            AW_HIP_TRY(awk::launch_lw_merge(p, ns, sp->ctx->stream, tmp));
+            AW_HIP_TRY(awk::launch_lw_split(p, ns, sp->ctx->stream, timer.stages()));
+            AW_HIP_TRY(awk::launch_lw_rows(p, ns, sp->ctx->stream, timer.stages()));
+            AW_HIP_TRY(awk::launch_lw_merge(p, ns, sp->ctx->stream, timer.stages()));
         }
-        if (sp->profiling) {
-            AW_HIP_TRY(hipEventRecord(e1, sp->ctx->stream));
-            sp->pending.emplace_back(e0, e1);
-        }
+        AW_HIP_TRY(timer.end());
         sp->dominant_frames = (long long)ns * frames;
     }
     return AW_OK;
@@ -1020,25 +947,6 @@ static aw_status sp_process_longwin(aw_spatializer *sp, const LwCallPlan &call, 
 static constexpr int64_t kZeroCopyFrames = 16384;
 static bool sp_zero_copy(const aw_spatializer *sp, int64_t frames) {
     return sp->n_streams == 1 && frames <= kZeroCopyFrames && sp->h_pin_in.capacity() >= (size_t)frames * sp->n_channels && sp->h_pin_out.capacity() >= (size_t)frames * 2;
-}
-
-// The longest call of at most max_frames frames that the policy (lw_choose with every window length available) leaves to the partitioned
-// kernels (0: none; a path-0 spatializer never runs them).  A reserved spatializer only has the window lengths of its reserve() plan, so a
-// call well short of max_frames may still come to the partitioned kernels beyond this length: it then runs in stream chunks clamped to the
-// pool (part_plan), correct and a little slower — what reserve() buys is no allocation, and the full rate at the length it was asked for.  Scanned in steps of whole blocks; with more than 2048
-// candidate lengths the scan strides and answers one stride longer, i.e. never too short.
-static int64_t part_longest_call(const aw_spatializer *sp, int64_t max_frames) {
-    if (sp->path != 1) return 0;
-    const int64_t B = sp->hop, n_blocks = (max_frames + B - 1) / B;
-    const int64_t stride = std::max<int64_t>(1, n_blocks / 2048);
-    int64_t longest = 0;
-    const awp::LwInputs in = lw_inputs(sp);
-    for (int64_t nb = 1;; nb += stride) {
-        const int64_t f = std::min<int64_t>(std::min(nb, n_blocks) * B, max_frames);
-        if (!awp::lw_choose(in, f, true).n_groups) longest = std::min<int64_t>(f + (stride - 1) * B, max_frames);
-        if (nb >= n_blocks) break;
-    }
-    return longest;
 }
 
 // Sizes every grow-only device buffer for calls of up to max_frames frames, so that the process entries never
@@ -1059,23 +967,9 @@ aw_status aw_spatializer_reserve(aw_spatializer *sp, int64_t max_frames) try {
         // From here on a call of up to max_frames frames chooses only among the window lengths whose tables exist (lw_choose).
         const int64_t reserved_before = sp->reserved_frames;
         sp->reserved_frames = std::max<int64_t>(sp->reserved_frames, max_frames);
-        size_t need = 0;
-        if (lw_res.n_groups) {
-            LwScratch per_group[2];
-            need = lw_plan_scratch(sp, lw_res, part_budget(sp), 0, per_group).need;
-        }
-        if (sp->path == 1) {
-            // Shorter calls may still run on the partitioned kernels: size for the longest call lw_choose() leaves to them (cfg 3: 45 056
-            // of 480 000 frames, 4 GB — round 4 sized for max_frames on BOTH kernel sets: 41.5 GB where the long-window kernels need 19),
-            // and for ONE stream of max_frames whatever the policy says (a call inside the reserved size clamps its stream chunk to the
-            // buffer that is there, part_plan / lw_scratch: it never reallocates).
-            const int64_t longest = part_longest_call(sp, sp->reserved_frames);
-            if (longest > 0) need = std::max(need, part_plan(sp, longest, part_budget(sp)).need);
-            const PartPlan one = part_plan(sp, sp->reserved_frames, part_budget(sp));
-            need = std::max(need, one.per_stream + one.per_stream_w);
-        }
+        const size_t need = awp::reserve_need(lw_inputs(sp), lw_res, sp->reserved_frames, sp_scratch_budget(sp)).need;
         const auto t0 = std::chrono::steady_clock::now();
-        aw_status st = part_ensure_scratch(sp, need);
+        aw_status st = sp_ensure_scratch(sp, need);
         if (st == AW_OK) {
             const hipError_t es = hipStreamSynchronize(sp->ctx->stream);
             if (es != hipSuccess) st = awr::hip_fail(es, "hipStreamSynchronize (reserve)");
@@ -1405,17 +1299,6 @@ static aw_status lim_host_call(aw_spatializer *sp, float *y, int64_t frames, flo
  * through page-locked chunks by the context's copy threads (below).  aw_spatializer_reserve_host() sizes the device-side chunk buffers
  * and the bounce chunks ahead of time; without it they grow on the first call.  The kernels of a chunk are the batch entries' one chunk
  * step (batch_chunk, below): the host entry adds the copies and the events around it. */
-// in_bytes: bytes per input sample (4 for float32; aw_spatializer_process_host_pcm: 2 / 3 / 4).  AW_HOST_CHUNK_MB counts input bytes as
-// they cross PCIe, so a 16-bit batch moves twice the streams per chunk of a float32 one.
-static int64_t host_chunk_streams(const aw_spatializer *sp, int64_t frames, size_t in_bytes = sizeof(float)) {
-    const size_t chunk_bytes = (size_t)sp->ctx->cfg.host_chunk_mb << 20;        // input bytes per staged chunk (LaunchCfg: read once per context)
-    const size_t per_stream = (size_t)frames * sp->n_channels * in_bytes;
-    if (sp->n_streams < 4 || per_stream * sp->n_streams < 2 * chunk_bytes) return 0;           // small batches: one piece, serial (plug-in shaped calls)
-    int64_t cs = (int64_t)std::max<size_t>(1, chunk_bytes / per_stream);
-    cs = std::max<int64_t>(cs, 2);
-    return std::min<int64_t>(cs, (sp->n_streams + 1) / 2);
-}
-
 // Page-locked (hipHostMalloc / hipHostRegister) memory moves by DMA as it is; anything else is bounced.
 static bool host_ptr_is_pinned(const void *p) {
     hipPointerAttribute_t a{};
@@ -1456,7 +1339,7 @@ static aw_status sp_clip_counter(aw_spatializer *sp) {
 // (aw_spatializer_reserve_host / _reserve_pcm make them; a call on pageable memory that was not reserved for makes them on its first use)
 static aw_status host_stage_buffers(aw_spatializer *sp, int64_t frames, int64_t cs, bool bounce_in = false, bool bounce_out = false,
                                     int in_fmt = AW_SAMPLE_F32, int out_fmt = AW_SAMPLE_F32, bool host = true) {
-    const size_t streams = cs > 0 ? 2 * (size_t)cs : (size_t)sp->n_streams;           // two chunks in flight each way, or the whole batch
+    const size_t streams = awp::staged_streams(cs, sp->n_streams);
     const size_t in_n = streams * frames * sp->n_channels, out_n = streams * frames * 2;   // elements
     const size_t in_b = (size_t)awp::format_bytes(in_fmt), out_b = (size_t)awp::format_bytes(out_fmt);
     aw_status st = grow_buf(sp, &sp->d_stage_in, in_n);
@@ -1471,19 +1354,17 @@ static aw_status host_stage_buffers(aw_spatializer *sp, int64_t frames, int64_t 
 
 static bool pcm_format_ok(aw_sample_format f) { return awp::format_bytes(f) > 0; }
 
-// the chunking of a staged call: what the formats ask for, or — inside what a reserve sized — the chunking its buffers were sized for
-// (never a reallocation on this path)
+// the chunking of a staged call (host/scratch_plan.hpp): what the formats ask for (in_bytes per input sample, LaunchCfg::host_chunk_mb per
+// chunk), or — inside what a reserve sized — the chunking its buffers were sized for (never a reallocation on this path)
 static int64_t staged_chunk_streams(const aw_spatializer *sp, int64_t frames, size_t in_bytes) {
-    int64_t cs = host_chunk_streams(sp, frames, in_bytes);
-    if (frames <= sp->host_reserved_frames) cs = sp->host_chunk_reserved > 0 ? (cs > 0 ? std::min(cs, sp->host_chunk_reserved) : sp->host_chunk_reserved) : 0;
-    return cs;
+    return awp::staged_chunk_streams(sp->n_streams, sp->n_channels, frames, in_bytes, sp->ctx->cfg.host_chunk_mb, sp->host_reserved_frames, sp->host_chunk_reserved);
 }
 
 static aw_status reserve_staged(aw_spatializer *sp, int64_t max_frames, aw_sample_format in_fmt, aw_sample_format out_fmt) {
     aw_status st = aw_spatializer_reserve(sp, max_frames);
     if (st != AW_OK) return st;
     std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
-    const int64_t cs = host_chunk_streams(sp, max_frames, (size_t)awp::format_bytes(in_fmt));
+    const int64_t cs = awp::host_chunk_streams(sp->n_streams, sp->n_channels, max_frames, (size_t)awp::format_bytes(in_fmt), sp->ctx->cfg.host_chunk_mb);
     if (cs > 0) { st = host_pipeline_objects(sp->ctx); if (st != AW_OK) return st; }
     st = host_stage_buffers(sp, max_frames, cs, /*bounce_in=*/true, /*bounce_out=*/true, in_fmt, out_fmt);
     if (st == AW_OK) { sp->host_chunk_streams = cs; sp->host_chunk_reserved = cs; sp->host_reserved_frames = std::max(sp->host_reserved_frames, max_frames); }

@@ -25,8 +25,8 @@ def _body(src: str, name: str) -> str:
 def test_no_environment_lookups_on_process_paths():
     rt = open(os.path.join(ROOT, "airwave_amd", "csrc", "runtime.cpp")).read()
     for fn in ("sp_process_fused", "sp_process_partitioned", "sp_process_longwin", "sp_run_streams", "sp_begin_call", "aw_spatializer_process",
-               "aw_spatializer_process_host", "aw_spatializer_process_planar", "aw_realtime_process", "aw_engine_process", "part_plan",
-               "part_ensure_scratch", "host_chunk_streams", "host_stage_buffers", "aw_spatializer_reserve", "aw_spatializer_reserve_host",
+               "aw_spatializer_process_host", "aw_spatializer_process_planar", "aw_realtime_process", "aw_engine_process", "sp_scratch_budget",
+               "sp_ensure_scratch", "sp_held_scratch", "staged_chunk_streams", "reserve_staged", "host_stage_buffers", "aw_spatializer_reserve", "aw_spatializer_reserve_host",
                "batch_args", "batch_formats", "batch_begin", "batch_chunk", "batch_run_pinned", "host_process_pinned",
                "stage_zero", "ld_begin_call"):
         assert "getenv" not in _body(rt, fn), fn
@@ -35,6 +35,11 @@ def test_no_environment_lookups_on_process_paths():
     # the planner those entries call is pure: the knobs come to it as arguments
     assert "getenv" not in open(os.path.join(ROOT, "airwave_amd", "csrc", "host", "path_policy.hpp")).read()
     assert "getenv" not in open(os.path.join(ROOT, "airwave_amd", "csrc", "host", "stage_records.hpp")).read()      # (the stages' layouts likewise)
+    # ... and so is the sizing of the scratch and of the stream chunks (part_scratch, lw_plan_scratch, reserve_need, host_chunk_streams)
+    plan = open(os.path.join(ROOT, "airwave_amd", "csrc", "host", "scratch_plan.hpp")).read()
+    assert "getenv" not in plan and all(f"inline {t} {fn}(" in plan for t, fn in (("PartScratch", "part_scratch"), ("LwPlanScratch", "lw_plan_scratch"),
+                                                                                   ("ReserveNeed", "reserve_need"), ("int64_t", "host_chunk_streams")))
+    assert "PartPlan" not in rt and "LwScratch" not in rt
     for f in ("kernels.hip", "march_kernels.hip", "eq_kernels.hip"):
         src = open(os.path.join(ROOT, "airwave_amd", "csrc", "device", f)).read()
         for m in re.finditer(r"getenv", src):       # only inside prepare_kernels (context creation)
