@@ -15,6 +15,7 @@ from .api import (  # noqa: E402
     RealtimeAudioProcessor, Resampler, SAMPLE_FORMATS, Spatializer, WAVData, WAVError, WAVLoader, default_context, sample_format_bytes,
 )
 
+from .rateconv import RateConverter, convert, rateconv_filter, rateconv_plan  # noqa: E402
 from .batching import MixedRateBatch, RateBucket, bucket_by_rate, resample_tracks  # noqa: E402
 from .graph import AudioEffectGraph, AudioEffectPreparationResult, AudioEffectWarning  # noqa: E402
 from .eq import (  # noqa: E402
@@ -26,6 +27,7 @@ from .eq import (  # noqa: E402
 __all__ = [
     "AudioEffectGraph", "AudioEffectPreparationResult", "AudioEffectWarning",
     "MixedRateBatch", "RateBucket", "bucket_by_rate", "resample_tracks",
+    "RateConverter", "convert", "rateconv_filter", "rateconv_plan",
     "BiquadCoefficientBuilder", "BiquadCoefficientError", "EqualizerAPOParser", "EqualizerAudioEffectError",
     "EqualizerDefinition", "EqualizerFilter", "EqualizerParseError", "EqualizerRuntimeEffect",
     "ParametricEqualizerPreparationError", "ParametricEqualizerProcessor", "ParametricEqualizerState", "EqualizerNotFoldable", "FoldedHRIR", "fold_equalizer",

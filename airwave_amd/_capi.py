@@ -145,6 +145,15 @@ SIGNATURES = {
     "aw_eq_debug_hold_publication_lock": (_I32, [_V, _I32]),
     "aw_eq_transition_length": (_I32, [_V]),
     "aw_eq_is_transitioning": (_I32, [_V]),
+    "aw_rateconv_plan": (_I32, [_D, _D, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
+    "aw_rateconv_filter": (_I32, [_D, _D, c_float_p, _I64]),
+    "aw_rateconv_create": (_I32, [_V, _D, _D, _I32, _I32, c_void_pp]),
+    "aw_rateconv_destroy": (None, [_V]),
+    "aw_rateconv_info": (_I64, [_V, _I32]),
+    "aw_rateconv_output_frames": (_I64, [_V, _I64]),
+    "aw_rateconv_process": (_I32, [_V, _V, _I64, _V, _I64, ctypes.POINTER(ctypes.c_int64)]),
+    "aw_rateconv_flush": (_I32, [_V, _V, _I64, ctypes.POINTER(ctypes.c_int64)]),
+    "aw_rateconv_reset": (_I32, [_V]),
 }
 
 

@@ -5,6 +5,7 @@ device of that rate — the HRIR (not the audio) is resampled to the stream rate
 side.  Host-side orchestration over the kernels of the convolution path; nothing here touches samples."""
 from __future__ import annotations
 
+import sys
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
@@ -22,6 +23,9 @@ class RateBucket:
     equalizer: Optional[object] = None      # ParametricEqualizerState that runs AFTER the spatializer (None: no equalizer, folded into the HRIR, or the spatializer's own stage)
     eq_response_taps: int = 0        # equalizer folded into the HRIR: samples of its impulse response that were kept (0: not folded)
     eq_tail_bound: float = 0.0       # ... and the bound on what the cut can change, relative to the spatializer output's peak
+    converter: Optional[object] = None      # RateConverter (two channels) behind the spatializer and its trailing equalizer: the bucket leaves at output_rate
+    stage: int = 0                   # device staging of the bucket's stereo output at its own rate, in front of the converter (grow-only)
+    stage_bytes: int = 0
 
 
 # An equalizer is folded into the HRIR (fold=None, the default) when that is the cheaper form: the folded HRIR is longer by the
@@ -56,20 +60,25 @@ class MixedRateBatch:
     def __init__(self, tracks, hrir_rate: float, layout: InputLayout, stream_rates: Sequence[float],
                  hrirMap: Optional[HRIRChannelMap] = None, ctx: Optional[Context] = None, literal_vgenp: bool = False,
                  equalizer=None, fold_equalizer: Optional[bool] = None, eq_tail_tolerance: float = 1e-7, eq_max_taps: int = 65536,
-                 stream_equalizers=None):
+                 stream_equalizers=None, output_rate: Optional[float] = None):
         """equalizer: an EqualizerDefinition applied after the spatializer, as AudioEffectGraph orders the two effects
         (AudioEffectGraph.swift:195-211).  fold_equalizer: True = folded into the HRIR (aw_eq_fold_hrir; raises EqualizerNotFoldable
         if its response is too long), False = the cascade kernel after the spatializer, None = whichever is cheaper (see _fold_pays),
         the cascade if it cannot be folded.
         stream_equalizers: instead of `equalizer`, one EqualizerDefinition or None per stream, in the caller's order (one headphone
         preset per output device, DeviceProfileManager): every bucket's spatializer runs them as its equalizer stage
-        (Spatializer.set_equalizer), the bucket's distinct definitions being the presets.  Never folded: the HRIR is shared."""
+        (Spatializer.set_equalizer), the bucket's distinct definitions being the presets.  Never folded: the HRIR is shared.
+        output_rate: every stream leaves at this rate: a bucket at another rate gets a two-channel RateConverter (aw_rateconv, a
+        Kaiser-windowed sinc on the audio — not the HRIR's linear interpolation) behind its spatializer and its trailing equalizer.  None:
+        every stream leaves at the rate it came in with."""
+        from .rateconv import RateConverter
         from .eq import EqualizerNotFoldable, ParametricEqualizerState, fold_equalizer as fold
         if equalizer is not None and stream_equalizers is not None:
             raise ValueError("equalizer= and stream_equalizers= are mutually exclusive")
         if stream_equalizers is not None and len(stream_equalizers) != len(stream_rates):
             raise ValueError(f"stream_equalizers needs one entry per stream ({len(stream_rates)}), got {len(stream_equalizers)}")
         self.ctx = ctx or default_context()
+        self.output_rate = None if output_rate is None else float(output_rate)
         tracks = np.ascontiguousarray(tracks, dtype=np.float32)
         # the reference's chooser: 7-track files take the 7-channel map, everything else the 14-channel one
         # (HRIRManager.swift:355-360; aw_preset_activate does the same) — an 8..13-track HRIR then fails the bounds check
@@ -99,25 +108,69 @@ class MixedRateBatch:
                         presets.append(d)
                     which.append(-1 if d is None else presets.index(d))
                 sp.set_equalizer(presets, which if presets else None)
-            self.buckets[rate] = RateBucket(rate, ids, int(tr.shape[1]), sp, eq_state, folded.responseTaps if folded else 0, folded.tailBound if folded else 0.0)
+            conv = None
+            if self.output_rate is not None and rate != self.output_rate:
+                conv = RateConverter(rate, self.output_rate, len(ids), 2, ctx=self.ctx)
+            self.buckets[rate] = RateBucket(rate, ids, int(tr.shape[1]), sp, eq_state, folded.responseTaps if folded else 0, folded.tailBound if folded else 0.0,
+                                            conv)
 
-    def process_device(self, in_ptrs: Dict[float, int], out_ptrs: Dict[float, int], frames: Dict[float, int]) -> None:
-        """Per-rate device buffers ([bucket streams][frames][C] -> [..][frames][2]); all launches are queued on
-        the context stream, buckets back to back."""
+    def __del__(self):
+        if sys.is_finalizing() or not getattr(getattr(self, "ctx", None), "_h", None):
+            return
+        for b in getattr(self, "buckets", {}).values():
+            if b.stage:
+                self.ctx.synchronize()
+                self.ctx.free(b.stage)
+                b.stage, b.stage_bytes = 0, 0
+
+    def reserve_output_staging(self, frames: Dict[float, int]) -> None:
+        """output_rate: sizes the staging in front of every converter for calls of up to frames[rate] frames, so that process_device
+        allocates nothing afterwards."""
         for rate, b in self.buckets.items():
-            b.spatializer.process_device(in_ptrs[rate], out_ptrs[rate], frames[rate])
+            need = len(b.stream_ids) * int(frames.get(rate, 0)) * 2 * 4
+            if b.converter is not None and need > b.stage_bytes:
+                if b.stage:
+                    self.ctx.synchronize()
+                    self.ctx.free(b.stage)
+                b.stage, b.stage_bytes = self.ctx.alloc(need), need
+
+    def process_device(self, in_ptrs: Dict[float, int], out_ptrs: Dict[float, int], frames: Dict[float, int],
+                       out_capacities: Optional[Dict[float, int]] = None) -> Optional[Dict[float, int]]:
+        """Per-rate device buffers ([bucket streams][frames][C] -> [..][frames][2]); all launches are queued on
+        the context stream, buckets back to back.
+        output_rate: a converted bucket writes [bucket streams][n][2] at output_rate, dense in the n frames this call produced (what
+        converter.output_frames(frames) said; the rest follows with later calls or flush_device), and needs out_capacities[rate] >= n;
+        the other buckets write `frames` frames as before.  Returns the counts per rate (None without output_rate)."""
+        if self.output_rate is not None:
+            self.reserve_output_staging(frames)
+        counts: Dict[float, int] = {}
+        for rate, b in self.buckets.items():
+            y = b.stage if b.converter is not None else out_ptrs[rate]
+            b.spatializer.process_device(in_ptrs[rate], y, frames[rate])
             if b.equalizer is not None:
-                b.equalizer.process_device(out_ptrs[rate], out_ptrs[rate], frames[rate])      # in place, same stream
+                b.equalizer.process_device(y, y, frames[rate])      # in place, same stream
+            counts[rate] = frames[rate]
+            if b.converter is not None:
+                counts[rate] = b.converter.process_device(y, frames[rate], out_ptrs[rate], (out_capacities or {}).get(rate, 0))
+        return counts if self.output_rate is not None else None
+
+    def flush_device(self, out_ptrs: Dict[float, int], out_capacities: Dict[float, int]) -> Dict[float, int]:
+        """output_rate: the frames every converter still owes for its input so far, [bucket streams][n][2] per converted rate; the
+        converters start over.  Returns the counts per converted rate."""
+        return {rate: b.converter.flush_device(out_ptrs[rate], out_capacities[rate]) for rate, b in self.buckets.items() if b.converter is not None}
 
     def process(self, streams: Sequence[np.ndarray], stream_rates: Sequence[float]) -> List[np.ndarray]:
         """Host convenience for tests: streams[i] is [frames_i][C] at stream_rates[i]; streams of one bucket must
-        have equal length.  Returns the stereo outputs in the caller's order."""
+        have equal length.  Returns the stereo outputs in the caller's order — with output_rate, every stream at that rate and
+        flushed: ceil(frames_i L / M) frames for a stream of a converted bucket."""
         out: List[Optional[np.ndarray]] = [None] * len(streams)
         for rate, b in self.buckets.items():
             x = np.stack([np.asarray(streams[i], dtype=np.float32) for i in b.stream_ids])
             y = b.spatializer.process(x)
             if b.equalizer is not None:
                 y = b.equalizer.process_batch(y)
+            if b.converter is not None:
+                y = np.concatenate([b.converter.process(y), b.converter.flush()], axis=1)
             for k, i in enumerate(b.stream_ids):
                 out[i] = y[k]
         return out  # type: ignore[return-value]
@@ -127,3 +180,5 @@ class MixedRateBatch:
             b.spatializer.reset()
             if b.equalizer is not None:
                 b.equalizer.reset()
+            if b.converter is not None:
+                b.converter.reset()

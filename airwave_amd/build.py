@@ -41,8 +41,10 @@ SOURCES = [
     "device/loudness_kernels.hip",
     "device/truepeak_kernels.hip",
     "device/limiter_kernels.hip",
+    "device/rateconv_kernels.hip",
     "runtime.cpp",
     "eq_runtime.cpp",
+    "rateconv_runtime.cpp",
     "host/eq.cpp",
     "host/tables.cpp",
     "host/host_api.cpp",

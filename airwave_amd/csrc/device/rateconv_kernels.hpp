@@ -1,0 +1,14 @@
+// rateconv_kernels.hpp — host-callable launcher of the sample-rate converter's kernel (rateconv_kernels.hip; device code in
+// rateconv_tile.hpp, rules in rateconv.hpp).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "rateconv_tile.hpp"
+
+namespace awk {
+
+// One call of p.in_frames input frames of p.n_streams streams: one workgroup per tile of p.tile output frames and stream (one per stream
+// when the call produces nothing).  Writes p.out, p.hist_out and p.counts; reads p.in, p.hist_in and p.c.
+hipError_t launch_rateconv(const RateconvParams &p, hipStream_t stream);
+
+}  // namespace awk

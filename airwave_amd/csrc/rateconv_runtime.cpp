@@ -1,0 +1,184 @@
+// rateconv_runtime.cpp — C ABI of the batch sample-rate converter (aw_rateconv_*, include/airwave_hip.h): the rules are
+// device/rateconv.hpp, the kernel device/rateconv_tile.hpp.  Audio-rate conversion has no counterpart in the reference, whose two-point
+// linear interpolation (Resampler.swift:31-68, aw_resample) is for an HRIR at activation and images and aliases at about -30 dB on audio.
+// One owner thread per handle, like every other handle of this library; the handle goes as aw_eq does: device current, stream idle, then
+// its members.
+#include <memory>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "device/rateconv_kernels.hpp"
+#include "runtime.hpp"
+
+using awr::fail;
+
+namespace {
+
+aw_status plan_checked(double in_rate, double out_rate, awrc::Plan &p) {
+    switch (awrc::plan(in_rate, out_rate, p)) {
+        case awrc::kPlanNotIntegral: return fail(AW_ERR_INVALID_ARGUMENT, "sample rates must be positive integers in Hz");
+        case awrc::kPlanEqual: return fail(AW_ERR_INVALID_ARGUMENT, "the rates are equal: there is nothing to convert");
+        case awrc::kPlanTooLarge:
+            return fail(AW_ERR_INVALID_ARGUMENT, "the reduced ratio out / in has a term above " + std::to_string(awrc::kMaxTerm) + ": not approximated");
+        default: return AW_OK;
+    }
+}
+
+}  // namespace
+
+struct aw_rateconv {
+    aw_context *ctx = nullptr;
+    int n_streams = 0, n_channels = 0, tile = 0;
+    awrc::Plan plan;
+    awrc::Counts counts;                       // the same for every stream
+    awr::Buf<float> d_c;                       // [L][row_stride]
+    awr::Buf<float> d_hist[2];                 // [streams][taps - 1][channels]: a call reads slot cur and writes the other
+    awr::Buf<long long> d_counts;              // [streams][2], written by each call's last tiles
+    int cur = 0;
+};
+
+namespace {
+
+aw_status reset_state(aw_rateconv *rc) {
+    AW_HIP_TRY(hipMemsetAsync(rc->d_hist[rc->cur].get(), 0, rc->d_hist[rc->cur].bytes(), rc->ctx->stream));
+    AW_HIP_TRY(hipMemsetAsync(rc->d_counts.get(), 0, rc->d_counts.bytes(), rc->ctx->stream));
+    rc->counts = awrc::Counts{};
+    return AW_OK;
+}
+
+// in NULL: in_frames frames of zeros
+aw_status run(aw_rateconv *rc, const float *in, long long in_frames, float *out, long long capacity, int64_t *out_frames) {
+    const awrc::Plan &pl = rc->plan;
+    const long long n_out = awrc::outputs_after(rc->counts.consumed + in_frames, pl.L, pl.M, pl.latency) - rc->counts.produced;
+    if (capacity < n_out)
+        return fail(AW_ERR_INVALID_ARGUMENT, "out_capacity_frames " + std::to_string(capacity) + " is below the " + std::to_string(n_out) +
+                                                 " frames this call produces (aw_rateconv_output_frames)");
+    if (n_out > 0 && !out) return fail(AW_ERR_INVALID_ARGUMENT, "out_device is NULL");
+    if (out_frames) *out_frames = n_out;
+    if (in_frames == 0) return AW_OK;
+    AW_HIP_TRY(hipSetDevice(rc->ctx->device));
+    awk::RateconvParams p{};
+    p.in = in; p.in_frames = in_frames; p.out = out; p.out_frames = n_out;
+    p.n_streams = rc->n_streams; p.channels = rc->n_channels;
+    p.L = pl.L; p.M = pl.M; p.taps = pl.taps; p.latency = pl.latency;
+    p.tile = rc->tile; p.row_stride = awk::rc_row_stride(pl.taps); p.c = rc->d_c.get();
+    p.hist_in = rc->d_hist[rc->cur].get(); p.hist_out = rc->d_hist[rc->cur ^ 1].get();
+    p.consumed = rc->counts.consumed; p.produced = rc->counts.produced; p.counts = rc->d_counts.get();
+    AW_HIP_TRY(awk::launch_rateconv(p, rc->ctx->stream));
+    rc->cur ^= 1;
+    rc->counts.consumed += in_frames;
+    rc->counts.produced += n_out;
+    return AW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+aw_status aw_rateconv_plan(double in_rate, double out_rate, int32_t *L, int32_t *M, int32_t *taps, int32_t *latency) try {
+    awrc::Plan p;
+    const aw_status st = plan_checked(in_rate, out_rate, p);
+    if (st != AW_OK) return st;
+    if (L) *L = p.L;
+    if (M) *M = p.M;
+    if (taps) *taps = p.taps;
+    if (latency) *latency = p.latency;
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_rateconv_filter(double in_rate, double out_rate, float *c, int64_t capacity_floats) try {
+    if (!c) return fail(AW_ERR_INVALID_ARGUMENT, "c is NULL");
+    awrc::Plan p;
+    const aw_status st = plan_checked(in_rate, out_rate, p);
+    if (st != AW_OK) return st;
+    if (capacity_floats < (int64_t)p.L * p.taps)
+        return fail(AW_ERR_INVALID_ARGUMENT, "capacity_floats is below L * taps = " + std::to_string((long long)p.L * p.taps));
+    awrc::filter(p, c);
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_rateconv_create(aw_context *ctx, double in_rate, double out_rate, int32_t n_streams, int32_t n_channels, aw_rateconv **out) try {
+    if (!out) return fail(AW_ERR_INVALID_ARGUMENT, "out is NULL");
+    *out = nullptr;
+    if (!ctx) return fail(AW_ERR_NO_DEVICE, "no context (no HIP device): there is no CPU fallback");
+    if (n_streams <= 0) return fail(AW_ERR_INVALID_ARGUMENT, "n_streams must be > 0");
+    if (n_channels < 1 || n_channels > awrc::kMaxChannels) return fail(AW_ERR_INVALID_ARGUMENT, "n_channels must be in 1..16");
+    awrc::Plan pl;
+    const aw_status planned = plan_checked(in_rate, out_rate, pl);
+    if (planned != AW_OK) return planned;
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(AW_ERR_NO_DEVICE, "hipSetDevice failed");
+    awr::Owner<aw_rateconv> rc(new (std::nothrow) aw_rateconv(), aw_rateconv_destroy);
+    if (!rc) return fail(AW_ERR_OUT_OF_MEMORY, "allocation failed");
+    rc->ctx = ctx; rc->n_streams = n_streams; rc->n_channels = n_channels; rc->plan = pl;
+    rc->tile = awk::rc_tile(pl.L, pl.M, pl.taps, n_channels);
+    if (rc->tile < 1) return fail(AW_ERR_INVALID_ARGUMENT, "no tile of this converter fits the kernel's LDS");
+    // the table, rows padded to 16-byte words (the pad is never read as a tap)
+    const int stride = awk::rc_row_stride(pl.taps);
+    std::vector<float> dense((size_t)pl.L * pl.taps), rows((size_t)pl.L * stride, 0.0f);
+    awrc::filter(pl, dense.data());
+    for (int ph = 0; ph < pl.L; ++ph)
+        for (int k = 0; k < pl.taps; ++k) rows[(size_t)ph * stride + k] = dense[(size_t)ph * pl.taps + k];
+    awr::Counter *const allocs = &ctx->device_allocs;
+    AW_HIP_TRY(rc->d_c.upload(rows.data(), rows.size(), allocs, &ctx->sync_copies));
+    const size_t hist = (size_t)n_streams * (pl.taps - 1) * n_channels;
+    AW_HIP_TRY(rc->d_hist[0].alloc(hist, allocs));
+    AW_HIP_TRY(rc->d_hist[1].alloc(hist, allocs));
+    AW_HIP_TRY(rc->d_counts.alloc((size_t)n_streams * 2, allocs));
+    const aw_status zeroed = reset_state(rc.get());
+    if (zeroed != AW_OK) return zeroed;
+    *out = rc.release();
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+void aw_rateconv_destroy(aw_rateconv *rc) {
+    if (!rc) return;
+    (void)hipSetDevice(rc->ctx->device);
+    (void)hipStreamSynchronize(rc->ctx->stream);
+    delete rc;
+}
+
+int64_t aw_rateconv_info(const aw_rateconv *rc, int32_t what) {
+    if (!rc) return -1;
+    switch (what) {
+        case 0: return rc->plan.L;
+        case 1: return rc->plan.M;
+        case 2: return rc->plan.taps;
+        case 3: return rc->plan.latency;
+        case 4: return rc->tile;
+        case 5: return rc->counts.consumed;
+        case 6: return rc->counts.produced;
+        default: return -1;
+    }
+}
+
+int64_t aw_rateconv_output_frames(const aw_rateconv *rc, int64_t in_frames) {
+    if (!rc || in_frames < 0) return -1;
+    return awrc::outputs_after(rc->counts.consumed + in_frames, rc->plan.L, rc->plan.M, rc->plan.latency) - rc->counts.produced;
+}
+
+aw_status aw_rateconv_process(aw_rateconv *rc, const float *in_device, int64_t in_frames, float *out_device, int64_t out_capacity_frames,
+                              int64_t *out_frames) try {
+    if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
+    if (in_frames < 0) return fail(AW_ERR_INVALID_ARGUMENT, "in_frames must be >= 0");
+    if (in_frames > 0 && !in_device) return fail(AW_ERR_INVALID_ARGUMENT, "in_device is NULL");
+    if ((reinterpret_cast<uintptr_t>(in_device) | reinterpret_cast<uintptr_t>(out_device)) & 3u)
+        return fail(AW_ERR_INVALID_ARGUMENT, "buffers must be 4-byte aligned");
+    return run(rc, in_device, in_frames, out_device, out_capacity_frames, out_frames);
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_rateconv_flush(aw_rateconv *rc, float *out_device, int64_t out_capacity_frames, int64_t *out_frames) try {
+    if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
+    if (reinterpret_cast<uintptr_t>(out_device) & 3u) return fail(AW_ERR_INVALID_ARGUMENT, "buffers must be 4-byte aligned");
+    const aw_status st = run(rc, nullptr, rc->plan.latency, out_device, out_capacity_frames, out_frames);
+    if (st != AW_OK) return st;
+    return reset_state(rc);
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_rateconv_reset(aw_rateconv *rc) try {
+    if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
+    AW_HIP_TRY(hipSetDevice(rc->ctx->device));
+    return reset_state(rc);
+} AW_NOEXCEPT_TAIL
+
+}  // extern "C"

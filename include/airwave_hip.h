@@ -655,6 +655,41 @@ AW_API aw_status aw_eq_debug_hold_publication_lock(aw_eq *eq, int32_t hold);
 AW_API int32_t aw_eq_transition_length(const aw_eq *eq);
 AW_API int32_t aw_eq_is_transitioning(const aw_eq *eq);
 
+/* ---- batch sample-rate converter ---------------------------------------------------------------
+ * Audio-rate conversion has no counterpart in the reference.  What the reference resamples is an HRIR at activation, by two-point linear
+ * interpolation (Resampler.swift:31-68; aw_resample above), which is right for an impulse response and images and aliases at about
+ * -30 dB on audio: audio does not take that path.  aw_rateconv is a polyphase Kaiser-windowed sinc (48 zero crossings a side, beta 10,
+ * stopband from the lower Nyquist on; rules and constants: airwave_amd/csrc/device/rateconv.hpp), a stand-alone handle beside aw_eq: it
+ * changes the frame count, which the in-place stages of the batch entries cannot, and it takes any channel count 1..16, so it can sit in
+ * front of a spatializer or behind one.
+ *  - rates are positive integers in Hz (passed as doubles that must be integral).  With g = gcd(in, out), L = out / g and M = in / g,
+ *    equal rates and an L or M above 640 are refused; 640 covers every pair among 44100, 48000, 88200, 96000, 176400 and 192000.  Every
+ *    refusal is AW_ERR_INVALID_ARGUMENT with a message; no ratio is approximated.
+ *  - output n of a stream sits exactly at input time n M / L (time aligned) and is written once input frame floor(n M / L) + latency has
+ *    arrived: after N input frames in total a stream has produced max(0, ceil((N - latency) L / M)) frames.
+ *  - every output is a pure function of the stream's input since the last reset: splitting calls in time, sharding streams over handles
+ *    and buffer alignment change no bit.  Inputs are not sanitised: a NaN reaches the outputs whose windows hold it.
+ * aw_rateconv_plan / _filter are pure host and need no context: what a pair of rates means, and the float32 table c[L][taps].
+ * aw_rateconv_create makes every device allocation (the table, two history slots [streams][taps - 1][channels], the counts); no later
+ * call allocates.  aw_rateconv_process reads [streams][in_frames][channels] float32 and writes [streams][*out_frames][channels], dense in
+ * the count it produced, which is what aw_rateconv_output_frames(rc, in_frames) said; it is asynchronous on the context's stream.  A
+ * call may produce 0 frames (fewer than latency + 1 input frames so far): it then only moves the history.  out_capacity_frames below
+ * the count returns AW_ERR_INVALID_ARGUMENT and leaves the handle untouched.  in and out must not overlap, and need 4-byte alignment
+ * only.  aw_rateconv_flush is exactly a process call of `latency` zero frames followed by aw_rateconv_reset: after it a stream fed N
+ * frames has produced ceil(N L / M) in total.  One owner thread per handle, as for aw_eq; destroy waits for the stream. */
+typedef struct aw_rateconv aw_rateconv;
+AW_API aw_status aw_rateconv_plan(double in_rate, double out_rate, int32_t *L, int32_t *M, int32_t *taps, int32_t *latency /* D, input frames */);
+AW_API aw_status aw_rateconv_filter(double in_rate, double out_rate, float *c /* [L][taps] */, int64_t capacity_floats);
+AW_API aw_status aw_rateconv_create(aw_context *ctx, double in_rate, double out_rate, int32_t n_streams, int32_t n_channels, aw_rateconv **out);
+AW_API void aw_rateconv_destroy(aw_rateconv *rc);
+/* what: 0 L, 1 M, 2 taps, 3 latency, 4 tile (output frames per workgroup), 5 frames consumed, 6 frames produced; -1 otherwise */
+AW_API int64_t aw_rateconv_info(const aw_rateconv *rc, int32_t what);
+AW_API int64_t aw_rateconv_output_frames(const aw_rateconv *rc, int64_t in_frames);  /* what the next process call of in_frames writes */
+AW_API aw_status aw_rateconv_process(aw_rateconv *rc, const float *in_device, int64_t in_frames, float *out_device,
+                                     int64_t out_capacity_frames, int64_t *out_frames);
+AW_API aw_status aw_rateconv_flush(aw_rateconv *rc, float *out_device, int64_t out_capacity_frames, int64_t *out_frames);
+AW_API aw_status aw_rateconv_reset(aw_rateconv *rc);
+
 AW_API const char *aw_version(void);
 
 #ifdef __cplusplus

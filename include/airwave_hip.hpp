@@ -247,4 +247,42 @@ class ParametricEqualizerProcessor {
     aw_eq *h_ = nullptr;
 };
 
+// aw_rateconv: the batch sample-rate converter (no counterpart in the reference, whose Resampler.swift:31-68 interpolates an HRIR, not audio)
+struct RateConversionPlan { int32_t L = 0, M = 0, taps = 0, latency = 0; };
+inline RateConversionPlan rateConversionPlan(double inRate, double outRate) {
+    RateConversionPlan p;
+    check(aw_rateconv_plan(inRate, outRate, &p.L, &p.M, &p.taps, &p.latency));
+    return p;
+}
+inline std::vector<float> rateConversionFilter(double inRate, double outRate) {          // c[L][taps]
+    const RateConversionPlan p = rateConversionPlan(inRate, outRate);
+    std::vector<float> c((size_t)p.L * (size_t)p.taps);
+    check(aw_rateconv_filter(inRate, outRate, c.data(), (int64_t)c.size()));
+    return c;
+}
+class RateConverter {
+  public:
+    RateConverter(Context &ctx, double inRate, double outRate, int nStreams, int nChannels) {
+        check(aw_rateconv_create(ctx.get(), inRate, outRate, nStreams, nChannels, &h_));
+    }
+    ~RateConverter() { aw_rateconv_destroy(h_); }
+    RateConverter(const RateConverter &) = delete;
+    int64_t info(int32_t what) const { return aw_rateconv_info(h_, what); }
+    int64_t outputFrames(int64_t inFrames) const { return aw_rateconv_output_frames(h_, inFrames); }
+    // device buffers; returns the frames written
+    int64_t process(const float *inDevice, int64_t inFrames, float *outDevice, int64_t outCapacityFrames) {
+        int64_t n = 0;
+        check(aw_rateconv_process(h_, inDevice, inFrames, outDevice, outCapacityFrames, &n));
+        return n;
+    }
+    int64_t flush(float *outDevice, int64_t outCapacityFrames) {
+        int64_t n = 0;
+        check(aw_rateconv_flush(h_, outDevice, outCapacityFrames, &n));
+        return n;
+    }
+    void reset() { check(aw_rateconv_reset(h_)); }
+  private:
+    aw_rateconv *h_ = nullptr;
+};
+
 }  // namespace aw
