@@ -154,6 +154,13 @@ SIGNATURES = {
     "aw_rateconv_process": (_I32, [_V, _V, _I64, _V, _I64, ctypes.POINTER(ctypes.c_int64)]),
     "aw_rateconv_flush": (_I32, [_V, _V, _I64, ctypes.POINTER(ctypes.c_int64)]),
     "aw_rateconv_reset": (_I32, [_V]),
+    "aw_pcm_rateconv_process": (_I32, [_V, _V, _I32, _I64, _V, _I32, _I64, ctypes.POINTER(ctypes.c_int64), _V]),
+    "aw_pcm_rateconv_flush": (_I32, [_V, _V, _I32, _I64, ctypes.POINTER(ctypes.c_int64), _V]),
+    "aw_pcm_rateconv_set_dither": (_I32, [_V, _I32, _U64, _U64]),
+    "aw_pcm_rateconv_set_gain": (_I32, [_V, _I32, c_float_p, _I32]),
+    "aw_pcm_rateconv_set_metering": (_I32, [_V, _I32]),
+    "aw_pcm_rateconv_get_levels": (_I32, [_V, _I32, _I32, _V]),
+    "aw_pcm_rateconv_reset_levels": (_I32, [_V]),
 }
 
 

@@ -21,6 +21,18 @@
 // fmaf is correctly rounded on host and device, so y[n] is a pure function of the stream's input since the reset: splitting calls in
 // time, sharding streams over handles and the kernel's tiling change no bit.  A stream carries its last T - 1 input frames and the two
 // 64-bit counts of frames consumed and produced.
+//
+// Integer PCM in and out (aw_pcm_rateconv_*): the same rule between a decode and an encode, both pcm.hpp's.  For stream s of the handle
+// (global stream first_stream + s) and channel ch: x = awp::decode_at of the input element (F32 as it is; the history stays decoded
+// float32, so formats may change from call to call); y as above; u = (float)(y * g_s) under a fixed gain, else y; F32 output is u, s32
+// output awp::encode_s32(u), s16 / s24 output awp::encode_dithered_at's rule with d = awp::dither_value(mode, K_j, n, e), where n is the
+// stream's absolute output index since the last reset or flush (the same n as above), j = ch >> 1, e = ch & 1 and
+//   K_j = awp::dither_key(seed, first_stream + s) + j * 0xA0761D6478BD642F   (mod 2^64).
+// K_0 is the spatializer's key, so a stereo converter's noise at frame n is the spatializer's at position n; further channel pairs get
+// keys of their own, for the spatializer's 2 p + ear counter would collide from the third channel on.  Per stream, while metering is on:
+// peak = max |y| over finite samples of all channels (before the gain), nonfinite = NaN / +-inf y, frames = output frames written,
+// clipped = samples the integer encode clipped (after gain and dither): maxima and integer sums, so every field is exact and, like every
+// output byte, independent of call splitting, sharding, byte alignment and tiling.
 #pragma once
 #include <cmath>
 #include <cstdint>

@@ -1,4 +1,4 @@
-// rateconv_kernels.hip — gfx950 kernel of the sample-rate converter (device code in rateconv_tile.hpp).
+// rateconv_kernels.hip — gfx950 kernels of the sample-rate converter (device code in rateconv_tile.hpp): the float32 form and the PCM form.
 #include "rateconv_kernels.hpp"
 #include "stage_gpu_ctx.hpp"
 
@@ -11,7 +11,16 @@ __global__ void __launch_bounds__(kRcThreads) aw_rateconv_kernel(RateconvParams 
     rateconv_tile<StageGpuCtx<float>>(ctx, p, (long long)blockIdx.y, (long long)blockIdx.x);
 }
 
-hipError_t launch_rateconv(const RateconvParams &p, hipStream_t stream) {
+__global__ void __launch_bounds__(kRcThreads) aw_rateconv_pcm_kernel(RateconvParams p) {
+    __shared__ __align__(16) float rc_lds[kRcLdsFloats];
+    StageGpuCtx<float> ctx{rc_lds};
+    rateconv_tile_pcm<StageGpuCtx<float>>(ctx, p, (long long)blockIdx.y, (long long)blockIdx.x);
+}
+
+namespace {
+
+// pcm: p.in and p.out are byte buffers of p.in_format / p.out_format at any alignment
+hipError_t launch_form(const RateconvParams &p, bool pcm, hipStream_t stream) {
     if (p.n_streams <= 0 || p.in_frames <= 0) return hipSuccess;
     if (p.channels < 1 || p.channels > awrc::kMaxChannels || p.L < 1 || p.M < 1 || p.L > awrc::kMaxTerm || p.M > awrc::kMaxTerm ||
         p.taps < 4 || p.taps != 2 * p.latency || p.row_stride != rc_row_stride(p.taps) || p.out_frames < 0 || p.consumed < 0 || p.produced < 0 ||
@@ -19,24 +28,41 @@ hipError_t launch_rateconv(const RateconvParams &p, hipStream_t stream) {
         return hipErrorInvalidValue;
     if (p.out_frames != awrc::outputs_after(p.consumed + p.in_frames, p.L, p.M, p.latency) - p.produced) return hipErrorInvalidValue;
     if (!p.c || !p.hist_in || !p.hist_out || p.hist_in == p.hist_out || !p.counts || (p.out_frames > 0 && !p.out) ||
-        (reinterpret_cast<uintptr_t>(p.in) & 3u) || (reinterpret_cast<uintptr_t>(p.out) & 3u) || (reinterpret_cast<uintptr_t>(p.c) & 15u))
+        (reinterpret_cast<uintptr_t>(p.c) & 15u))
         return hipErrorInvalidValue;
+    if (pcm) {
+        if (!awp::format_bytes(p.in_format) || !awp::format_bytes(p.out_format) || p.dither < awp::kDitherNone || p.dither > awp::kDitherTpdfHp)
+            return hipErrorInvalidValue;
+    } else if ((reinterpret_cast<uintptr_t>(p.in) & 3u) || (reinterpret_cast<uintptr_t>(p.out) & 3u)) {
+        return hipErrorInvalidValue;
+    }
     const long long tiles = (p.out_frames + p.tile - 1) / p.tile;
     if (tiles > 0x7FFFFFFFll) return hipErrorInvalidValue;
     const size_t hist = (size_t)(p.taps - 1) * p.channels;
+    const long long bi = pcm ? awp::format_bytes(p.in_format) : 4, bo = pcm ? awp::format_bytes(p.out_format) : 4;
     // the y dimension of a grid holds 65,535 workgroups: more streams go in slices
     for (int s0 = 0; s0 < p.n_streams; s0 += 65535) {
         RateconvParams q = p;
         q.n_streams = p.n_streams - s0 < 65535 ? p.n_streams - s0 : 65535;
-        if (p.in) q.in = p.in + (long long)s0 * p.in_frames * p.channels;
-        if (p.out) q.out = p.out + (long long)s0 * p.out_frames * p.channels;
+        if (p.in) q.in = reinterpret_cast<const float *>(reinterpret_cast<const unsigned char *>(p.in) + (long long)s0 * p.in_frames * p.channels * bi);
+        if (p.out) q.out = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(p.out) + (long long)s0 * p.out_frames * p.channels * bo);
         q.hist_in = p.hist_in + s0 * hist; q.hist_out = p.hist_out + s0 * hist;
         q.counts = p.counts + 2 * (size_t)s0;
-        hipLaunchKernelGGL(aw_rateconv_kernel, dim3((unsigned)(tiles > 0 ? tiles : 1), (unsigned)q.n_streams), dim3(kRcThreads), 0, stream, q);
+        q.first_stream = p.first_stream + (unsigned long long)s0;
+        if (p.gains) q.gains = p.gains + s0;
+        if (p.levels) q.levels = p.levels + s0;
+        const dim3 grid((unsigned)(tiles > 0 ? tiles : 1), (unsigned)q.n_streams);
+        if (pcm) hipLaunchKernelGGL(aw_rateconv_pcm_kernel, grid, dim3(kRcThreads), 0, stream, q);
+        else hipLaunchKernelGGL(aw_rateconv_kernel, grid, dim3(kRcThreads), 0, stream, q);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
+
+}  // namespace
+
+hipError_t launch_rateconv(const RateconvParams &p, hipStream_t stream) { return launch_form(p, false, stream); }
+hipError_t launch_rateconv_pcm(const RateconvParams &p, hipStream_t stream) { return launch_form(p, true, stream); }
 
 }  // namespace awk

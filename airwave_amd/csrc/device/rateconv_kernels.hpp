@@ -10,5 +10,8 @@ namespace awk {
 // One call of p.in_frames input frames of p.n_streams streams: one workgroup per tile of p.tile output frames and stream (one per stream
 // when the call produces nothing).  Writes p.out, p.hist_out and p.counts; reads p.in, p.hist_in and p.c.
 hipError_t launch_rateconv(const RateconvParams &p, hipStream_t stream);
+// The PCM form of the same call: p.in and p.out are byte buffers of p.in_format and p.out_format (awp::Format) at any byte alignment,
+// and p.dither, p.gains, p.levels and p.clipped apply (rateconv.hpp, "integer PCM in and out").  Also adds to p.levels and *p.clipped.
+hipError_t launch_rateconv_pcm(const RateconvParams &p, hipStream_t stream);
 
 }  // namespace awk

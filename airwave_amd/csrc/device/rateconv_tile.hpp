@@ -15,6 +15,15 @@
 // stores are dense although a wave's outputs lie L frames apart.  The last tile of a stream also writes the next call's history — the last
 // T - 1 frames of (history ++ call), straight from global memory — into the other slot, and the stream's counts: no tile reads what
 // another writes.  Positions in a stream are 64-bit; inside a tile they are offsets from the tile's first output and fit 32 bits.
+//
+// The PCM form (rateconv_tile_pcm; rule: rateconv.hpp, "integer PCM in and out") is the same tile with a decode in the LDS fill and an
+// encode in the pass that leaves the gathered image.  The float32 form above is the code it always was (PCM is a template argument, so no
+// branch of the PCM form is compiled into it); inside the PCM form the two formats, the dither mode, the gain and the records are uniform
+// run-time branches, for they stand outside the tap loop.  Input of any byte alignment is read in aligned 16-byte words where the whole
+// word lies inside the call's buffer and byte by byte elsewhere; an element belongs to the word that holds its first byte, and the up to
+// three bytes it may have in the next word are read singly (with the byte behind them where the buffer holds it).  On the way out a thread encodes whole elements once, in place in the gathered
+// image (so every count is taken once), and behind a barrier the tile's bytes leave as aligned 4-byte words put together from those codes,
+// with single bytes at the tile's ragged ends: no word shared with a neighbouring tile or stream is read or rewritten.
 #pragma once
 #include <cstdint>
 
@@ -27,6 +36,13 @@ constexpr int kRcLdsFloats = 12288;                               // 48 KB, stat
 constexpr int kRcMaxTile = 4096;
 constexpr int kRcSegmentShift = 5, kRcSegment = 1 << kRcSegmentShift;      // the input image lies in segments of 32 frames ...
 constexpr int kRcHalo = 3;                                        // ... each behind a copy of the 3 frames before it
+
+// One stream's record (aw_rateconv_levels): every field is a max or an integer sum.
+struct RateconvLevels {
+    uint32_t peak_bits;              // the bits of max |y| over finite samples, before gain (a float >= 0 orders as its bits do)
+    uint32_t reserved;
+    unsigned long long frames, clipped, nonfinite;
+};
 
 struct RateconvParams {
     const float *in;                 // [n_streams][in_frames][channels], dense, 4-byte aligned; NULL: in_frames frames of zeros (flush)
@@ -42,6 +58,13 @@ struct RateconvParams {
     float *hist_out;                 // ... before the next call (another buffer)
     long long consumed, produced;    // the streams' counts before this call
     long long *counts;               // [n_streams][2]: consumed, produced after it
+    // ---- the PCM form only (rateconv_tile_pcm, launch_rateconv_pcm); all zero: F32 in and out, no dither, no gain, no records ----
+    int in_format, out_format;       // awp::Format of in and out, which then are byte buffers of any alignment
+    int dither;                      // awp::Dither of an s16 / s24 encode
+    unsigned long long dither_seed, first_stream;      // global stream = first_stream + s
+    const float *gains;              // [n_streams], or NULL: no gain
+    RateconvLevels *levels;          // [n_streams], or NULL: not metered
+    unsigned long long *clipped;     // NULL, or the word every tile adds its clipped count to
 };
 
 AWP_HD int rc_block(int channels) { return channels % 4 == 0 ? 4 : channels % 2 == 0 ? 2 : 1; }
@@ -119,8 +142,148 @@ AWP_HD void rc_output(const Ctx &ctx, const float *image, const float *row, int 
     for (int e = 0; e < CB; ++e) y[e] = acc[e];
 }
 
-// `tile` counts the tiles of this call; a call without outputs runs tile 0 for the history alone.
-template <class Ctx> AWP_HD void rateconv_tile(const Ctx &ctx, const RateconvParams &p, long long s, long long tile) {
+// ---- the PCM form's element helpers ----
+AWP_HD uint32_t rc_bits(float x) {
+    uint32_t u;
+    __builtin_memcpy(&u, &x, 4);
+    return u;
+}
+// 32 bits at byte `o` (0 .. 15) of the little-endian words x0 .. x4; scalars and selects, so that nothing here is an indexed array
+AWP_HD uint32_t rc_bytes_at(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t x4, int o) {
+    const int i = o >> 2, sh = (o & 3) * 8;
+    const uint32_t lo = i == 0 ? x0 : i == 1 ? x1 : i == 2 ? x2 : x3;
+    const uint32_t hi = i == 0 ? x1 : i == 1 ? x2 : i == 2 ? x3 : x4;
+    return (uint32_t)((((unsigned long long)hi << 32) | lo) >> sh);
+}
+// the up to four bytes at `at` .. `at` + 3 of a buffer of `total` bytes as a little-endian word; bytes outside the buffer are not read
+AWP_HD uint32_t rc_word_bytewise(const unsigned char *base, long long at, long long total) {
+    uint32_t u = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (at + j >= 0 && at + j < total) u |= (uint32_t)base[at + j] << (8 * j);
+    return u;
+}
+// awp::decode_at of an element whose little-endian bytes are the low bytes of u
+AWP_HD float rc_decode(int fmt, uint32_t u) {
+    if (fmt == awp::kS16) return awp::decode_s16((int16_t)(uint16_t)u);
+    if (fmt == awp::kS24) return awp::decode_s24(u & 0xFFu, (u >> 8) & 0xFFu, (u >> 16) & 0xFFu);
+    if (fmt == awp::kS32) return awp::decode_s32((int32_t)u);
+    float f;
+    __builtin_memcpy(&f, &u, 4);
+    return f;
+}
+// awp::encode_dithered_at as the integer it would write (its low format_bytes bytes); F32: the float's bits
+AWP_HD uint32_t rc_encode(int fmt, int mode, float x, uint64_t key, uint64_t n, int e, unsigned *clip) {
+    if (fmt == awp::kS32) return (uint32_t)awp::encode_s32(x, clip);
+    if (fmt == awp::kS16 || fmt == awp::kS24) {
+        if (mode == awp::kDitherNone) return (uint32_t)(fmt == awp::kS16 ? awp::encode_s16(x, clip) : awp::encode_s24(x, clip));
+        const float d = awp::dither_value(mode, key, n, e);
+        return (uint32_t)(fmt == awp::kS16 ? awp::encode_s16_dithered(x, d, clip) : awp::encode_s24_dithered(x, d, clip));
+    }
+    return rc_bits(x);
+}
+// element e of the call's buffer (flat over [streams][frames][channels]), one element at a time: the history write
+template <bool PCM> AWP_HD float rc_input(const RateconvParams &p, long long e) {
+    if constexpr (PCM) return awp::decode_at(p.in_format, reinterpret_cast<const unsigned char *>(p.in) + e * awp::format_bytes(p.in_format));
+    else return p.in[e];
+}
+// byte b of a tile's output: byte b % bytes of the code of element b / bytes
+AWP_HD uint32_t rc_out_byte(const float *codes, int b, int bytes) {
+    const int k = bytes == 2 ? b >> 1 : bytes == 3 ? b / 3 : b >> 2;
+    return (rc_bits(codes[k]) >> (8 * (b - k * bytes))) & 0xFFu;
+}
+
+// The PCM form's LDS fill: elements e0 .. e0 + n - 1 of the call's buffer (flat over [streams][frames][channels]) decoded into image
+// frames first_frame ..; nothing outside [p.in, p.in + bytes of the call) is read.
+template <class Ctx> AWP_HD void rc_fill_pcm(const Ctx &ctx, const RateconvParams &p, float *image, long long e0, int n, int first_frame) {
+    const int C = p.channels, fi = p.in_format, bi = awp::format_bytes(fi);
+    const unsigned char *base = reinterpret_cast<const unsigned char *>(p.in);
+    const long long total = (long long)p.n_streams * p.in_frames * C * bi, b0 = e0 * bi;   // bytes of the call; byte of the span's first element
+    const int q = (int)(reinterpret_cast<uintptr_t>(base + b0) & 15u);                    // bytes between the 16-byte boundary below and the span
+    const bool straddles = bi == 3 || (reinterpret_cast<uintptr_t>(base) & (uintptr_t)(bi - 1)) != 0;      // elements may cross a word's end
+    const int n_words = (n * bi + q + 15) >> 4;
+    for (int w = ctx.tid(); w < n_words; w += kRcThreads) {
+        const int r0 = 16 * w - q;                                 // byte of the span the word starts at
+        const long long wb = b0 + r0;                              // ... of the buffer
+        uint32_t x0, x1, x2, x3;
+        if (wb >= 0 && wb + 16 <= total) {
+            float v[4];
+            ctx.ld16(reinterpret_cast<const float *>(base + wb), v);
+            x0 = rc_bits(v[0]); x1 = rc_bits(v[1]); x2 = rc_bits(v[2]); x3 = rc_bits(v[3]);
+        } else {                                                   // a word that reaches past the buffer: its bytes one by one
+            x0 = rc_word_bytewise(base, wb, total); x1 = rc_word_bytewise(base, wb + 4, total);
+            x2 = rc_word_bytewise(base, wb + 8, total); x3 = rc_word_bytewise(base, wb + 12, total);
+        }
+        const uint32_t x4 = straddles ? rc_word_bytewise(base, wb + 16, total) : 0u;      // what an element that starts here has over there
+        int k = r0 <= 0 ? 0 : (r0 + bi - 1) / bi;                  // the first element that starts in this word
+#pragma unroll
+        for (int j = 0; j < 8; ++j, ++k) {                         // (at most 8 elements start in 16 bytes)
+            const int o = k * bi - r0;
+            if (o < 16 && k < n) {
+                const int f = k / C;
+                rc_store(image, first_frame + f, k - f * C, C, rc_decode(fi, rc_bytes_at(x0, x1, x2, x3, x4, o)));
+            }
+        }
+    }
+}
+
+// The PCM form's way out of the gathered image [valid][C]: gain, dither, encode and the records, then the tile's own bytes.
+template <class Ctx> AWP_HD void rc_leave_pcm(const Ctx &ctx, const RateconvParams &p, float *gathered, long long s, long long o0, int valid) {
+    const int t = ctx.tid(), C = p.channels, fo = p.out_format, bo = awp::format_bytes(fo);
+    const float g = p.gains ? p.gains[s] : 1.0f;
+    const uint64_t key0 = awp::dither_key(p.dither_seed, p.first_stream + (uint64_t)s);
+    const uint64_t n0 = (uint64_t)(p.produced + o0);
+    uint32_t peak = 0u;
+    unsigned nonfinite = 0u, clipped = 0u;
+    for (int k = t; k < valid * C; k += kRcThreads) {              // element k: read, encoded and put back by this thread alone
+        const int f = k / C, ch = k - f * C;
+        const float y = gathered[k];
+        const uint32_t a = rc_bits(y) & 0x7FFFFFFFu;
+        if (a >= 0x7F800000u) ++nonfinite; else peak = a > peak ? a : peak;
+        const float u = p.gains ? y * g : y;
+        unsigned clip = 0u;
+        const uint32_t code = rc_encode(fo, p.dither, u, key0 + (uint64_t)(ch >> 1) * 0xA0761D6478BD642Full, n0 + (uint64_t)f, ch & 1, &clip);
+        __builtin_memcpy(&gathered[k], &code, 4);                  // (the image stays an array of float: its elements now carry the codes' bits)
+        clipped += clip;
+    }
+    if (p.levels || p.clipped) {                                   // (uniform: every wave is whole at the wave operations)
+        const unsigned c = ctx.wave_sum(clipped);
+        if ((t & 63) == 0 && c) {
+            if (p.levels) ctx.atomic_add(&p.levels[s].clipped, (unsigned long long)c);
+            if (p.clipped) ctx.atomic_add(p.clipped, (unsigned long long)c);
+        }
+    }
+    if (p.levels) {
+        const uint32_t m = ctx.wave_max(peak);
+        const unsigned nf = ctx.wave_sum(nonfinite);
+        if ((t & 63) == 0) {
+            if (m) ctx.atomic_max(&p.levels[s].peak_bits, m);
+            if (nf) ctx.atomic_add(&p.levels[s].nonfinite, (unsigned long long)nf);
+        }
+        if (t == 0) ctx.atomic_add(&p.levels[s].frames, (unsigned long long)valid);
+    }
+    ctx.barrier();
+    unsigned char *out = reinterpret_cast<unsigned char *>(p.out) + (s * p.out_frames + o0) * C * bo;
+    const int n = valid * C * bo;                                  // the tile's bytes
+    int head = (int)((4u - (unsigned)(reinterpret_cast<uintptr_t>(out) & 3u)) & 3u);       // ... in front of its first whole word
+    head = head < n ? head : n;
+    const int n_words = (n - head) >> 2, tail = head + 4 * n_words;
+    if (bo == 4 && head == 0) {
+        for (int w = t; w < n_words; w += kRcThreads) reinterpret_cast<uint32_t *>(out)[w] = rc_bits(gathered[w]);
+    } else {
+        for (int w = t; w < n_words; w += kRcThreads) {
+            const int b = head + 4 * w;
+            *reinterpret_cast<uint32_t *>(out + b) = rc_out_byte(gathered, b, bo) | (rc_out_byte(gathered, b + 1, bo) << 8) |
+                                                     (rc_out_byte(gathered, b + 2, bo) << 16) | (rc_out_byte(gathered, b + 3, bo) << 24);
+        }
+    }
+    if (t < head) out[t] = (unsigned char)rc_out_byte(gathered, t, bo);
+    if (t >= 64 && t - 64 < n - tail) out[tail + t - 64] = (unsigned char)rc_out_byte(gathered, tail + t - 64, bo);
+}
+
+// `tile` counts the tiles of this call; a call without outputs runs tile 0 for the history alone.  PCM: p.in and p.out are byte buffers of
+// p.in_format and p.out_format, and the gain, the dither and the records of p apply; else the float32 form, which reads none of those.
+template <bool PCM, class Ctx> AWP_HD void rateconv_tile_form(const Ctx &ctx, const RateconvParams &p, long long s, long long tile) {
     float *image = ctx.lds();
     const int t = ctx.tid();
     const int C = p.channels, T = p.taps, D = p.latency, CB = rc_block(C);
@@ -144,6 +307,8 @@ template <class Ctx> AWP_HD void rateconv_tile(const Ctx &ctx, const RateconvPar
                 const int f = k / C;
                 rc_store(image, n_hist + f, k - f * C, C, 0.0f);
             }
+        } else if constexpr (PCM) {
+            if (n_floats > 0) rc_fill_pcm(ctx, p, image, (s * p.in_frames + (rel + n_hist)) * C, n_floats, n_hist);
         } else if (n_floats > 0) {
             const long long e0 = (s * p.in_frames + (rel + n_hist)) * C, n_total = (long long)p.n_streams * p.in_frames * C;
             const int q = (int)((reinterpret_cast<uintptr_t>(p.in + e0) >> 2) & 3u);       // floats between the 16-byte boundary below and the span
@@ -184,14 +349,18 @@ template <class Ctx> AWP_HD void rateconv_tile(const Ctx &ctx, const RateconvPar
             else rc_output<1>(ctx, image + b, row, f0, C, T, y);
         }
         ctx.barrier();
-        float *out = p.out + (s * p.out_frames + o0) * C;
-        for (int k = t; k < valid * C; k += kRcThreads) out[k] = gathered[k];
+        if constexpr (PCM) {
+            rc_leave_pcm(ctx, p, gathered, s, o0, valid);
+        } else {
+            float *out = p.out + (s * p.out_frames + o0) * C;
+            for (int k = t; k < valid * C; k += kRcThreads) out[k] = gathered[k];
+        }
     }
     const long long tiles = (p.out_frames + p.tile - 1) / p.tile;
     if (tile == (tiles > 0 ? tiles - 1 : 0)) {                     // the stream's last tile: the last T - 1 frames of (history ++ call)
         for (int k = t; k < (T - 1) * C; k += kRcThreads) {
             const long long f = p.in_frames - (T - 1) + k / C;     // frame of the call
-            p.hist_out[s * (T - 1) * C + k] = f >= 0 ? (p.in ? p.in[(s * p.in_frames + f) * C + k % C] : 0.0f)
+            p.hist_out[s * (T - 1) * C + k] = f >= 0 ? (p.in ? rc_input<PCM>(p, (s * p.in_frames + f) * C + k % C) : 0.0f)
                                                      : p.hist_in[(s * (T - 1) + (f + (T - 1))) * C + k % C];
         }
         if (t == 0) {
@@ -199,6 +368,13 @@ template <class Ctx> AWP_HD void rateconv_tile(const Ctx &ctx, const RateconvPar
             p.counts[2 * s + 1] = p.produced + p.out_frames;
         }
     }
+}
+
+template <class Ctx> AWP_HD void rateconv_tile(const Ctx &ctx, const RateconvParams &p, long long s, long long tile) {
+    rateconv_tile_form<false>(ctx, p, s, tile);
+}
+template <class Ctx> AWP_HD void rateconv_tile_pcm(const Ctx &ctx, const RateconvParams &p, long long s, long long tile) {
+    rateconv_tile_form<true>(ctx, p, s, tile);
 }
 
 }  // namespace awk

@@ -1,8 +1,10 @@
 // rateconv_runtime.cpp — C ABI of the batch sample-rate converter (aw_rateconv_*, include/airwave_hip.h): the rules are
 // device/rateconv.hpp, the kernel device/rateconv_tile.hpp.  Audio-rate conversion has no counterpart in the reference, whose two-point
 // linear interpolation (Resampler.swift:31-68, aw_resample) is for an HRIR at activation and images and aliases at about -30 dB on audio.
+// The aw_pcm_rateconv_* entries run the same handle through the kernel's PCM form (integer PCM in and out, dither, gain, records).
 // One owner thread per handle, like every other handle of this library; the handle goes as aw_eq does: device current, stream idle, then
 // its members.
+#include <cmath>
 #include <memory>
 #include <new>
 #include <string>
@@ -36,7 +38,18 @@ struct aw_rateconv {
     awr::Buf<float> d_hist[2];                 // [streams][taps - 1][channels]: a call reads slot cur and writes the other
     awr::Buf<long long> d_counts;              // [streams][2], written by each call's last tiles
     int cur = 0;
+    // the aw_pcm_rateconv_* entries' settings; aw_rateconv_process / _flush / _reset ignore them
+    int dither = AW_DITHER_NONE;
+    uint64_t dither_seed = 0, first_stream = 0;
+    int gain_mode = AW_GAIN_NONE;
+    int metering = 0;
+    awr::Buf<float> d_gains;                   // [streams], made by set_gain(AW_GAIN_FIXED)
+    awr::Buf<awk::RateconvLevels> d_levels;    // [streams], made by set_metering(on); aw_rateconv_levels is its layout
 };
+
+static_assert(sizeof(aw_rateconv_levels) == 32 && sizeof(awk::RateconvLevels) == 32, "aw_rateconv_levels is the kernel's record");
+static_assert(AW_SAMPLE_F32 == awp::kF32 && AW_SAMPLE_S16 == awp::kS16 && AW_SAMPLE_S24 == awp::kS24 && AW_SAMPLE_S32 == awp::kS32, "formats");
+static_assert(AW_DITHER_NONE == awp::kDitherNone && AW_DITHER_TPDF == awp::kDitherTpdf && AW_DITHER_TPDF_HP == awp::kDitherTpdfHp, "dither modes");
 
 namespace {
 
@@ -47,8 +60,14 @@ aw_status reset_state(aw_rateconv *rc) {
     return AW_OK;
 }
 
-// in NULL: in_frames frames of zeros
-aw_status run(aw_rateconv *rc, const float *in, long long in_frames, float *out, long long capacity, int64_t *out_frames) {
+// What an aw_pcm_rateconv_* call adds to the float32 form.
+struct PcmCall {
+    aw_sample_format in_format, out_format;
+    uint64_t *clipped;
+};
+
+// in NULL: in_frames frames of zeros; pcm NULL: the float32 form
+aw_status run(aw_rateconv *rc, const void *in, long long in_frames, void *out, long long capacity, int64_t *out_frames, const PcmCall *pcm = nullptr) {
     const awrc::Plan &pl = rc->plan;
     const long long n_out = awrc::outputs_after(rc->counts.consumed + in_frames, pl.L, pl.M, pl.latency) - rc->counts.produced;
     if (capacity < n_out)
@@ -59,13 +78,22 @@ aw_status run(aw_rateconv *rc, const float *in, long long in_frames, float *out,
     if (in_frames == 0) return AW_OK;
     AW_HIP_TRY(hipSetDevice(rc->ctx->device));
     awk::RateconvParams p{};
-    p.in = in; p.in_frames = in_frames; p.out = out; p.out_frames = n_out;
+    p.in = static_cast<const float *>(in); p.in_frames = in_frames; p.out = static_cast<float *>(out); p.out_frames = n_out;
     p.n_streams = rc->n_streams; p.channels = rc->n_channels;
     p.L = pl.L; p.M = pl.M; p.taps = pl.taps; p.latency = pl.latency;
     p.tile = rc->tile; p.row_stride = awk::rc_row_stride(pl.taps); p.c = rc->d_c.get();
     p.hist_in = rc->d_hist[rc->cur].get(); p.hist_out = rc->d_hist[rc->cur ^ 1].get();
     p.consumed = rc->counts.consumed; p.produced = rc->counts.produced; p.counts = rc->d_counts.get();
-    AW_HIP_TRY(awk::launch_rateconv(p, rc->ctx->stream));
+    if (pcm) {
+        p.in_format = pcm->in_format; p.out_format = pcm->out_format;
+        p.dither = rc->dither; p.dither_seed = rc->dither_seed; p.first_stream = rc->first_stream;
+        p.gains = rc->gain_mode == AW_GAIN_FIXED ? rc->d_gains.get() : nullptr;
+        p.levels = rc->metering ? rc->d_levels.get() : nullptr;
+        p.clipped = reinterpret_cast<unsigned long long *>(pcm->clipped);
+        AW_HIP_TRY(awk::launch_rateconv_pcm(p, rc->ctx->stream));
+    } else {
+        AW_HIP_TRY(awk::launch_rateconv(p, rc->ctx->stream));
+    }
     rc->cur ^= 1;
     rc->counts.consumed += in_frames;
     rc->counts.produced += n_out;
@@ -148,6 +176,9 @@ int64_t aw_rateconv_info(const aw_rateconv *rc, int32_t what) {
         case 4: return rc->tile;
         case 5: return rc->counts.consumed;
         case 6: return rc->counts.produced;
+        case 7: return rc->dither;
+        case 8: return rc->gain_mode;
+        case 9: return rc->metering;
         default: return -1;
     }
 }
@@ -179,6 +210,86 @@ aw_status aw_rateconv_reset(aw_rateconv *rc) try {
     if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
     AW_HIP_TRY(hipSetDevice(rc->ctx->device));
     return reset_state(rc);
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_pcm_rateconv_process(aw_rateconv *rc, const void *in_device, aw_sample_format in_format, int64_t in_frames, void *out_device,
+                                  aw_sample_format out_format, int64_t out_capacity_frames, int64_t *out_frames, uint64_t *clipped_device) try {
+    if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
+    if (!awp::format_bytes(in_format) || !awp::format_bytes(out_format)) return fail(AW_ERR_INVALID_ARGUMENT, "unknown sample format");
+    if (in_frames < 0) return fail(AW_ERR_INVALID_ARGUMENT, "in_frames must be >= 0");
+    if (in_frames > 0 && !in_device) return fail(AW_ERR_INVALID_ARGUMENT, "in_device is NULL");
+    const PcmCall call{in_format, out_format, clipped_device};
+    return run(rc, in_device, in_frames, out_device, out_capacity_frames, out_frames, &call);
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_pcm_rateconv_flush(aw_rateconv *rc, void *out_device, aw_sample_format out_format, int64_t out_capacity_frames, int64_t *out_frames,
+                                uint64_t *clipped_device) try {
+    if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
+    if (!awp::format_bytes(out_format)) return fail(AW_ERR_INVALID_ARGUMENT, "unknown sample format");
+    const PcmCall call{AW_SAMPLE_F32, out_format, clipped_device};
+    const aw_status st = run(rc, nullptr, rc->plan.latency, out_device, out_capacity_frames, out_frames, &call);
+    if (st != AW_OK) return st;
+    return reset_state(rc);
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_pcm_rateconv_set_dither(aw_rateconv *rc, aw_dither mode, uint64_t seed, uint64_t first_stream) try {
+    if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
+    if (mode != AW_DITHER_NONE && mode != AW_DITHER_TPDF && mode != AW_DITHER_TPDF_HP) return fail(AW_ERR_INVALID_ARGUMENT, "unknown dither mode");
+    rc->dither = mode; rc->dither_seed = seed; rc->first_stream = first_stream;
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_pcm_rateconv_set_gain(aw_rateconv *rc, aw_gain_mode mode, const float *gains_host, int32_t n) try {
+    if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
+    if (mode == AW_GAIN_NONE) { rc->gain_mode = AW_GAIN_NONE; return AW_OK; }
+    if (mode == AW_GAIN_PEAK_CEILING || mode == AW_GAIN_TRUE_PEAK_CEILING)
+        return fail(AW_ERR_INVALID_ARGUMENT, "the ceiling gains are per-call functions of a peak, which the one-pass converter does not have: meter, then set AW_GAIN_FIXED");
+    if (mode != AW_GAIN_FIXED) return fail(AW_ERR_INVALID_ARGUMENT, "unknown gain mode");
+    if (!gains_host || (n != 1 && n != rc->n_streams)) return fail(AW_ERR_INVALID_ARGUMENT, "AW_GAIN_FIXED takes 1 gain or one per stream");
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(gains_host[i])) return fail(AW_ERR_INVALID_ARGUMENT, "gain " + std::to_string(i) + " is not finite");
+    std::vector<float> g((size_t)rc->n_streams);
+    for (int s = 0; s < rc->n_streams; ++s) g[(size_t)s] = gains_host[n == 1 ? 0 : s];
+    AW_HIP_TRY(hipSetDevice(rc->ctx->device));
+    AW_HIP_TRY(hipStreamSynchronize(rc->ctx->stream));          // (no call still reads the gains this one replaces)
+    awr::Buf<float> fresh;
+    AW_HIP_TRY(fresh.upload(g.data(), g.size(), &rc->ctx->device_allocs, &rc->ctx->sync_copies));
+    rc->d_gains = std::move(fresh);
+    rc->gain_mode = AW_GAIN_FIXED;
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_pcm_rateconv_set_metering(aw_rateconv *rc, int32_t on) try {
+    if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
+    if (on && !rc->d_levels) {
+        AW_HIP_TRY(hipSetDevice(rc->ctx->device));
+        awr::Buf<awk::RateconvLevels> fresh;
+        AW_HIP_TRY(fresh.alloc((size_t)rc->n_streams, &rc->ctx->device_allocs));
+        AW_HIP_TRY(hipMemsetAsync(fresh.get(), 0, fresh.bytes(), rc->ctx->stream));
+        rc->d_levels = std::move(fresh);
+    }
+    rc->metering = on ? 1 : 0;
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_pcm_rateconv_get_levels(aw_rateconv *rc, int32_t first_stream, int32_t n, aw_rateconv_levels *out_host) try {
+    if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
+    if (!out_host) return fail(AW_ERR_INVALID_ARGUMENT, "out_host is NULL");
+    if (first_stream < 0 || n < 0 || (long long)first_stream + n > rc->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "stream range outside the handle");
+    if (!rc->d_levels) return fail(AW_ERR_INVALID_ARGUMENT, "aw_pcm_rateconv_set_metering was never called on this handle");
+    AW_HIP_TRY(hipSetDevice(rc->ctx->device));
+    if (n > 0)
+        AW_HIP_TRY(hipMemcpyAsync(out_host, rc->d_levels.get() + first_stream, (size_t)n * sizeof(aw_rateconv_levels), hipMemcpyDeviceToHost, rc->ctx->stream));
+    AW_HIP_TRY(hipStreamSynchronize(rc->ctx->stream));
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_pcm_rateconv_reset_levels(aw_rateconv *rc) try {
+    if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
+    if (!rc->d_levels) return AW_OK;
+    AW_HIP_TRY(hipSetDevice(rc->ctx->device));
+    AW_HIP_TRY(hipMemsetAsync(rc->d_levels.get(), 0, rc->d_levels.bytes(), rc->ctx->stream));
+    return AW_OK;
 } AW_NOEXCEPT_TAIL
 
 }  // extern "C"

@@ -10,9 +10,20 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import _capi
-from .api import Context, _check, _f32, _finalizing, _fp, default_context
+from .api import (DITHER_MODES, GAIN_MODES, SAMPLE_FORMATS, _FORMAT_DTYPE, Context, _check, _f32, _finalizing, _fp, _pcm_array,
+                  default_context)
 
-_INFO = ("L", "M", "taps", "latency", "tile", "frames_consumed", "frames_produced")
+_INFO = ("L", "M", "taps", "latency", "tile", "frames_consumed", "frames_produced", "dither", "gain_mode", "metering")
+# aw_rateconv_levels, byte for byte (RateConverter.levels)
+RATECONV_LEVELS_DTYPE = np.dtype([("peak", np.float32), ("reserved", np.uint32), ("frames", np.uint64), ("clipped", np.uint64),
+                                  ("nonfinite", np.uint64)], align=False)
+
+
+def _format_code(fmt) -> int:
+    code = SAMPLE_FORMATS.get(fmt, -1) if isinstance(fmt, str) else int(fmt)
+    if code not in _FORMAT_DTYPE:
+        raise ValueError(f"unknown sample format {fmt!r}")
+    return code
 
 
 def rateconv_plan(in_rate: float, out_rate: float) -> Dict[str, int]:
@@ -45,7 +56,11 @@ class RateConverter:
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.aw_rateconv_destroy(self._h)
+            # a reference cycle is finalised in no particular order: where the context went first, its stream is gone, and
+            # aw_rateconv_destroy, which waits for that stream, must not run (what the handle owns on the device then stays
+            # allocated until the process ends)
+            if getattr(self.ctx, "_h", None):
+                self._lib.aw_rateconv_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -113,18 +128,127 @@ class RateConverter:
     def reset(self) -> None:
         _check(self._lib.aw_rateconv_reset(self._h))
 
+    # ---- integer PCM in and out, with dither, gain and levels (aw_pcm_rateconv_*) ----
 
-def convert(x, in_rate: float, out_rate: float, ctx: Optional[Context] = None) -> np.ndarray:
-    """One shot: x [streams][N][channels] (or [N][channels]) -> [..][ceil(N L / M)][channels]: process + flush, concatenated."""
-    a = _f32(x)
-    squeeze = a.ndim == 2
+    def process_pcm_device(self, in_ptr: int, in_format, in_frames: int, out_ptr: int, out_format, capacity: int, clipped_ptr: int = 0) -> int:
+        """aw_pcm_rateconv_process on device buffers of any byte alignment; formats by name ('f32', 's16', 's24', 's32') or code.
+        clipped_ptr: 0, or a device uint64 the call adds its clipped-sample count to.  Returns the frames written."""
+        n = ctypes.c_int64()
+        _check(self._lib.aw_pcm_rateconv_process(self._h, ctypes.c_void_p(in_ptr), _format_code(in_format), int(in_frames), ctypes.c_void_p(out_ptr),
+                                                 _format_code(out_format), int(capacity), ctypes.byref(n), ctypes.c_void_p(clipped_ptr or None)))
+        return int(n.value)
+
+    def flush_pcm_device(self, out_ptr: int, out_format, capacity: int, clipped_ptr: int = 0) -> int:
+        n = ctypes.c_int64()
+        _check(self._lib.aw_pcm_rateconv_flush(self._h, ctypes.c_void_p(out_ptr), _format_code(out_format), int(capacity), ctypes.byref(n),
+                                               ctypes.c_void_p(clipped_ptr or None)))
+        return int(n.value)
+
+    def set_dither(self, mode, seed: int = 0, first_stream: int = 0) -> None:
+        """aw_pcm_rateconv_set_dither: dither of every later s16 / s24 encode of the PCM entries ('none', 'tpdf', 'tpdf_hp', or the
+        aw_dither code).  first_stream: the global index of this handle's stream 0."""
+        if isinstance(mode, str):
+            if mode not in DITHER_MODES:
+                raise ValueError(f"unknown dither mode {mode!r} (one of {', '.join(DITHER_MODES)})")
+            mode = DITHER_MODES[mode]
+        _check(self._lib.aw_pcm_rateconv_set_dither(self._h, int(mode), int(seed), int(first_stream)))
+
+    def set_gain(self, mode, gains=None) -> None:
+        """aw_pcm_rateconv_set_gain: 'none', or 'fixed' with one gain (every stream) or one per stream.  The ceiling modes are refused by
+        the library: they are per-call functions of a peak, which the one-pass converter does not have."""
+        if isinstance(mode, str):
+            if mode not in GAIN_MODES:
+                raise ValueError(f"unknown gain mode {mode!r} (one of {', '.join(GAIN_MODES)})")
+            mode = GAIN_MODES[mode]
+        g = None
+        if gains is not None:
+            g = np.ascontiguousarray(np.atleast_1d(np.asarray(gains, np.float32)))
+            if g.ndim != 1:
+                raise ValueError(f"gains must be 1 or {self.n_streams} values, got shape {g.shape}")
+        _check(self._lib.aw_pcm_rateconv_set_gain(self._h, int(mode), None if g is None else _fp(g), 0 if g is None else int(g.size)))
+
+    def set_metering(self, on: bool = True) -> None:
+        """aw_pcm_rateconv_set_metering: per-stream records of every later PCM call; switching it on allocates them here."""
+        _check(self._lib.aw_pcm_rateconv_set_metering(self._h, int(bool(on))))
+
+    def levels(self, first_stream: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """aw_pcm_rateconv_get_levels: the records of n streams from first_stream on (default: all) as a structured array of
+        RATECONV_LEVELS_DTYPE (peak, frames, clipped, nonfinite).  Synchronises the context's stream."""
+        first_stream = int(first_stream)
+        n = self.n_streams - first_stream if n is None else int(n)
+        out = np.zeros(max(n, 0), RATECONV_LEVELS_DTYPE)
+        _check(self._lib.aw_pcm_rateconv_get_levels(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
+        return out
+
+    def reset_levels(self) -> None:
+        _check(self._lib.aw_pcm_rateconv_reset_levels(self._h))
+
+    def _pcm_to_host(self, run, n_out: int, fo: int):
+        """-> (array in the conventions of Spatializer's PCM methods, clipped count of the call)."""
+        shape = (self.n_streams, n_out, self.n_channels) + ((3,) if fo == 2 else ())
+        out = np.zeros(shape, _FORMAT_DTYPE[fo])
+        d = self.ctx.alloc(max(out.nbytes, 4) + 8)       # the clipped count leads, the samples follow it
+        d_clip = d
+        try:
+            zero = np.zeros(1, np.uint64)
+            self.ctx.h2d(d_clip, zero)
+            made = run(d + 8, n_out, d_clip)
+            assert made == n_out
+            if out.size:
+                self.ctx.d2h(out, d + 8)
+            self.ctx.d2h(zero, d_clip)
+        finally:
+            self.ctx.free(d)
+        return out, int(zero[0])
+
+    def process_pcm(self, x, out_format, in_format=None):
+        """Host arrays: x [streams][frames][channels] of int16, int32, float32 or packed s24 (uint8 [..., 3], in_format='s24') ->
+        (y, clipped): y [streams][output_frames(frames)][channels] in out_format (packed s24: uint8 [..., 3]) and the call's clipped count."""
+        if not isinstance(x, np.ndarray) or x.ndim < 3:
+            raise ValueError("x: [streams][frames][channels] array required")
+        frames = x.shape[1]
+        x, fi = _pcm_array(x, in_format, (self.n_streams, frames, self.n_channels), "x")
+        fo = _format_code(out_format)
+        if frames == 0:
+            return np.zeros((self.n_streams, 0, self.n_channels) + ((3,) if fo == 2 else ()), _FORMAT_DTYPE[fo]), 0
+        d_in = self.ctx.alloc(x.nbytes)
+        try:
+            self.ctx.h2d(d_in, x)
+            return self._pcm_to_host(lambda d, cap, clip: self.process_pcm_device(d_in, fi, frames, d, fo, cap, clip), self.output_frames(frames), fo)
+        finally:
+            self.ctx.free(d_in)
+
+    def flush_pcm(self, out_format):
+        """(the outputs still owed in out_format, their clipped count), then reset(); the records stay."""
+        fo = _format_code(out_format)
+        return self._pcm_to_host(lambda d, cap, clip: self.flush_pcm_device(d, fo, cap, clip), self.flush_frames(), fo)
+
+
+def convert(x, in_rate: float, out_rate: float, ctx: Optional[Context] = None, out_format=None, dither="none", seed: int = 0,
+            in_format=None) -> np.ndarray:
+    """One shot: x [streams][N][channels] (or [N][channels]) -> [..][ceil(N L / M)][channels]: process + flush, concatenated.  With
+    out_format ('f32', 's16', 's24', 's32') x may be int16, int32, float32 or packed s24 (uint8 [..., 3], in_format='s24') and the result
+    is in out_format, s16 / s24 dithered by `dither` ('none', 'tpdf', 'tpdf_hp') with `seed`."""
+    if out_format is None:
+        if dither not in ("none", 0) or in_format is not None:
+            raise ValueError("dither and in_format need an out_format")
+        a = _f32(x)
+        packed = 0
+    else:
+        a = np.ascontiguousarray(x)
+        packed = 1 if (in_format in ("s24", 2)) else 0
+    squeeze = a.ndim - packed == 2
     if squeeze:
         a = a[None]
-    if a.ndim != 3:
+    if a.ndim - packed != 3:
         raise ValueError(f"expected [streams][frames][channels] or [frames][channels], got {a.shape}")
     rc = RateConverter(in_rate, out_rate, a.shape[0], a.shape[2], ctx=ctx)
     try:
-        y = np.concatenate([rc.process(a), rc.flush()], axis=1)
+        if out_format is None:
+            y = np.concatenate([rc.process(a), rc.flush()], axis=1)
+        else:
+            rc.set_dither(dither, seed)
+            y = np.concatenate([rc.process_pcm(a, out_format, in_format)[0], rc.flush_pcm(out_format)[0]], axis=1)
     finally:
         rc.close()
     return y[0] if squeeze else y

@@ -682,13 +682,74 @@ AW_API aw_status aw_rateconv_plan(double in_rate, double out_rate, int32_t *L, i
 AW_API aw_status aw_rateconv_filter(double in_rate, double out_rate, float *c /* [L][taps] */, int64_t capacity_floats);
 AW_API aw_status aw_rateconv_create(aw_context *ctx, double in_rate, double out_rate, int32_t n_streams, int32_t n_channels, aw_rateconv **out);
 AW_API void aw_rateconv_destroy(aw_rateconv *rc);
-/* what: 0 L, 1 M, 2 taps, 3 latency, 4 tile (output frames per workgroup), 5 frames consumed, 6 frames produced; -1 otherwise */
+/* what: 0 L, 1 M, 2 taps, 3 latency, 4 tile (output frames per workgroup), 5 frames consumed, 6 frames produced, 7 the aw_dither mode,
+ * 8 the aw_gain_mode, 9 metering on (7 - 9: the settings of the aw_pcm_rateconv_* entries below); -1 otherwise */
 AW_API int64_t aw_rateconv_info(const aw_rateconv *rc, int32_t what);
 AW_API int64_t aw_rateconv_output_frames(const aw_rateconv *rc, int64_t in_frames);  /* what the next process call of in_frames writes */
 AW_API aw_status aw_rateconv_process(aw_rateconv *rc, const float *in_device, int64_t in_frames, float *out_device,
                                      int64_t out_capacity_frames, int64_t *out_frames);
 AW_API aw_status aw_rateconv_flush(aw_rateconv *rc, float *out_device, int64_t out_capacity_frames, int64_t *out_frames);
 AW_API aw_status aw_rateconv_reset(aw_rateconv *rc);
+/* Integer PCM in and out of the converter, with dither, gain and levels: the same handle through the entries below, so that a converter
+ * behind a spatializer writes the file a host delivers (s16 / s24 / s32, dithered, gained, metered, with a clip count) and one in front of
+ * a spatializer reads the 16- or 24-bit PCM a host holds.  Decode and encode are fused into the converter's kernel: there is no float32
+ * staging and no allocation on a process path.  aw_rateconv_process, _flush and _reset keep their behaviour exactly and ignore dither,
+ * gain and metering; both families may be mixed on one handle from call to call, and so may the formats (the carried history is float32).
+ * For stream s of the handle (global stream first_stream + s) and channel ch:
+ *  - decode: x is the input; F32 as it is, s16 / s24 / s32 by the rules of "integer PCM sample formats" above (exact: the scales are
+ *    powers of two).
+ *  - convert: y is what the rule of aw_rateconv_process makes of x.  F32 in, F32 out, no gain and no dither gives its bits.
+ *  - gain: u = (float)(y * g_s) under AW_GAIN_FIXED, u = y under AW_GAIN_NONE.
+ *  - encode: F32 output is u; s32 is the s32 rule above, never dithered; s16 / s24 are rintf(u * 32768.0f + d) / rintf(u * 8388608.0f + d),
+ *    saturated, with the NaN and clip rules above and d the dither of aw_spatializer_set_dither's formulas at position p = n, ear
+ *    e = ch & 1 and key K_j, j = ch >> 1:
+ *      n   = the stream's absolute output frame index since the last reset or flush (aw_rateconv_info 6 plus the frame's index in the call)
+ *      K_j = ((seed ^ 0xD1B54A32D192ED03) + first_stream + s) * 0x9E3779B97F4A7C15 + j * 0xA0761D6478BD642F   (mod 2^64).
+ *    For a stereo converter K_0 is the spatializer's key: the noise of frame n is bit for bit what aw_spatializer_set_dither with the same
+ *    seed and first stream gives at position n.  Further channel pairs get keys of their own (the spatializer's 2p + e counter would
+ *    collide from the third channel on).
+ *  - records (aw_rateconv_levels), per stream, while metering is on: peak = max |y| over finite samples of all channels, BEFORE the gain;
+ *    nonfinite counts NaN / +-inf y; frames counts output frames written; clipped counts the samples the integer encode clipped, after
+ *    gain and dither.  Every field is a max or an integer sum, so every field is exact.  Reset and flush restart n at 0 and leave the
+ *    records alone: they live until aw_pcm_rateconv_reset_levels, so a host reads them after the flush.
+ *  - clipped_device: NULL, or a device uint64 that the call atomically adds its clipped count to, as in aw_spatializer_process_pcm; it
+ *    works with metering off.
+ *  - flush feeds `latency` frames of zeros whatever the input format was, writes in out_format, then resets as aw_rateconv_flush does.
+ *  - splitting calls in time, sharding streams over handles (with first_stream), the byte alignment of either buffer and the kernel's
+ *    tiling change no output byte and no record field.  Buffers may have ANY byte alignment, F32 included (F32 keeps its 4-byte rule
+ *    only through aw_rateconv_process / _flush).
+ *  - loudness, true peak and the limiter of a spatializer in front of the converter measure the signal BEFORE conversion; the converter's
+ *    own peak is the SAMPLE peak after it.  A true-peak meter or limiter after the converter is not provided here.
+ * An unknown format, a NULL handle, a NULL input with in_frames > 0 or a capacity below the count returns AW_ERR_INVALID_ARGUMENT before
+ * any HIP call, leaves the handle untouched and does not write *out_frames.  Process, flush and reset_levels only enqueue on the context's
+ * stream; get_levels copies on that stream and then synchronises it. */
+typedef struct aw_rateconv_levels {
+    float    peak;         /* max |y| over finite samples of every channel, before gain */
+    uint32_t reserved;     /* 0 */
+    uint64_t frames;       /* output frames written */
+    uint64_t clipped;      /* samples the integer encodes clipped (after gain and dither) */
+    uint64_t nonfinite;    /* NaN / inf samples y */
+} aw_rateconv_levels;      /* 32 bytes */
+AW_API aw_status aw_pcm_rateconv_process(aw_rateconv *rc, const void *in_device, aw_sample_format in_format, int64_t in_frames,
+                                         void *out_device, aw_sample_format out_format, int64_t out_capacity_frames, int64_t *out_frames,
+                                         uint64_t *clipped_device);
+AW_API aw_status aw_pcm_rateconv_flush(aw_rateconv *rc, void *out_device, aw_sample_format out_format, int64_t out_capacity_frames,
+                                       int64_t *out_frames, uint64_t *clipped_device);
+/* Applies to every later s16 / s24 encode of the aw_pcm_rateconv_* entries.  An unknown mode is refused.  Allocates nothing. */
+AW_API aw_status aw_pcm_rateconv_set_dither(aw_rateconv *rc, aw_dither mode, uint64_t seed, uint64_t first_stream);
+/* AW_GAIN_NONE: gains_host and n are ignored.  AW_GAIN_FIXED: n finite gains, n == 1 (every stream) or n == the stream count, uploaded by
+ * this call (one allocation; it waits for the context's stream first).  AW_GAIN_PEAK_CEILING and AW_GAIN_TRUE_PEAK_CEILING are refused
+ * with AW_ERR_INVALID_ARGUMENT: they are per-call functions of a peak, which the one-pass kernel does not have.  A refusal leaves the
+ * previous setting. */
+AW_API aw_status aw_pcm_rateconv_set_gain(aw_rateconv *rc, aw_gain_mode mode, const float *gains_host, int32_t n);
+/* on != 0: allocates the records at the first such call (one allocation, never on a process path) and meters every later
+ * aw_pcm_rateconv_* call; 0: stops metering, the records stay readable. */
+AW_API aw_status aw_pcm_rateconv_set_metering(aw_rateconv *rc, int32_t on);
+/* Copies the records of streams [first_stream, first_stream + n) to out_host on the context's stream, then synchronises it.  A range
+ * outside the handle's streams, or a handle on which set_metering(on) was never called, returns AW_ERR_INVALID_ARGUMENT. */
+AW_API aw_status aw_pcm_rateconv_get_levels(aw_rateconv *rc, int32_t first_stream, int32_t n, aw_rateconv_levels *out_host);
+/* Zeroes every record (asynchronous on the context's stream); the settings stay. */
+AW_API aw_status aw_pcm_rateconv_reset_levels(aw_rateconv *rc);
 
 AW_API const char *aw_version(void);
 

@@ -281,6 +281,29 @@ class RateConverter {
         return n;
     }
     void reset() { check(aw_rateconv_reset(h_)); }
+    // integer PCM in and out (aw_pcm_rateconv_*): device buffers of any byte alignment; clippedDevice: nullptr, or a device uint64 the
+    // call adds its clipped-sample count to
+    int64_t processPcm(const void *inDevice, aw_sample_format inFormat, int64_t inFrames, void *outDevice, aw_sample_format outFormat,
+                       int64_t outCapacityFrames, uint64_t *clippedDevice = nullptr) {
+        int64_t n = 0;
+        check(aw_pcm_rateconv_process(h_, inDevice, inFormat, inFrames, outDevice, outFormat, outCapacityFrames, &n, clippedDevice));
+        return n;
+    }
+    int64_t flushPcm(void *outDevice, aw_sample_format outFormat, int64_t outCapacityFrames, uint64_t *clippedDevice = nullptr) {
+        int64_t n = 0;
+        check(aw_pcm_rateconv_flush(h_, outDevice, outFormat, outCapacityFrames, &n, clippedDevice));
+        return n;
+    }
+    void setDither(aw_dither mode, uint64_t seed = 0, uint64_t firstStream = 0) { check(aw_pcm_rateconv_set_dither(h_, mode, seed, firstStream)); }
+    void setGainNone() { check(aw_pcm_rateconv_set_gain(h_, AW_GAIN_NONE, nullptr, 0)); }
+    void setGainFixed(const std::vector<float> &gains) { check(aw_pcm_rateconv_set_gain(h_, AW_GAIN_FIXED, gains.data(), (int32_t)gains.size())); }
+    void setMetering(bool on) { check(aw_pcm_rateconv_set_metering(h_, on ? 1 : 0)); }
+    std::vector<aw_rateconv_levels> levels(int32_t firstStream, int32_t n) {
+        std::vector<aw_rateconv_levels> out((size_t)(n > 0 ? n : 0));
+        check(aw_pcm_rateconv_get_levels(h_, firstStream, n, out.data()));
+        return out;
+    }
+    void resetLevels() { check(aw_pcm_rateconv_reset_levels(h_)); }
   private:
     aw_rateconv *h_ = nullptr;
 };
