@@ -161,6 +161,11 @@ SIGNATURES = {
     "aw_pcm_rateconv_set_metering": (_I32, [_V, _I32]),
     "aw_pcm_rateconv_get_levels": (_I32, [_V, _I32, _I32, _V]),
     "aw_pcm_rateconv_reset_levels": (_I32, [_V]),
+    "aw_tp_rateconv_set": (_I32, [_V, _I32]),
+    "aw_tp_rateconv_get": (_I32, [_V, _I32, _I32, _V]),
+    "aw_tp_rateconv_reset_records": (_I32, [_V]),
+    "aw_tp_rateconv_measure": (_I32, [_V, _V, _I32, _I64, ctypes.POINTER(ctypes.c_int64)]),
+    "aw_tp_rateconv_measure_flush": (_I32, [_V, ctypes.POINTER(ctypes.c_int64)]),
 }
 
 

@@ -60,7 +60,7 @@ class MixedRateBatch:
     def __init__(self, tracks, hrir_rate: float, layout: InputLayout, stream_rates: Sequence[float],
                  hrirMap: Optional[HRIRChannelMap] = None, ctx: Optional[Context] = None, literal_vgenp: bool = False,
                  equalizer=None, fold_equalizer: Optional[bool] = None, eq_tail_tolerance: float = 1e-7, eq_max_taps: int = 65536,
-                 stream_equalizers=None, output_rate: Optional[float] = None):
+                 stream_equalizers=None, output_rate: Optional[float] = None, output_true_peak_ceiling: Optional[float] = None):
         """equalizer: an EqualizerDefinition applied after the spatializer, as AudioEffectGraph orders the two effects
         (AudioEffectGraph.swift:195-211).  fold_equalizer: True = folded into the HRIR (aw_eq_fold_hrir; raises EqualizerNotFoldable
         if its response is too long), False = the cascade kernel after the spatializer, None = whichever is cheaper (see _fold_pays),
@@ -70,7 +70,12 @@ class MixedRateBatch:
         (Spatializer.set_equalizer), the bucket's distinct definitions being the presets.  Never folded: the HRIR is shared.
         output_rate: every stream leaves at this rate: a bucket at another rate gets a two-channel RateConverter (aw_rateconv, a
         Kaiser-windowed sinc on the audio — not the HRIR's linear interpolation) behind its spatializer and its trailing equalizer.  None:
-        every stream leaves at the rate it came in with."""
+        every stream leaves at the rate it came in with.
+        output_true_peak_ceiling (linear full scale; needs output_rate): process() holds the true peak of every CONVERTED stream, measured
+        behind the converter, at or below it — a measuring pass over the bucket's device staging (RateConverter.measure_device), the
+        per-stream gains min(1, ceiling / true peak), then the converting pass.  Buckets already at output_rate have no converter and are
+        left as they are (a ceiling on them is the spatializer's own: Spatializer.set_gain('true_peak_ceiling')).  process_device is
+        untouched."""
         from .rateconv import RateConverter
         from .eq import EqualizerNotFoldable, ParametricEqualizerState, fold_equalizer as fold
         if equalizer is not None and stream_equalizers is not None:
@@ -79,6 +84,9 @@ class MixedRateBatch:
             raise ValueError(f"stream_equalizers needs one entry per stream ({len(stream_rates)}), got {len(stream_equalizers)}")
         self.ctx = ctx or default_context()
         self.output_rate = None if output_rate is None else float(output_rate)
+        if output_true_peak_ceiling is not None and (self.output_rate is None or not (float(output_true_peak_ceiling) > 0.0)):
+            raise ValueError("output_true_peak_ceiling needs an output_rate and must be positive")
+        self.output_true_peak_ceiling = None if output_true_peak_ceiling is None else float(output_true_peak_ceiling)
         tracks = np.ascontiguousarray(tracks, dtype=np.float32)
         # the reference's chooser: 7-track files take the 7-channel map, everything else the 14-channel one
         # (HRIRManager.swift:355-360; aw_preset_activate does the same) — an 8..13-track HRIR then fails the bounds check
@@ -169,11 +177,32 @@ class MixedRateBatch:
             y = b.spatializer.process(x)
             if b.equalizer is not None:
                 y = b.equalizer.process_batch(y)
-            if b.converter is not None:
+            if b.converter is not None and self.output_true_peak_ceiling is not None and y.shape[1] > 0:
+                y = self._convert_under_ceiling(rate, b, np.ascontiguousarray(y, dtype=np.float32))
+            elif b.converter is not None:
                 y = np.concatenate([b.converter.process(y), b.converter.flush()], axis=1)
             for k, i in enumerate(b.stream_ids):
                 out[i] = y[k]
         return out  # type: ignore[return-value]
+
+    def _convert_under_ceiling(self, rate: float, b: RateBucket, y: np.ndarray) -> np.ndarray:
+        """process(): y [bucket streams][frames][2] through the bucket's converter in two passes from the device staging — measure and
+        measure_flush, the ceiling's gains, then process and flush to float32."""
+        c, frames = b.converter, y.shape[1]
+        self.reserve_output_staging({rate: frames})
+        self.ctx.h2d(b.stage, y)
+        c.reset_true_peak()
+        c.set_true_peak(True)
+        try:
+            c.measure_device(b.stage, "f32", frames)
+            c.measure_flush_device()
+            c.set_gain("fixed", c.ceiling_gains(self.output_true_peak_ceiling))
+            c.set_true_peak(False)
+            head = c._pcm_to_host(lambda d, cap, clip: c.process_pcm_device(b.stage, "f32", frames, d, "f32", cap, clip), c.output_frames(frames), 0)[0]
+            return np.concatenate([head, c.flush_pcm("f32")[0]], axis=1)
+        finally:
+            c.set_true_peak(False)
+            c.set_gain("none")
 
     def reset(self) -> None:
         for b in self.buckets.values():

@@ -33,12 +33,23 @@
 // peak = max |y| over finite samples of all channels (before the gain), nonfinite = NaN / +-inf y, frames = output frames written,
 // clipped = samples the integer encode clipped (after gain and dither): maxima and integer sums, so every field is exact and, like every
 // output byte, independent of call splitting, sharding, byte alignment and tiling.
+//
+// True peak of the converted output (aw_tp_rateconv_*): truepeak.hpp's rule, per channel, on the converter's own float32 output.  For
+// stream s, channel ch and the absolute output index n since the last reset or flush: y[n] as above, BEFORE gain, dither and encode;
+// v[n] = awtp::filter_input(y[n]) (y where finite, else 0) and v[n] = 0 for n < 0; frame n of channel ch contributes
+// awtp::frame_peak_bits over v[n], v[n-1], .., v[n-11] of that channel.  Per stream: true_peak = the max of the contributions over
+// channels and frames, sample_peak = max |v| over the same frames, frames = output frames measured: maxima of bit patterns and an
+// integer sum, so every field is exact and independent of call splitting, sharding, alignment, formats and tiling.  A stream carries
+// its last 11 cleaned output frames [11][channels]; flush and reset zero them, a call that produces nothing leaves them, a call of fewer
+// than 11 outputs carries a mix of old and new ones.  The six-frame look-ahead of the centred filter is not flushed (the spatializer's
+// rule).  The ceiling is host arithmetic over a measuring pass: g = tp > c ? c / tp : 1 in float32 (ceiling_gain below), then a fixed gain.
 #pragma once
 #include <cmath>
 #include <cstdint>
 #include <vector>
 
 #include "pcm.hpp"
+#include "truepeak.hpp"
 
 namespace awrc {
 
@@ -142,5 +153,36 @@ inline long long sequential(const Plan &p, const float *c, const float *x, long 
     n.produced = end;
     return made;
 }
+
+// One stream's true-peak record (aw_rateconv_true_peak is its layout).
+struct TruePeakRecord {
+    uint32_t true_peak_bits;             // the bits of the largest frame contribution over channels and frames
+    uint32_t sample_peak_bits;           // ... of max |v| over the same frames
+    unsigned long long frames;           // output frames measured
+};
+
+// The true-peak rule, frame by frame: y [frames][channels] are a stream's next outputs, hist [11][channels] its last 11 cleaned output
+// frames (oldest first), which are carried on.  c: awtp::filter.
+inline void true_peak_sequential(const float *c, const float *y, long long frames, int channels, float *hist, TruePeakRecord &rec) {
+    const int H = awtp::kHistory;
+    for (int ch = 0; ch < channels; ++ch) {
+        float w[awtp::kTaps];            // w[k] = v[n - k]
+        w[0] = 0.0f;
+        for (int k = 1; k <= H; ++k) w[k] = hist[(H - k) * channels + ch];
+        for (long long n = 0; n < frames; ++n) {
+            if (n > 0) for (int k = H; k > 0; --k) w[k] = w[k - 1];
+            unsigned nonfinite = 0;
+            w[0] = awtp::filter_input(y[n * channels + ch], nonfinite);
+            const uint32_t a = awtp::float_bits(w[0]) & 0x7FFFFFFFu, m = awtp::frame_peak_bits(c, w, 1);
+            if (a > rec.sample_peak_bits) rec.sample_peak_bits = a;
+            if (m > rec.true_peak_bits) rec.true_peak_bits = m;
+        }
+        if (frames > 0) for (int k = 1; k <= H; ++k) hist[(H - k) * channels + ch] = w[k - 1];
+    }
+    rec.frames += (unsigned long long)(frames > 0 ? frames : 0);
+}
+
+// The gain that holds ceiling c over a stream whose measured true peak is tp.
+inline float ceiling_gain(float tp, float c) { return tp > c ? c / tp : 1.0f; }
 
 }  // namespace awrc

@@ -24,6 +24,15 @@
 // three bytes it may have in the next word are read singly (with the byte behind them where the buffer holds it).  On the way out a thread encodes whole elements once, in place in the gathered
 // image (so every count is taken once), and behind a barrier the tile's bytes leave as aligned 4-byte words put together from those codes,
 // with single bytes at the tile's ragged ends: no word shared with a neighbouring tile or stream is read or rewritten.
+//
+// The measuring forms (rateconv_tile_pcm_tp, rateconv_tile_tp_measure; rule: rateconv.hpp, "true peak of the converted output") are the PCM
+// form with the true-peak rule of truepeak.hpp applied to the gathered image between the tap loop and the encode, which overwrites that
+// image.  A frame needs its 11 predecessors: the gathered image is [11 + valid][channels], and its first 11 frames are the stream's
+// carried history for the first tile of a call and outputs o0 - 11 .. o0 - 1, computed again, for every later one (tiles run in parallel;
+// where a tile is shorter than 11 and o0 - 11 < 0, the history supplies the frames before the call: no input before history ++ call is
+// needed).  A measuring tile is therefore 11 outputs shorter,
+// rc_tp_tile, inside the same LDS layout.  The tile that holds the stream's last output writes the last 11 cleaned frames of its image
+// into the other history slot.  TP is a template argument beside PCM, so neither earlier form carries a branch of it.
 #pragma once
 #include <cstdint>
 
@@ -67,6 +76,19 @@ struct RateconvParams {
     unsigned long long *clipped;     // NULL, or the word every tile adds its clipped count to
 };
 
+using RateconvTruePeak = awrc::TruePeakRecord;                    // one stream's true-peak record (aw_rateconv_true_peak)
+
+// What the measuring forms take beside RateconvParams.
+struct RateconvTp {
+    const float *hist_in;            // [n_streams][11][channels] cleaned output frames before this call (oldest first)
+    float *hist_out;                 // ... before the next call (another buffer); written only by a call that produces frames
+    RateconvTruePeak *records;       // [n_streams]
+    int tile;                        // rc_tp_tile(L, M, taps, channels)
+    float c[awtp::kCoefficients];    // awtp::filter
+};
+
+constexpr int kRcTpOff = 0, kRcTpOn = 1, kRcTpOnly = 2;           // TP of rateconv_tile_form: not measured; measured and written; measured only
+
 AWP_HD int rc_block(int channels) { return channels % 4 == 0 ? 4 : channels % 2 == 0 ? 2 : 1; }
 AWP_HD int rc_row_stride(int taps) { return (taps + 3) & ~3; }
 // LDS position of channel 0 of frame f of the input image: segment f / 32 starts with its halo of kRcHalo frames
@@ -86,6 +108,10 @@ inline int rc_tile(int L, int M, int taps, int channels) {
     }
     return lo;
 }
+
+// The tile length of the measuring forms: 11 gathered frames and their span go to the predecessors.  A function of (L, M, T, channels)
+// only; 0 or less: this handle has no measuring tile.
+inline int rc_tp_tile(int L, int M, int taps, int channels) { return rc_tile(L, M, taps, channels) - awtp::kHistory; }
 
 template <int CB, class Ctx> AWP_HD void rc_read(const Ctx &ctx, const float *l, float (&x)[CB]) {
     if constexpr (CB == 4) ctx.ld_lds16(l, x);
@@ -281,19 +307,56 @@ template <class Ctx> AWP_HD void rc_leave_pcm(const Ctx &ctx, const RateconvPara
     if (t >= 64 && t - 64 < n - tail) out[tail + t - 64] = (unsigned char)rc_out_byte(gathered, tail + t - 64, bo);
 }
 
+// The measuring forms' pass over the gathered image [11 + valid][C], whose first 11 frames are the predecessors: the contribution of
+// every frame and channel of the tile to the stream's record, and (last: the tile holds the stream's last output) the next history.
+// Reads the image only.
+template <class Ctx> AWP_HD void rc_measure(const Ctx &ctx, const RateconvParams &p, const RateconvTp &tp, const float *gathered, long long s, int valid, bool last) {
+    const int t = ctx.tid(), C = p.channels, H = awtp::kHistory;
+    uint32_t true_peak = 0u, sample_peak = 0u;
+#pragma unroll 1
+    for (int k = t; k < valid * C; k += kRcThreads) {              // element k of the tile: frame k / C, channel k % C
+        const float *top = gathered + H * C + k;
+        float w[awtp::kTaps];                                      // w[j] = v[n - j]
+        unsigned nonfinite = 0u;
+#pragma unroll
+        for (int j = 0; j < awtp::kTaps; ++j) w[j] = awtp::filter_input(top[-j * C], nonfinite);
+        const uint32_t a = awtp::float_bits(w[0]) & 0x7FFFFFFFu, m = awtp::frame_peak_bits(tp.c, w, 1);
+        sample_peak = a > sample_peak ? a : sample_peak;
+        true_peak = m > true_peak ? m : true_peak;
+    }
+    const uint32_t wt = ctx.wave_max(true_peak), ws = ctx.wave_max(sample_peak);       // (uniform: every wave is whole here)
+    if ((t & 63) == 0) {
+        if (wt) ctx.atomic_max(&tp.records[s].true_peak_bits, wt);
+        if (ws) ctx.atomic_max(&tp.records[s].sample_peak_bits, ws);
+    }
+    if (t == 0) ctx.atomic_add(&tp.records[s].frames, (unsigned long long)valid);
+    if (last) {
+        unsigned nonfinite = 0u;
+        for (int k = t; k < H * C; k += kRcThreads) tp.hist_out[s * H * C + k] = awtp::filter_input(gathered[valid * C + k], nonfinite);
+    }
+}
+
 // `tile` counts the tiles of this call; a call without outputs runs tile 0 for the history alone.  PCM: p.in and p.out are byte buffers of
 // p.in_format and p.out_format, and the gain, the dither and the records of p apply; else the float32 form, which reads none of those.
-template <bool PCM, class Ctx> AWP_HD void rateconv_tile_form(const Ctx &ctx, const RateconvParams &p, long long s, long long tile) {
+// TP (kRcTpOn, kRcTpOnly; PCM only): tiles of tp->tile outputs, measured into tp->records; kRcTpOnly writes no output, no levels record and
+// no clip count.
+template <bool PCM, int TP, class Ctx>
+AWP_HD void rateconv_tile_form(const Ctx &ctx, const RateconvParams &p, const RateconvTp *tp, long long s, long long tile) {
+    static_assert(TP == kRcTpOff || PCM, "the measuring forms are forms of the PCM form");
     float *image = ctx.lds();
     const int t = ctx.tid();
     const int C = p.channels, T = p.taps, D = p.latency, CB = rc_block(C);
-    const long long o0 = tile * p.tile;                                                    // the tile's first output within the call
-    const int valid = (int)(p.out_frames - o0 < p.tile ? p.out_frames - o0 : p.tile);      // outputs of this tile (0: none at all)
+    int step = p.tile;
+    if constexpr (TP != kRcTpOff) step = tp->tile;
+    const long long o0 = tile * step;                                                      // the tile's first output within the call
+    const int valid = (int)(p.out_frames - o0 < step ? p.out_frames - o0 : step);          // outputs of this tile (0: none at all)
     if (valid > 0) {
-        const long long n0 = p.produced + o0;                                              // absolute output index
+        // the measuring forms compute the outputs before a later tile again, up to 11 and as many as the call has: `lead` of them, `made` in all
+        const int lead = TP != kRcTpOff ? (int)(o0 < awtp::kHistory ? o0 : awtp::kHistory) : 0, made = valid + lead;
+        const long long n0 = p.produced + o0 - lead;                                       // absolute output index
         const int p0 = awrc::phase(n0, p.L, p.M);
         const long long lo = awrc::input_index(n0, p.L, p.M) + D - (T - 1);                // absolute input frames lo .. hi
-        const long long hi = awrc::input_index(n0 + valid - 1, p.L, p.M) + D;
+        const long long hi = awrc::input_index(n0 + made - 1, p.L, p.M) + D;
         const int span = (int)(hi - lo + 1);                                               // <= rc_span(p.tile, ..)
         const long long rel = lo - p.consumed;                                             // frame of the call; >= -(T - 1)
         const int n_hist = rel < 0 ? (int)(-rel < span ? -rel : span) : 0;                 // frames the history supplies
@@ -333,30 +396,41 @@ template <bool PCM, class Ctx> AWP_HD void rateconv_tile_form(const Ctx &ctx, co
         }
         ctx.barrier();
         // work items: (phase class r, member g of the class, channel block b), b fastest, then g
-        float *gathered = image + rc_image_floats(rc_span(p.tile, p.L, p.M, T), C);        // [valid][C]
-        const int NB = C / CB, G = (valid + p.L - 1) / p.L, classes = valid < p.L ? valid : p.L;
+        float *gathered = image + rc_image_floats(rc_span(p.tile, p.L, p.M, T), C);        // [made][C]; measuring: [11 + valid][C]
+        float *computed = gathered;                                                        // where output n0 goes
+        if constexpr (TP != kRcTpOff) {                            // the predecessors from before the call: history frames o0 .. 10
+            for (int k = t; k < (awtp::kHistory - lead) * C; k += kRcThreads) gathered[k] = tp->hist_in[(s * awtp::kHistory + o0) * C + k];
+            computed += (awtp::kHistory - lead) * C;
+        }
+        const int NB = C / CB, G = (made + p.L - 1) / p.L, classes = made < p.L ? made : p.L;
         for (int item = t; item < classes * G * NB; item += kRcThreads) {
             const int b = item % NB, g = (item / NB) % G, r = item / (NB * G);
             const int o = r + p.L * g;
-            if (o >= valid) continue;
+            if (o >= made) continue;
             // (n0 + o) M = i(n0) L + p(n0) + o M: inside the tile the position is 32-bit arithmetic, p(n0) + o M < 640 + 4096 * 640
             const unsigned v = (unsigned)p0 + (unsigned)o * (unsigned)p.M;
             const int f0 = (int)(v / (unsigned)p.L) + (T - 1);                             // i(n0 + o) + D - lo
             const float *row = p.c + (long long)(v % (unsigned)p.L) * p.row_stride;
-            float *y = gathered + o * C + b * CB;
+            float *y = computed + o * C + b * CB;
             if (CB == 4) rc_output<4>(ctx, image + b * 4, row, f0, C, T, y);
             else if (CB == 2) rc_output<2>(ctx, image + b * 2, row, f0, C, T, y);
             else rc_output<1>(ctx, image + b, row, f0, C, T, y);
         }
         ctx.barrier();
-        if constexpr (PCM) {
+        if constexpr (TP != kRcTpOff) {
+            rc_measure(ctx, p, *tp, gathered, s, valid, o0 + valid == p.out_frames);
+            if constexpr (TP == kRcTpOn) {
+                ctx.barrier();                                     // (the encode below overwrites what the measurement reads)
+                rc_leave_pcm(ctx, p, gathered + awtp::kHistory * C, s, o0, valid);
+            }
+        } else if constexpr (PCM) {
             rc_leave_pcm(ctx, p, gathered, s, o0, valid);
         } else {
             float *out = p.out + (s * p.out_frames + o0) * C;
             for (int k = t; k < valid * C; k += kRcThreads) out[k] = gathered[k];
         }
     }
-    const long long tiles = (p.out_frames + p.tile - 1) / p.tile;
+    const long long tiles = (p.out_frames + step - 1) / step;
     if (tile == (tiles > 0 ? tiles - 1 : 0)) {                     // the stream's last tile: the last T - 1 frames of (history ++ call)
         for (int k = t; k < (T - 1) * C; k += kRcThreads) {
             const long long f = p.in_frames - (T - 1) + k / C;     // frame of the call
@@ -371,10 +445,18 @@ template <bool PCM, class Ctx> AWP_HD void rateconv_tile_form(const Ctx &ctx, co
 }
 
 template <class Ctx> AWP_HD void rateconv_tile(const Ctx &ctx, const RateconvParams &p, long long s, long long tile) {
-    rateconv_tile_form<false>(ctx, p, s, tile);
+    rateconv_tile_form<false, kRcTpOff>(ctx, p, nullptr, s, tile);
 }
 template <class Ctx> AWP_HD void rateconv_tile_pcm(const Ctx &ctx, const RateconvParams &p, long long s, long long tile) {
-    rateconv_tile_form<true>(ctx, p, s, tile);
+    rateconv_tile_form<true, kRcTpOff>(ctx, p, nullptr, s, tile);
+}
+// The PCM form, measured: also adds to tp.records and carries tp.hist_in to tp.hist_out.
+template <class Ctx> AWP_HD void rateconv_tile_pcm_tp(const Ctx &ctx, const RateconvParams &p, const RateconvTp &tp, long long s, long long tile) {
+    rateconv_tile_form<true, kRcTpOn>(ctx, p, &tp, s, tile);
+}
+// The measurement alone: the input history, the counts, tp.records and tp.hist_out move; p.out, p.gains, p.levels and p.clipped are not used.
+template <class Ctx> AWP_HD void rateconv_tile_tp_measure(const Ctx &ctx, const RateconvParams &p, const RateconvTp &tp, long long s, long long tile) {
+    rateconv_tile_form<true, kRcTpOnly>(ctx, p, &tp, s, tile);
 }
 
 }  // namespace awk

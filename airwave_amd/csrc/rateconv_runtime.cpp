@@ -1,7 +1,8 @@
 // rateconv_runtime.cpp — C ABI of the batch sample-rate converter (aw_rateconv_*, include/airwave_hip.h): the rules are
 // device/rateconv.hpp, the kernel device/rateconv_tile.hpp.  Audio-rate conversion has no counterpart in the reference, whose two-point
 // linear interpolation (Resampler.swift:31-68, aw_resample) is for an HRIR at activation and images and aliases at about -30 dB on audio.
-// The aw_pcm_rateconv_* entries run the same handle through the kernel's PCM form (integer PCM in and out, dither, gain, records).
+// The aw_pcm_rateconv_* entries run the same handle through the kernel's PCM form (integer PCM in and out, dither, gain, records), and
+// the aw_tp_rateconv_* entries add the true peak of the converted output: the PCM form's measuring forms.
 // One owner thread per handle, like every other handle of this library; the handle goes as aw_eq does: device current, stream idle, then
 // its members.
 #include <cmath>
@@ -45,9 +46,18 @@ struct aw_rateconv {
     int metering = 0;
     awr::Buf<float> d_gains;                   // [streams], made by set_gain(AW_GAIN_FIXED)
     awr::Buf<awk::RateconvLevels> d_levels;    // [streams], made by set_metering(on); aw_rateconv_levels is its layout
+    // the aw_tp_rateconv_* entries' state, one allocation made by aw_tp_rateconv_set(on): the records [streams] (aw_rateconv_true_peak is
+    // their layout), then two history slots [streams][11][channels]; a call that produces frames reads slot tp_cur and writes the other
+    int true_peak = 0, tp_tile = 0, tp_cur = 0;
+    awr::Buf<float> d_tp;
+    float tp_c[awtp::kCoefficients];
+    awk::RateconvTruePeak *tp_records() const { return reinterpret_cast<awk::RateconvTruePeak *>(d_tp.get()); }
+    size_t tp_hist_floats() const { return (size_t)n_streams * awtp::kHistory * n_channels; }
+    float *tp_hist(int slot) const { return d_tp.get() + (size_t)n_streams * (sizeof(awk::RateconvTruePeak) / sizeof(float)) + (size_t)slot * tp_hist_floats(); }
 };
 
 static_assert(sizeof(aw_rateconv_levels) == 32 && sizeof(awk::RateconvLevels) == 32, "aw_rateconv_levels is the kernel's record");
+static_assert(sizeof(aw_rateconv_true_peak) == 16 && sizeof(awk::RateconvTruePeak) == 16, "aw_rateconv_true_peak is the kernel's record");
 static_assert(AW_SAMPLE_F32 == awp::kF32 && AW_SAMPLE_S16 == awp::kS16 && AW_SAMPLE_S24 == awp::kS24 && AW_SAMPLE_S32 == awp::kS32, "formats");
 static_assert(AW_DITHER_NONE == awp::kDitherNone && AW_DITHER_TPDF == awp::kDitherTpdf && AW_DITHER_TPDF_HP == awp::kDitherTpdfHp, "dither modes");
 
@@ -56,6 +66,7 @@ namespace {
 aw_status reset_state(aw_rateconv *rc) {
     AW_HIP_TRY(hipMemsetAsync(rc->d_hist[rc->cur].get(), 0, rc->d_hist[rc->cur].bytes(), rc->ctx->stream));
     AW_HIP_TRY(hipMemsetAsync(rc->d_counts.get(), 0, rc->d_counts.bytes(), rc->ctx->stream));
+    if (rc->d_tp) AW_HIP_TRY(hipMemsetAsync(rc->tp_hist(rc->tp_cur), 0, rc->tp_hist_floats() * sizeof(float), rc->ctx->stream));      // v = 0 before the next frame
     rc->counts = awrc::Counts{};
     return AW_OK;
 }
@@ -64,16 +75,18 @@ aw_status reset_state(aw_rateconv *rc) {
 struct PcmCall {
     aw_sample_format in_format, out_format;
     uint64_t *clipped;
+    bool measure_only;                         // aw_tp_rateconv_measure / _measure_flush: no output buffer, no capacity
 };
 
 // in NULL: in_frames frames of zeros; pcm NULL: the float32 form
 aw_status run(aw_rateconv *rc, const void *in, long long in_frames, void *out, long long capacity, int64_t *out_frames, const PcmCall *pcm = nullptr) {
     const awrc::Plan &pl = rc->plan;
     const long long n_out = awrc::outputs_after(rc->counts.consumed + in_frames, pl.L, pl.M, pl.latency) - rc->counts.produced;
-    if (capacity < n_out)
+    const bool measure_only = pcm && pcm->measure_only;
+    if (!measure_only && capacity < n_out)
         return fail(AW_ERR_INVALID_ARGUMENT, "out_capacity_frames " + std::to_string(capacity) + " is below the " + std::to_string(n_out) +
                                                  " frames this call produces (aw_rateconv_output_frames)");
-    if (n_out > 0 && !out) return fail(AW_ERR_INVALID_ARGUMENT, "out_device is NULL");
+    if (!measure_only && n_out > 0 && !out) return fail(AW_ERR_INVALID_ARGUMENT, "out_device is NULL");
     if (out_frames) *out_frames = n_out;
     if (in_frames == 0) return AW_OK;
     AW_HIP_TRY(hipSetDevice(rc->ctx->device));
@@ -90,7 +103,16 @@ aw_status run(aw_rateconv *rc, const void *in, long long in_frames, void *out, l
         p.gains = rc->gain_mode == AW_GAIN_FIXED ? rc->d_gains.get() : nullptr;
         p.levels = rc->metering ? rc->d_levels.get() : nullptr;
         p.clipped = reinterpret_cast<unsigned long long *>(pcm->clipped);
-        AW_HIP_TRY(awk::launch_rateconv_pcm(p, rc->ctx->stream));
+        if (rc->true_peak) {
+            awk::RateconvTp tp{};
+            tp.hist_in = rc->tp_hist(rc->tp_cur); tp.hist_out = rc->tp_hist(rc->tp_cur ^ 1);
+            tp.records = rc->tp_records(); tp.tile = rc->tp_tile;
+            for (int i = 0; i < awtp::kCoefficients; ++i) tp.c[i] = rc->tp_c[i];
+            AW_HIP_TRY(measure_only ? awk::launch_rateconv_tp_measure(p, tp, rc->ctx->stream) : awk::launch_rateconv_pcm_tp(p, tp, rc->ctx->stream));
+            if (n_out > 0) rc->tp_cur ^= 1;                     // (a call without frames leaves the carried v history where it is)
+        } else {
+            AW_HIP_TRY(awk::launch_rateconv_pcm(p, rc->ctx->stream));
+        }
     } else {
         AW_HIP_TRY(awk::launch_rateconv(p, rc->ctx->stream));
     }
@@ -140,6 +162,7 @@ aw_status aw_rateconv_create(aw_context *ctx, double in_rate, double out_rate, i
     if (!rc) return fail(AW_ERR_OUT_OF_MEMORY, "allocation failed");
     rc->ctx = ctx; rc->n_streams = n_streams; rc->n_channels = n_channels; rc->plan = pl;
     rc->tile = awk::rc_tile(pl.L, pl.M, pl.taps, n_channels);
+    rc->tp_tile = awk::rc_tp_tile(pl.L, pl.M, pl.taps, n_channels);
     if (rc->tile < 1) return fail(AW_ERR_INVALID_ARGUMENT, "no tile of this converter fits the kernel's LDS");
     // the table, rows padded to 16-byte words (the pad is never read as a tap)
     const int stride = awk::rc_row_stride(pl.taps);
@@ -179,6 +202,8 @@ int64_t aw_rateconv_info(const aw_rateconv *rc, int32_t what) {
         case 7: return rc->dither;
         case 8: return rc->gain_mode;
         case 9: return rc->metering;
+        case 10: return rc->true_peak;
+        case 11: return rc->tp_tile > 0 ? rc->tp_tile : 0;
         default: return -1;
     }
 }
@@ -218,7 +243,7 @@ aw_status aw_pcm_rateconv_process(aw_rateconv *rc, const void *in_device, aw_sam
     if (!awp::format_bytes(in_format) || !awp::format_bytes(out_format)) return fail(AW_ERR_INVALID_ARGUMENT, "unknown sample format");
     if (in_frames < 0) return fail(AW_ERR_INVALID_ARGUMENT, "in_frames must be >= 0");
     if (in_frames > 0 && !in_device) return fail(AW_ERR_INVALID_ARGUMENT, "in_device is NULL");
-    const PcmCall call{in_format, out_format, clipped_device};
+    const PcmCall call{in_format, out_format, clipped_device, false};
     return run(rc, in_device, in_frames, out_device, out_capacity_frames, out_frames, &call);
 } AW_NOEXCEPT_TAIL
 
@@ -226,7 +251,7 @@ aw_status aw_pcm_rateconv_flush(aw_rateconv *rc, void *out_device, aw_sample_for
                                 uint64_t *clipped_device) try {
     if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
     if (!awp::format_bytes(out_format)) return fail(AW_ERR_INVALID_ARGUMENT, "unknown sample format");
-    const PcmCall call{AW_SAMPLE_F32, out_format, clipped_device};
+    const PcmCall call{AW_SAMPLE_F32, out_format, clipped_device, false};
     const aw_status st = run(rc, nullptr, rc->plan.latency, out_device, out_capacity_frames, out_frames, &call);
     if (st != AW_OK) return st;
     return reset_state(rc);
@@ -290,6 +315,67 @@ aw_status aw_pcm_rateconv_reset_levels(aw_rateconv *rc) try {
     AW_HIP_TRY(hipSetDevice(rc->ctx->device));
     AW_HIP_TRY(hipMemsetAsync(rc->d_levels.get(), 0, rc->d_levels.bytes(), rc->ctx->stream));
     return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_tp_rateconv_set(aw_rateconv *rc, int32_t on) try {
+    if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
+    if (!on) { rc->true_peak = 0; return AW_OK; }
+    if (rc->tp_tile < 1)
+        return fail(AW_ERR_INVALID_ARGUMENT, "the measuring form needs 11 output frames beside a tile, and this converter's tile of " +
+                                                 std::to_string(rc->tile) + " leaves none");
+    if (rc->true_peak) return AW_OK;
+    AW_HIP_TRY(hipSetDevice(rc->ctx->device));
+    if (!rc->d_tp) {
+        awr::Buf<float> fresh;
+        const size_t floats = (size_t)rc->n_streams * (sizeof(awk::RateconvTruePeak) / sizeof(float)) + 2 * rc->tp_hist_floats();
+        AW_HIP_TRY(fresh.alloc(floats, &rc->ctx->device_allocs));
+        AW_HIP_TRY(hipMemsetAsync(fresh.get(), 0, fresh.bytes(), rc->ctx->stream));
+        rc->d_tp = std::move(fresh);
+        awtp::filter(rc->tp_c);
+    } else {                                   // switched on again: what the meter did not see counts as v = 0
+        AW_HIP_TRY(hipMemsetAsync(rc->tp_hist(rc->tp_cur), 0, rc->tp_hist_floats() * sizeof(float), rc->ctx->stream));
+    }
+    rc->true_peak = 1;
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_tp_rateconv_get(aw_rateconv *rc, int32_t first_stream, int32_t n, aw_rateconv_true_peak *out_host) try {
+    if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
+    if (!out_host) return fail(AW_ERR_INVALID_ARGUMENT, "out_host is NULL");
+    if (first_stream < 0 || n < 0 || (long long)first_stream + n > rc->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "stream range outside the handle");
+    if (!rc->d_tp) return fail(AW_ERR_INVALID_ARGUMENT, "aw_tp_rateconv_set was never switched on on this handle");
+    AW_HIP_TRY(hipSetDevice(rc->ctx->device));
+    if (n > 0)
+        AW_HIP_TRY(hipMemcpyAsync(out_host, rc->tp_records() + first_stream, (size_t)n * sizeof(aw_rateconv_true_peak), hipMemcpyDeviceToHost, rc->ctx->stream));
+    AW_HIP_TRY(hipStreamSynchronize(rc->ctx->stream));
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_tp_rateconv_reset_records(aw_rateconv *rc) try {
+    if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
+    if (!rc->d_tp) return AW_OK;
+    AW_HIP_TRY(hipSetDevice(rc->ctx->device));
+    AW_HIP_TRY(hipMemsetAsync(rc->tp_records(), 0, (size_t)rc->n_streams * sizeof(awk::RateconvTruePeak), rc->ctx->stream));
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_tp_rateconv_measure(aw_rateconv *rc, const void *in_device, aw_sample_format in_format, int64_t in_frames, int64_t *out_frames) try {
+    if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
+    if (!awp::format_bytes(in_format)) return fail(AW_ERR_INVALID_ARGUMENT, "unknown sample format");
+    if (in_frames < 0) return fail(AW_ERR_INVALID_ARGUMENT, "in_frames must be >= 0");
+    if (in_frames > 0 && !in_device) return fail(AW_ERR_INVALID_ARGUMENT, "in_device is NULL");
+    if (!rc->true_peak) return fail(AW_ERR_INVALID_ARGUMENT, "measuring is off: aw_tp_rateconv_set(rc, 1) first");
+    const PcmCall call{in_format, AW_SAMPLE_F32, nullptr, true};
+    return run(rc, in_device, in_frames, nullptr, 0, out_frames, &call);
+} AW_NOEXCEPT_TAIL
+
+aw_status aw_tp_rateconv_measure_flush(aw_rateconv *rc, int64_t *out_frames) try {
+    if (!rc) return fail(AW_ERR_INVALID_ARGUMENT, "rc is NULL");
+    if (!rc->true_peak) return fail(AW_ERR_INVALID_ARGUMENT, "measuring is off: aw_tp_rateconv_set(rc, 1) first");
+    const PcmCall call{AW_SAMPLE_F32, AW_SAMPLE_F32, nullptr, true};
+    const aw_status st = run(rc, nullptr, rc->plan.latency, nullptr, 0, out_frames, &call);
+    if (st != AW_OK) return st;
+    return reset_state(rc);
 } AW_NOEXCEPT_TAIL
 
 }  // extern "C"

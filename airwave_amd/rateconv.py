@@ -13,10 +13,12 @@ from . import _capi
 from .api import (DITHER_MODES, GAIN_MODES, SAMPLE_FORMATS, _FORMAT_DTYPE, Context, _check, _f32, _finalizing, _fp, _pcm_array,
                   default_context)
 
-_INFO = ("L", "M", "taps", "latency", "tile", "frames_consumed", "frames_produced", "dither", "gain_mode", "metering")
+_INFO = ("L", "M", "taps", "latency", "tile", "frames_consumed", "frames_produced", "dither", "gain_mode", "metering", "true_peak", "true_peak_tile")
 # aw_rateconv_levels, byte for byte (RateConverter.levels)
 RATECONV_LEVELS_DTYPE = np.dtype([("peak", np.float32), ("reserved", np.uint32), ("frames", np.uint64), ("clipped", np.uint64),
                                   ("nonfinite", np.uint64)], align=False)
+# aw_rateconv_true_peak, byte for byte (RateConverter.true_peak)
+RATECONV_TRUE_PEAK_DTYPE = np.dtype([("true_peak", np.float32), ("sample_peak", np.float32), ("frames", np.uint64)], align=False)
 
 
 def _format_code(fmt) -> int:
@@ -223,15 +225,76 @@ class RateConverter:
         fo = _format_code(out_format)
         return self._pcm_to_host(lambda d, cap, clip: self.flush_pcm_device(d, fo, cap, clip), self.flush_frames(), fo)
 
+    # ---- true peak of the converted output and the ceiling pass (aw_tp_rateconv_*) ----
+
+    def set_true_peak(self, on: bool = True) -> None:
+        """aw_tp_rateconv_set: measure the true peak of every later PCM call's own output (before gain, dither and encode); switching it
+        on makes the feature's one device allocation here.  The float32 family (process / flush) is not measured.  AirwaveError
+        (INVALID_ARGUMENT) for the few handles whose tile leaves no room for the measuring form (info()['true_peak_tile'] == 0)."""
+        _check(self._lib.aw_tp_rateconv_set(self._h, int(bool(on))))
+
+    def true_peak(self, first_stream: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """aw_tp_rateconv_get: the records of n streams from first_stream on (default: all) as a structured array of
+        RATECONV_TRUE_PEAK_DTYPE (true_peak, sample_peak, frames).  Synchronises the context's stream."""
+        first_stream = int(first_stream)
+        n = self.n_streams - first_stream if n is None else int(n)
+        out = np.zeros(max(n, 0), RATECONV_TRUE_PEAK_DTYPE)
+        _check(self._lib.aw_tp_rateconv_get(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
+        return out
+
+    def reset_true_peak(self) -> None:
+        _check(self._lib.aw_tp_rateconv_reset_records(self._h))
+
+    def measure_device(self, in_ptr: int, in_format, in_frames: int) -> int:
+        """aw_tp_rateconv_measure: process_pcm_device without an output — the counts and the history move, only the true-peak records
+        change.  Returns the frames the call would have written."""
+        n = ctypes.c_int64()
+        _check(self._lib.aw_tp_rateconv_measure(self._h, ctypes.c_void_p(in_ptr), _format_code(in_format), int(in_frames), ctypes.byref(n)))
+        return int(n.value)
+
+    def measure_flush_device(self) -> int:
+        """aw_tp_rateconv_measure_flush: flush_pcm_device without an output; ends with the reset, so a second pass starts clean."""
+        n = ctypes.c_int64()
+        _check(self._lib.aw_tp_rateconv_measure_flush(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def measure(self, x, in_format=None) -> int:
+        """Host arrays: measure_device over x [streams][frames][channels] (the conventions of process_pcm).  Returns the frames measured."""
+        if not isinstance(x, np.ndarray) or x.ndim < 3:
+            raise ValueError("x: [streams][frames][channels] array required")
+        frames = x.shape[1]
+        x, fi = _pcm_array(x, in_format, (self.n_streams, frames, self.n_channels), "x")
+        if frames == 0:
+            return 0
+        d_in = self.ctx.alloc(x.nbytes)
+        try:
+            self.ctx.h2d(d_in, x)
+            n = self.measure_device(d_in, fi, frames)
+            self.ctx.synchronize()
+        finally:
+            self.ctx.free(d_in)
+        return n
+
+    def ceiling_gains(self, ceiling: float) -> np.ndarray:
+        """The per-stream gains that hold `ceiling` (linear full scale) over what the records have measured: g = tp > c ? c / tp : 1 in
+        float32, for set_gain('fixed', g) before a second pass over the same input."""
+        c = np.float32(ceiling)
+        if not np.isfinite(c) or c <= 0:
+            raise ValueError(f"ceiling must be positive and finite, got {ceiling!r}")
+        t = self.true_peak()["true_peak"]
+        return np.where(t > c, c / np.maximum(t, np.float32(1e-38)), np.float32(1.0)).astype(np.float32)
+
 
 def convert(x, in_rate: float, out_rate: float, ctx: Optional[Context] = None, out_format=None, dither="none", seed: int = 0,
-            in_format=None) -> np.ndarray:
+            in_format=None, true_peak_ceiling: Optional[float] = None, gains=None) -> np.ndarray:
     """One shot: x [streams][N][channels] (or [N][channels]) -> [..][ceil(N L / M)][channels]: process + flush, concatenated.  With
     out_format ('f32', 's16', 's24', 's32') x may be int16, int32, float32 or packed s24 (uint8 [..., 3], in_format='s24') and the result
-    is in out_format, s16 / s24 dithered by `dither` ('none', 'tpdf', 'tpdf_hp') with `seed`."""
+    is in out_format, s16 / s24 dithered by `dither` ('none', 'tpdf', 'tpdf_hp') with `seed`.  `gains`: a fixed gain, one or one per
+    stream.  true_peak_ceiling (linear full scale; needs an out_format): a measuring pass (measure + measure_flush) first, then the
+    converting pass under the smaller of the ceiling's gain and the caller's, per stream."""
     if out_format is None:
-        if dither not in ("none", 0) or in_format is not None:
-            raise ValueError("dither and in_format need an out_format")
+        if dither not in ("none", 0) or in_format is not None or true_peak_ceiling is not None or gains is not None:
+            raise ValueError("dither, in_format, gains and true_peak_ceiling need an out_format")
         a = _f32(x)
         packed = 0
     else:
@@ -248,6 +311,16 @@ def convert(x, in_rate: float, out_rate: float, ctx: Optional[Context] = None, o
             y = np.concatenate([rc.process(a), rc.flush()], axis=1)
         else:
             rc.set_dither(dither, seed)
+            g = None if gains is None else np.broadcast_to(np.atleast_1d(np.asarray(gains, np.float32)), (rc.n_streams,))
+            if true_peak_ceiling is not None:
+                rc.set_true_peak(True)
+                rc.measure(a, in_format)
+                rc.measure_flush_device()
+                held = rc.ceiling_gains(true_peak_ceiling)
+                g = held if g is None else np.minimum(g, held)
+                rc.set_true_peak(False)
+            if g is not None:
+                rc.set_gain("fixed", g)
             y = np.concatenate([rc.process_pcm(a, out_format, in_format)[0], rc.flush_pcm(out_format)[0]], axis=1)
     finally:
         rc.close()

@@ -683,7 +683,8 @@ AW_API aw_status aw_rateconv_filter(double in_rate, double out_rate, float *c /*
 AW_API aw_status aw_rateconv_create(aw_context *ctx, double in_rate, double out_rate, int32_t n_streams, int32_t n_channels, aw_rateconv **out);
 AW_API void aw_rateconv_destroy(aw_rateconv *rc);
 /* what: 0 L, 1 M, 2 taps, 3 latency, 4 tile (output frames per workgroup), 5 frames consumed, 6 frames produced, 7 the aw_dither mode,
- * 8 the aw_gain_mode, 9 metering on (7 - 9: the settings of the aw_pcm_rateconv_* entries below); -1 otherwise */
+ * 8 the aw_gain_mode, 9 metering on (7 - 9: the settings of the aw_pcm_rateconv_* entries below), 10 true-peak measuring on, 11 output
+ * frames per workgroup of the measuring form, 0 where it has none (10 - 11: the aw_tp_rateconv_* entries below); -1 otherwise */
 AW_API int64_t aw_rateconv_info(const aw_rateconv *rc, int32_t what);
 AW_API int64_t aw_rateconv_output_frames(const aw_rateconv *rc, int64_t in_frames);  /* what the next process call of in_frames writes */
 AW_API aw_status aw_rateconv_process(aw_rateconv *rc, const float *in_device, int64_t in_frames, float *out_device,
@@ -720,6 +721,7 @@ AW_API aw_status aw_rateconv_reset(aw_rateconv *rc);
  *    only through aw_rateconv_process / _flush).
  *  - loudness, true peak and the limiter of a spatializer in front of the converter measure the signal BEFORE conversion; the converter's
  *    own peak is the SAMPLE peak after it.  A true-peak meter or limiter after the converter is not provided here.
+ *    (The meter and a ceiling pass are the aw_tp_rateconv_* entries: "True peak of the converted output" below.)
  * An unknown format, a NULL handle, a NULL input with in_frames > 0 or a capacity below the count returns AW_ERR_INVALID_ARGUMENT before
  * any HIP call, leaves the handle untouched and does not write *out_frames.  Process, flush and reset_levels only enqueue on the context's
  * stream; get_levels copies on that stream and then synchronises it. */
@@ -750,6 +752,51 @@ AW_API aw_status aw_pcm_rateconv_set_metering(aw_rateconv *rc, int32_t on);
 AW_API aw_status aw_pcm_rateconv_get_levels(aw_rateconv *rc, int32_t first_stream, int32_t n, aw_rateconv_levels *out_host);
 /* Zeroes every record (asynchronous on the context's stream); the settings stay. */
 AW_API aw_status aw_pcm_rateconv_reset_levels(aw_rateconv *rc);
+/* True peak of the converted output, and a ceiling pass.  Resampling moves inter-sample peaks, so a true peak measured in front of the
+ * converter does not hold behind it.  While measuring is on, the aw_pcm_rateconv_* entries apply the spatializer's true-peak rule
+ * ("per-stream true peak" above: aw_true_peak_filter, 49-tap Hann-windowed sinc, phases 1 .. 3, fixed fmaf chains, integer max) to their
+ * own output inside the converter's kernel, with no float32 staging.  For stream s, channel ch and the stream's absolute output index n
+ * since the last reset or flush:
+ *  - y[n] is the converter's float32 output BEFORE gain, dither and encode; v[n] = y[n] where it is finite, else 0; v[n] = 0 for n < 0.
+ *  - frame n of channel ch contributes max(|v[n]|, |t_1[n]|, |t_2[n]|, |t_3[n]|), t_p[n] the fmaf chain of aw_true_peak_filter's phase p
+ *    over v[n], v[n-1], .., v[n-11] of that channel, kept as the bit pattern of the absolute value.
+ *  - the record: true_peak = the maximum over channels and frames of the contributions, sample_peak = max |v| over the same frames,
+ *    frames = the output frames measured.  Maxima of bit patterns and an integer sum: every field is exact.
+ *  - flush and reset zero the carried v (the stream's last 11 cleaned output frames) and restart n; the records live until
+ *    aw_tp_rateconv_reset_records.  The six-frame look-ahead of the centred filter is not flushed, as in the spatializer.
+ *  - splitting calls in time, sharding streams over handles, buffer alignment, sample formats and the kernel's tiling change no bit of
+ *    any field.  Output bytes, aw_rateconv_levels and clip counts are exactly those with measuring off.
+ *  - aw_rateconv_process / _flush / _reset keep their behaviour and do not measure: a float32-family process call between measured calls
+ *    is NOT seen by the meter, which goes on as if those frames had not been produced.  _reset and both flushes zero the carried v.
+ * aw_tp_rateconv_measure / _measure_flush are aw_pcm_rateconv_process / _flush without an output buffer: the counts and the input history
+ * move exactly as there, *out_frames is the count the call would have written, and only the true-peak records change: no byte of
+ * output, no levels record and no clip count.  measure_flush ends with the reset, so a second pass over the same input starts clean.
+ * The ceiling is host arithmetic over the records of such a first pass:
+ *      g_s = true_peak_s > c ? c / true_peak_s : 1      (float32)
+ *      aw_pcm_rateconv_set_gain(rc, AW_GAIN_FIXED, g, n_streams), then the second pass through aw_pcm_rateconv_process / _flush.
+ * Outputs are a pure function of the input, so the second pass produces the y the first measured, and g y holds c up to the roundings
+ * of the product and of a second reading.  AW_GAIN_PEAK_CEILING and AW_GAIN_TRUE_PEAK_CEILING stay refused by aw_pcm_rateconv_set_gain.
+ * A NULL handle, an unknown format, a NULL input with in_frames > 0, a negative in_frames or a range outside the handle returns
+ * AW_ERR_INVALID_ARGUMENT before any HIP call and writes nothing. */
+typedef struct aw_rateconv_true_peak {
+    float    true_peak;    /* max over channels and frames of the contributions, linear full scale */
+    float    sample_peak;  /* max |v| over the same frames (equals aw_rateconv_levels.peak when both meters saw the same calls) */
+    uint64_t frames;       /* output frames measured */
+} aw_rateconv_true_peak;   /* 16 bytes */
+/* on != 0: makes the one device allocation the feature needs at the first such call (the records and two slots of carried v
+ * [streams][11][channels]; never on a process path) and measures every later aw_pcm_rateconv_* call; switching it on again after 0
+ * starts from v = 0.  The measuring form computes 11 output frames beside its tile; for the few handles whose tile (aw_rateconv_info 4)
+ * leaves none, on != 0 returns AW_ERR_INVALID_ARGUMENT and leaves the setting.  0: stops measuring, the records stay readable. */
+AW_API aw_status aw_tp_rateconv_set(aw_rateconv *rc, int32_t on);
+/* Copies the records of streams [first_stream, first_stream + n) to out_host on the context's stream, then synchronises it.  A range
+ * outside the handle's streams, or a handle that was never switched on, returns AW_ERR_INVALID_ARGUMENT. */
+AW_API aw_status aw_tp_rateconv_get(aw_rateconv *rc, int32_t first_stream, int32_t n, aw_rateconv_true_peak *out_host);
+/* Zeroes every record (asynchronous on the context's stream); the setting and the carried v stay. */
+AW_API aw_status aw_tp_rateconv_reset_records(aw_rateconv *rc);
+/* Both require measuring to be on (AW_ERR_INVALID_ARGUMENT otherwise, the counts untouched) and only enqueue on the context's stream. */
+AW_API aw_status aw_tp_rateconv_measure(aw_rateconv *rc, const void *in_device, aw_sample_format in_format, int64_t in_frames,
+                                        int64_t *out_frames);
+AW_API aw_status aw_tp_rateconv_measure_flush(aw_rateconv *rc, int64_t *out_frames);
 
 AW_API const char *aw_version(void);
 

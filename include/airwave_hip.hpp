@@ -304,6 +304,30 @@ class RateConverter {
         return out;
     }
     void resetLevels() { check(aw_pcm_rateconv_reset_levels(h_)); }
+    // true peak of the converted output and the ceiling pass (aw_tp_rateconv_*)
+    void setTruePeak(bool on) { check(aw_tp_rateconv_set(h_, on ? 1 : 0)); }
+    std::vector<aw_rateconv_true_peak> truePeak(int32_t firstStream, int32_t n) {
+        std::vector<aw_rateconv_true_peak> out((size_t)(n > 0 ? n : 0));
+        check(aw_tp_rateconv_get(h_, firstStream, n, out.data()));
+        return out;
+    }
+    void resetTruePeak() { check(aw_tp_rateconv_reset_records(h_)); }
+    int64_t measure(const void *inDevice, aw_sample_format inFormat, int64_t inFrames) {
+        int64_t n = 0;
+        check(aw_tp_rateconv_measure(h_, inDevice, inFormat, inFrames, &n));
+        return n;
+    }
+    int64_t measureFlush() {
+        int64_t n = 0;
+        check(aw_tp_rateconv_measure_flush(h_, &n));
+        return n;
+    }
+    // g = tp > c ? c / tp : 1 in float32 over what the records hold, for setGainFixed before the second pass
+    std::vector<float> ceilingGains(float ceiling, int32_t nStreams) {
+        std::vector<float> g;
+        for (const aw_rateconv_true_peak &r : truePeak(0, nStreams)) g.push_back(r.true_peak > ceiling ? ceiling / r.true_peak : 1.0f);
+        return g;
+    }
   private:
     aw_rateconv *h_ = nullptr;
 };
