@@ -26,10 +26,6 @@
 #define AW_HD inline __attribute__((always_inline))
 #endif
 
-#ifndef AW_PK_CMUL
-#define AW_PK_CMUL 0     // measured: -23 % VALU instructions (3872 -> 2995 per tile and wave), +2.5x v_mov, 10 spills: 1.56 -> 1.67 ms.  Off.
-#endif
-
 namespace awk {
 
 struct alignas(8) cf {
@@ -39,46 +35,6 @@ struct alignas(8) cf {
 AW_HD cf mk(float x, float y) { cf r; r.x = x; r.y = y; return r; }
 AW_HD cf operator+(cf a, cf b) { return mk(a.x + b.x, a.y + b.y); }
 AW_HD cf operator-(cf a, cf b) { return mk(a.x - b.x, a.y - b.y); }
-#if defined(__HIP_DEVICE_COMPILE__) && AW_PK_CMUL
-// Complex multiplies as two packed-FP32 instructions instead of four scalar ones: v_pk_mul/fma_f32 take a
-// register PAIR per operand and can pick the low or high half of each source per result half (op_sel /
-// op_sel_hi) and negate per half (neg_lo / neg_hi) — exactly the swizzles of (re, im) arithmetic.  hipcc packs
-// complex adds by itself but not these.
-typedef float aw_f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ aw_f2 aw_v2(cf a) { aw_f2 r; r.x = a.x; r.y = a.y; return r; }
-__device__ __forceinline__ cf aw_c(aw_f2 a) { return mk(a.x, a.y); }
-// t = (a.x b.x, a.y b.x) [+ acc]
-__device__ __forceinline__ aw_f2 aw_pk_mul_bx(aw_f2 a, aw_f2 b) {
-    aw_f2 t;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t) : "v"(a), "v"(b));
-    return t;
-}
-__device__ __forceinline__ aw_f2 aw_pk_fma_bx(aw_f2 a, aw_f2 b, aw_f2 c) {
-    aw_f2 t;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(t) : "v"(a), "v"(b), "v"(c));
-    return t;
-}
-// r = (t.x - a.y b.y, t.y + a.x b.y)          (a * b, second half)
-__device__ __forceinline__ aw_f2 aw_pk_fma_by(aw_f2 a, aw_f2 b, aw_f2 t) {
-    aw_f2 r;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]" : "=v"(r) : "v"(a), "v"(b), "v"(t));
-    return r;
-}
-// r = (t.x + a.y b.y, t.y - a.x b.y)          (a * conj(b) and conj(a) * b share it up to which operand is conjugated)
-__device__ __forceinline__ aw_f2 aw_pk_fma_by_c(aw_f2 a, aw_f2 b, aw_f2 t) {
-    aw_f2 r;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]" : "=v"(r) : "v"(a), "v"(b), "v"(t));
-    return r;
-}
-AW_HD cf cmul(cf a, cf b) { const aw_f2 A = aw_v2(a), B = aw_v2(b); return aw_c(aw_pk_fma_by(A, B, aw_pk_mul_bx(A, B))); }
-// a * conj(b) = (a.x b.x + a.y b.y, a.y b.x - a.x b.y)
-AW_HD cf cmulc(cf a, cf b) { const aw_f2 A = aw_v2(a), B = aw_v2(b); return aw_c(aw_pk_fma_by_c(A, B, aw_pk_mul_bx(A, B))); }
-AW_HD cf conj(cf a) { return mk(a.x, -a.y); }
-// acc + a*b
-AW_HD cf cfma(cf a, cf b, cf acc) { const aw_f2 A = aw_v2(a), B = aw_v2(b); return aw_c(aw_pk_fma_by(A, B, aw_pk_fma_bx(A, B, aw_v2(acc)))); }
-// acc + conj(a)*b = acc + (a.x b.x + a.y b.y, a.x b.y - a.y b.x) = acc + b * conj(a)
-AW_HD cf cfmac(cf a, cf b, cf acc) { const aw_f2 A = aw_v2(a), B = aw_v2(b); return aw_c(aw_pk_fma_by_c(B, A, aw_pk_fma_bx(B, A, aw_v2(acc)))); }
-#else
 AW_HD cf cmul(cf a, cf b) { return mk(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 // a * conj(b)
 AW_HD cf cmulc(cf a, cf b) { return mk(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }
@@ -91,7 +47,6 @@ AW_HD cf cfma(cf a, cf b, cf acc) {
 AW_HD cf cfmac(cf a, cf b, cf acc) {
     return mk(acc.x + a.x * b.x + a.y * b.y, acc.y + a.x * b.y - a.y * b.x);
 }
-#endif
 // multiply by -i (forward quarter turn) or +i
 AW_HD cf mul_mi(cf a) { return mk(a.y, -a.x); }
 AW_HD cf mul_pi(cf a) { return mk(-a.y, a.x); }
@@ -133,29 +88,10 @@ template <bool INV> AW_HD void fft8(cf (&v)[8]) {
     v[3] = e3 + o3; v[7] = e3 - o3;
 }
 
-// multiply by W16^m (forward) / conj (inverse), m compile-time in {0,1,2,3,4,6,9}
-template <bool INV, int M> AW_HD cf mul_w16(cf a) {
-    if constexpr (M == 0) return a;
-    else if constexpr (M == 4) return rot90<INV>(a);
-    else if constexpr (M == 2) return mul_w8_1<INV>(a);
-    else if constexpr (M == 6) return mul_w8_3<INV>(a);
-    else {
-        // W16^1 = c - i s, W16^3 = s - i c, W16^9 = -c + i s   (c = cos(pi/8), s = sin(pi/8))
-        constexpr float wr = (M == 1) ? kC8 : (M == 3) ? kS8 : -kC8;
-        constexpr float wi_f = (M == 1) ? -kS8 : (M == 3) ? -kC8 : kS8;
-        const float wi = INV ? -wi_f : wi_f;
-        return mk(a.x * wr - a.y * wi, a.x * wi + a.y * wr);
-    }
-}
-
 // ---- 16-point DFT, natural order in/out (4 x 4) ------------------------------------------------------------------------------
 // Second-layer groups with their constant twiddles folded into the butterflies (the vector unit issues an FMA at the price of an
 // add): x0 + W x2 and x0 - W x2 for an eighth-turn W are two FMAs on one unscaled sum, W_a x1 +- W_b x3 is one explicit product,
 // one FMA-form sum and 2 (W_a x1) - sum.  148 instead of 160 instructions per transform.
-#ifndef AW_FFT16_PLAIN
-#define AW_FFT16_PLAIN 0        // 1: the plain form (twiddle multiplies, then fft4) for A/B
-#endif
-
 // unscaled W8^M x / kS2 (forward) or conj(W8^M) x / kS2, M in {1, 3}: two adds
 template <bool INV, int M> AW_HD cf w8_sum(cf a) {
     if constexpr (M == 1) return INV ? mk(a.x - a.y, a.x + a.y) : mk(a.x + a.y, a.y - a.x);
@@ -200,20 +136,10 @@ template <bool INV> AW_HD void fft16(cf (&v)[16]) {
     fft4<INV>(v[2], v[6], v[10], v[14]);
     fft4<INV>(v[3], v[7], v[11], v[15]);
     // now v[4 k0 + n0] holds F_{n0}[k0]; X[k0 + 4 k1] = fft4 over n0 of W16^{n0 k0} v[4 k0 + n0]  -> result index k1 lands in slot 4 k0 + k1
-#if AW_FFT16_PLAIN
-    v[5] = mul_w16<INV, 1>(v[5]);  v[6] = mul_w16<INV, 2>(v[6]);   v[7] = mul_w16<INV, 3>(v[7]);
-    v[9] = mul_w16<INV, 2>(v[9]);  v[10] = mul_w16<INV, 4>(v[10]); v[11] = mul_w16<INV, 6>(v[11]);
-    v[13] = mul_w16<INV, 3>(v[13]); v[14] = mul_w16<INV, 6>(v[14]); v[15] = mul_w16<INV, 9>(v[15]);
-    fft4<INV>(v[0], v[1], v[2], v[3]);
-    fft4<INV>(v[4], v[5], v[6], v[7]);
-    fft4<INV>(v[8], v[9], v[10], v[11]);
-    fft4<INV>(v[12], v[13], v[14], v[15]);
-#else
     fft4<INV>(v[0], v[1], v[2], v[3]);
     fft4_w16<INV, 1>(v[4], v[5], v[6], v[7]);
     fft4_w8<INV>(v[8], v[9], v[10], v[11]);
     fft4_w16<INV, 3>(v[12], v[13], v[14], v[15]);
-#endif
     // slot 4 k0 + k1 holds X[k0 + 4 k1]: transpose to natural order
     cf t;
     t = v[1]; v[1] = v[4]; v[4] = t;

@@ -40,12 +40,6 @@ constexpr int kEqThreads = 256;
 #endif
 constexpr int kEqChunk = AW_EQ_CHUNK;            // frames per thread and span (power of two)
 constexpr int kEqSpan = kEqThreads * kEqChunk;   // 8192 frames
-#ifndef AW_EQ_COEF_AHEAD
-#define AW_EQ_COEF_AHEAD 0                       // 1: coefficient tables fetched one filter ahead (50 more SGPRs: spills, 3 % slower)
-#endif
-#ifndef AW_EQ_PREFETCH
-#define AW_EQ_PREFETCH 0                         // 1: the next span's loads are issued before the filter loop (kEqChunk x E more VGPRs; no faster at 16, spills at 32)
-#endif
 constexpr int kEqMaxFilters = 64;                // ParametricEqualizerState.maximumFilterCount :17
 constexpr int kEqScanSteps = 7;                  // P^(2^s), s = 0 .. 6 (6 = one whole wave of chunks)
 // LDS map (bytes)
@@ -173,12 +167,11 @@ template <class Ctx, int E> AW_HD void eq_cascade_stream(Ctx &ctx, const EqParam
         }
     };
     auto span_frames = [&](long long base) { const long long rem = p.frames - base; return rem < kEqSpan ? (int)rem : kEqSpan; };
-    if (AW_EQ_PREFETCH && p.frames > 0) fetch(0, span_frames(0));
 
     for (long long base = 0; base < p.frames; base += kEqSpan) {
         const int nfr = span_frames(base);
         const int nchunks = nfr / kEqChunk;
-        if (!AW_EQ_PREFETCH) fetch(base, nfr);
+        fetch(base, nfr);
         ctx.barrier();   // stage reads of the previous span and the carry writes are complete
         // registers -> LDS in frame order, LDS -> registers transposed to one chunk per thread
 #pragma unroll
@@ -192,7 +185,6 @@ template <class Ctx, int E> AW_HD void eq_cascade_stream(Ctx &ctx, const EqParam
         for (int j = 0; j < kEqChunk; ++j)
 #pragma unroll
             for (int e = 0; e < E; ++e) x[e][j] = (double)stage[tid * kStride + j * E + e] * preamp;   // :67-69
-        if (AW_EQ_PREFETCH && base + kEqSpan < p.frames) fetch(base + kEqSpan, span_frames(base + kEqSpan));              // lands during the filter loop
 
         // the filter's coefficients and scan powers (25 wave-uniform doubles) come in ONE batch of scalar loads at the top of
         // its iteration (left to itself hipcc loads the scan powers where they are used: two more stalls per filter)
@@ -206,15 +198,13 @@ template <class Ctx, int E> AW_HD void eq_cascade_stream(Ctx &ctx, const EqParam
 #pragma unroll
             for (int i = 0; i < 4; ++i) pk[16 + i] = c[5 + kEqChunk * 2 + 6 * 4 + i];
         };
-        if (AW_EQ_COEF_AHEAD && K > 0) fetch_coefs(0);
         for (int k = 0; k < K; ++k) {
             const double *c = p.t.tab + (long long)k * kEqTabDoubles;      // uniform: scalar loads
-            if (!AW_EQ_COEF_AHEAD) fetch_coefs(k);
+            fetch_coefs(k);
             const double b0 = ck[0], b1 = ck[1], b2 = ck[2], na1 = -ck[3], na2 = -ck[4];
             double pp[20];
 #pragma unroll
             for (int i = 0; i < 20; ++i) pp[i] = pk[i];
-            if (AW_EQ_COEF_AHEAD) fetch_coefs(k + 1 < K ? k + 1 : k);
             // this lane's powers of P: D[m] = P^(m+1).  Issued now, consumed after the chunk's recurrence
             const double *dk = p.t.plane + (long long)k * 64 * 4;
             double d16[4], d32[4], d64[4];

@@ -21,7 +21,7 @@ template <int CS, int NP, bool INTERIOR, bool ACC = false>
 __global__ void __launch_bounds__(kThreads) aw_fused_ols_kernel(TileParams p, long long n_tiles) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     GpuCtx ctx{reinterpret_cast<cf *>(smem), p.dbg ? p.dbg + (long long)blockIdx.x * kStamps : nullptr};
-    ctx.stamp_thread_ = p.stagger;          // diagnostic builds: which thread's wave is recorded
+    ctx.stamp_thread_ = p.stamp_thread;          // diagnostic builds: which thread's wave is recorded
     const XcdShare x = xcd_share(n_tiles);          // persistent workgroups, XCD-aware (gpu_ctx.hpp)
     tiles_fused_ols<GpuCtx, CS, NP, INTERIOR, ACC>(ctx, p, x.lo + x.slot, x.wgs, x.hi);
 }
@@ -29,9 +29,6 @@ __global__ void __launch_bounds__(kThreads) aw_fused_ols_kernel(TileParams p, lo
 
 // Windows [tile_lo, tile_hi) of every stream lie inside the call's input (INTERIOR), the others touch the
 // history or the zero page.  p.tile_lo/hi carry the window range here.
-#ifndef AW_FWD_RUNS
-#define AW_FWD_RUNS 0
-#endif
 // MODE 1: windows [tile_lo, tile_hi) (interior); MODE 2: windows [head_lo, tile_lo) (head: history + input);
 // MODE 0: the rest, [0, head_lo) and [tile_hi, n_windows).  Persistent, XCD-aware like the fused kernels: each XCD group
 // walks a contiguous eighth of the window list, so windows that overlap by half meet in one L2.
@@ -43,15 +40,7 @@ __global__ void __launch_bounds__(kThreads) aw_part_forward_kernel(TileParams p,
     const int per = MODE == 1 ? p.tile_hi - p.tile_lo : MODE == 2 ? p.tile_lo - head_lo : n_windows - (p.tile_hi - head_lo);
     const int w0 = MODE == 1 ? p.tile_lo : head_lo, skip = p.tile_hi - head_lo;
     const XcdShare x = xcd_share(n_ids);
-#if AW_FWD_RUNS
-    // each workgroup walks a contiguous run of windows: consecutive windows of a stream overlap by half, and the half a
-    // workgroup has just read is the likeliest to still be in its XCD's L2
-    const long long run = (x.hi - x.lo + x.wgs - 1) / x.wgs;
-    const long long first = x.lo + x.slot * run;
-    tiles_part_forward<GpuCtx, CS, MODE>(ctx, p, first, 1, first + run < x.hi ? first + run : x.hi, per, w0, skip);
-#else
     tiles_part_forward<GpuCtx, CS, MODE>(ctx, p, x.lo + x.slot, x.wgs, x.hi, per, w0, skip);
-#endif
 }
 
 // One-pair form: workgroup id -> (stream, window, pair), pairs innermost; kInvLdsBytes of LDS, two workgroups per CU.

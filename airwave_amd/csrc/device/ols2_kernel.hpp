@@ -14,7 +14,7 @@ template <int CS, int NB, bool INTERIOR>
 __global__ void __launch_bounds__(kThreads) aw_fused_ols2_kernel(TileParams p, long long n_tiles) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     GpuCtx ctx{reinterpret_cast<cf *>(smem), p.dbg ? p.dbg + (long long)blockIdx.x * kStamps : nullptr};
-    ctx.stamp_thread_ = p.stagger;
+    ctx.stamp_thread_ = p.stamp_thread;
     const XcdShare x = xcd_share(n_tiles);
     tiles_fused_ols2<GpuCtx, CS, NB, INTERIOR>(ctx, p, x.lo + x.slot, x.wgs, x.hi);
 }

@@ -86,7 +86,6 @@ template <bool INV, class Ctx> AW_HD void r16_tw2_apply(Ctx &ctx, cf (&v)[16], c
         cf w[B];
 #pragma unroll
         for (int i = 0; i < B; ++i) if (m + i < 16) w[i] = ctx.ld(tw2 + 16 * (m + i));
-        ctx.sched_fence();
 #pragma unroll
         for (int i = 0; i < B; ++i) if (m + i < 16) v[m + i] = twmul<INV>(v[m + i], w[i]);
     }

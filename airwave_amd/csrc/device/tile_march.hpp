@@ -78,13 +78,10 @@ template <int PQ> struct MarchState {
 #endif
 
 // One spectrum value, read once: a non-temporal load (measured 7.1 against 6.4 TB/s for plain streaming loads).
-#ifndef AW_MARCH_NT
-#define AW_MARCH_NT 1
-#endif
 template <bool NT>
 AW_HD cf march_ld(const cf *p) {
     if constexpr (!NT) return *p;
-#if defined(__HIP_DEVICE_COMPILE__) && AW_MARCH_NT
+#if defined(__HIP_DEVICE_COMPILE__)
     typedef float v2f __attribute__((ext_vector_type(2)));
     const v2f v = __builtin_nontemporal_load(reinterpret_cast<const v2f *>(p));
     return mk(v.x, v.y);

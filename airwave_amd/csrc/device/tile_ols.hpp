@@ -46,12 +46,11 @@
 //   - pass 1 from the register batch as a helper (either with its own x[16] or the caller's):
 //     aw_fused_ols_kernel<13, 7> / <14, 7> 19 -> 20 spilled VGPRs; written out at its call sites;
 //   - load_batch_head under load_frames: 1-2 more VGPRs in five head forward kernels;
-//   - the call-wrapping lambdas of the batch bodies (load_tab_, subfft_cmac_) and the
+//   - the call-wrapping lambda of the batch bodies (subfft_cmac_) and the
 //     overlap-add tile's ola_subfft_cmac, a wrapper with the old parameter list: calling
 //     pair_subfft_cmac_h directly moves aw_fused_ola_kernel<14, 7, 6> from 1 to 3 spilled VGPRs
 //     and <13, 7, 6> from 252 to 253 VGPRs.
 #pragma once
-#include <type_traits>
 #include "cplx.hpp"
 
 namespace awk {
@@ -69,28 +68,10 @@ constexpr int kLdsBytes = kLdsElems * 8;               // 152064 B (<= 160 KiB)
 #ifndef AW_XA_REG
 #define AW_XA_REG 0      // 1: first sub-FFT exchange through cross-lane swaps instead of LDS (correct; measured 1.54 -> 1.68 ms: +735 VALU instructions per tile and wave for -120 LDS ones)
 #endif
-#ifndef AW_PREFETCH_RAW_EARLY
-#define AW_PREFETCH_RAW_EARLY 1
-#endif
-constexpr bool kPrefetchRawEarly = AW_PREFETCH_RAW_EARLY != 0;
-#ifndef AW_TAB_EARLY
-#define AW_TAB_EARLY 0
-#endif
-constexpr bool kTabEarly0 = (AW_TAB_EARLY & 1) != 0;   // first pair of a batch: table loads issued before the barrier
-constexpr bool kTabEarly1 = (AW_TAB_EARLY & 2) != 0;   // second pair: issued right after the first pair's CMAC   // issue the next batch's frame loads before pair 1's sub-FFTs
 // The 8192-frame tile's tables after the transform in one go (64 VGPRs) or in two parts of eight bins.  Measured per layout (tools/ols2_ab.py
 // WINDOW=8192, tools/ubench/tile_bench.hip): 13 / 14 channels 22.5 / 21.9 -> 23.9 / 23.2 G frames/s (19 spilled VGPRs either way, fewer live through
 // the multiply-accumulate), 9 / 10 +-0, 11 / 12 channels 28.5 / 29.2 -> 24.0 / 23.0 (!), 8 channels +-0 (parts of four: -5 %) — seven pairs only.
-#ifndef AW_TAB_G7
-#define AW_TAB_G7 8
-#endif
-#ifndef AW_SKIP_PHANTOM
-#define AW_SKIP_PHANTOM 1
-#endif
-constexpr bool kSkipPhantom = AW_SKIP_PHANTOM != 0;   // run-time batch loop: an odd pair count's last batch transforms one pair, not a phantom second one
-#ifndef AW_EVEN_F2_LOADS
-#define AW_EVEN_F2_LOADS 0
-#endif
+constexpr int kTabG7 = 8;
 constexpr int kBatchCh = 4;       // input channels held in registers at once (two pairs)
 
 struct alignas(16) cf2 {          // one table entry: A[k], B[k]
@@ -125,7 +106,7 @@ struct TileParams {
     int ch_base;            // second pass of a wide layout: `in`, `hist` and `tab` are shifted by this many channels (8); 0 otherwise
     int fwd_one_pair;       // forward kernel form: 1 = one channel pair per workgroup (two workgroups per CU), 0 = all pairs in one workgroup
     int herm_last;          // odd channel count: the last pair's input is real, its spectrum Hermitian — rows 9..15 are neither stored nor read
-    int stagger;            // tuning: waves 4-7 idle this many 64-cycle slots after each barrier (phase offset)
+    int stamp_thread;       // diagnostic builds only (AW_STAMPS): the thread whose wave records its stamps
     unsigned long long *dbg; // diagnostic builds only (AW_STAMPS): [workgroup][16] s_memtime stamps of wave 0
 };
 constexpr int kStamps = 32;
@@ -165,9 +146,7 @@ AW_HD void sub_fft512x2(Ctx &ctx, cf (&a)[2][8], cf *scr0, cf *scr1, const cf *t
     ctx.stamp(SB + 0);
     // pass A: radix-8 over j -> ka, twiddle W_512^{lane ka}
     fft8<INV>(a[0]);
-    ctx.sched_fence();
     fft8<INV>(a[1]);
-    ctx.sched_fence();
 #pragma unroll
     for (int ka = 1; ka < 8; ++ka) {
         const cf w = ctx.ld(twa + ka * 64 + lane);
@@ -202,9 +181,7 @@ AW_HD void sub_fft512x2(Ctx &ctx, cf (&a)[2][8], cf *scr0, cf *scr1, const cf *t
     ctx.stamp(SB + 2);
     // pass B: radix-8 over l1 -> kb, twiddle W_64^{l0 kb}
     fft8<INV>(a[0]);
-    ctx.sched_fence();
     fft8<INV>(a[1]);
-    ctx.sched_fence();
 #pragma unroll
     for (int kb = 1; kb < 8; ++kb) {
         const cf w = ctx.ld(twb + kb * 8 + l0);
@@ -221,9 +198,7 @@ AW_HD void sub_fft512x2(Ctx &ctx, cf (&a)[2][8], cf *scr0, cf *scr1, const cf *t
     ctx.stamp(SB + 4);
     // pass C: radix-8 over l0 -> kc.  Now a[s][kc] = X_s[ka'' + 8 kb'' + 64 kc] = X_s[lane + 64 kc]
     fft8<INV>(a[0]);
-    ctx.sched_fence();
     fft8<INV>(a[1]);
-    ctx.sched_fence();
     ctx.stamp(SB + 5);
 }
 
@@ -279,7 +254,6 @@ template <bool INV, class Ctx> AW_HD void hl_tw_apply(Ctx &ctx, cf (&a)[16], con
         cf w[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) if (m + i < 16) w[i] = ctx.ld(L.twh + 32 * (m + i));
-        ctx.sched_fence();
 #pragma unroll
         for (int i = 0; i < 8; ++i) if (m + i < 16) a[m + i] = twmul<INV>(a[m + i], w[i]);
     }
@@ -435,11 +409,6 @@ AW_HD void load_frames(const Addr &addr, float (&raw)[16][kBatchCh]) {
         } else if constexpr (CS == 2) {
             ld_vec<2, true>(src, raw[j]);
             raw[j][2] = 0.f; raw[j][3] = 0.f;
-        } else if constexpr (CS % 2 == 0 && AW_EVEN_F2_LOADS) {
-            // 6, 10, 14 channels: frames are multiples of 8 bytes — two naturally aligned 8-byte loads instead of one
-            // dword-aligned 16-byte load (which the memory pipeline splits)
-            ld_vec<2, true>(src, raw[j]);
-            ld_vec<2, true>(src + 2, raw[j] + 2);
         } else {
             // frames that are not whole float4s (6, 7, 14 channels): one dword-aligned 16-B load all the
             // same.  The last batch of a frame runs up to 3 floats into the next frame; those lanes belong
@@ -453,14 +422,14 @@ AW_HD void load_frames(const Addr &addr, float (&raw)[16][kBatchCh]) {
 // Both four-channel batches of the 16 frames in one go (5 or more channels; the address rule points at the first of the
 // eight channels): the two 16-byte loads of a frame are issued back to back.
 // SECOND: floats of the second batch that are fetched — 4 (all), 2 (a seventh pair is the group's last: 13-14 channels) or
-// 0 (9-12 channels: the last eight-channel group has one batch).  FIRST = false: the second batch alone.
-template <int CS, int SECOND = 4, bool FIRST = true, class Addr>
+// 0 (9-12 channels: the last eight-channel group has one batch).
+template <int CS, int SECOND = 4, class Addr>
 AW_HD void load_frames2(const Addr &addr, float (&ra)[16][kBatchCh], float (&rb)[16][kBatchCh]) {
     static_assert(CS >= 5, "two batches of four channels (the first eight channels from the base pointer; wide layouts shift the base)");
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         const float *src = addr(j);
-        if constexpr (FIRST) ld_vec<4, CS % 4 == 0>(src, ra[j]);
+        ld_vec<4, CS % 4 == 0>(src, ra[j]);
         if constexpr (SECOND == 4) {
             ld_vec<4, CS % 4 == 0>(src + 4, rb[j]);       // frames that are not whole float4s: runs up to 3 floats into the next frame, zero tables (see load_frames)
         } else if constexpr (SECOND == 2) {
@@ -495,16 +464,10 @@ AW_HD void load_batch(const TileParams &p, const float *in_s, const float *hist_
 // frame are issued back to back, so the second one hits the line the first has just brought into L1 — the batches no longer
 // pull every line through the L2 -> L1 path twice, half a tile apart (tools/ubench/tile_bench.hip: frame loads are 20 % of a
 // cfg-2 tile, a throughput cost of that path).  Same registers as issuing batch 1 during batch 0's processing.
-#ifndef AW_WHOLE_FRAMES
-#define AW_WHOLE_FRAMES 1
-#endif
-#ifndef AW_WIDE_LATE_B
-#define AW_WIDE_LATE_B 0     // 1: the second batch of a wide layout's second channel group is fetched one pair later (measured: 14 channels 17.1 -> 15.9 G frames/s)
-#endif
 // (load_frames2 behind the interior address rule, under the name its five call sites use)
-template <int CS, int SECOND = 4, bool FIRST = true>
+template <int CS, int SECOND = 4>
 AW_HD void load_batch2(const float *in_s, long long f0, int t, float (&ra)[16][kBatchCh], float (&rb)[16][kBatchCh]) {
-    load_frames2<CS, SECOND, FIRST>(InteriorFrames<CS>(in_s, f0, t, 0), ra, rb);
+    load_frames2<CS, SECOND>(InteriorFrames<CS>(in_s, f0, t, 0), ra, rb);
 }
 
 // One batch of a head window.  The same loop as load_frames<CS>(HeadFrames<CS>(...), raw), written out: through the shared
@@ -750,8 +713,8 @@ AW_HD void tiles_fused_ols(Ctx &ctx, const TileParams &p, long long first, long 
     // while the first one's last pair is transformed — raw is free since batch 0's pass 1, raw_b since batch 1's — and takes
     // the first group's place.  One accumulator, one inverse transform and one output store for all pairs (the two-pass form
     // pays a second inverse and an output read-modify-write: 9 transforms instead of 8 for 14 channels).
-    constexpr bool kWide = AW_WHOLE_FRAMES != 0 && INTERIOR && !ACC && CS >= 9 && NP >= 5 && NP <= 8;
-    constexpr bool kWhole = kWide || (AW_WHOLE_FRAMES != 0 && INTERIOR && CS >= 5 && (NP == 3 || NP == 4));    // also both passes of the two-pass wide form
+    constexpr bool kWide = INTERIOR && !ACC && CS >= 9 && NP >= 5 && NP <= 8;
+    constexpr bool kWhole = kWide || (INTERIOR && CS >= 5 && (NP == 3 || NP == 4));    // also both passes of the two-pass wide form
     float raw[16][kBatchCh];
     float raw_b[kWhole ? 16 : 1][kBatchCh];
     {
@@ -777,9 +740,9 @@ AW_HD void tiles_fused_ols(Ctx &ctx, const TileParams &p, long long first, long 
     for (int i = 0; i < 16; ++i) wacc[i] = mk(0.f, 0.f);
 
     // Schedule per batch of two pairs:
-    //   pass 1 of both pairs -> buf0, buf1 ; issue pair 0's table loads ; barrier ;
-    //   sub-FFTs + CMAC of pair 0 ; issue pair 1's table loads and the NEXT batch's frame loads
-    //   (their latency hides under pair 1's sub-FFTs) ; sub-FFTs + CMAC of pair 1.
+    //   pass 1 of both pairs -> buf0, buf1 ; barrier ;
+    //   sub-FFTs + CMAC of pair 0 (its table loads are issued behind its row transforms) ; issue the NEXT batch's
+    //   frame loads (their latency hides under pair 1's sub-FFTs) ; sub-FFTs + CMAC of pair 1.
     const int n_pairs = NP > 0 ? NP : p.n_pairs;
     auto batch = [&](int pair0, bool two, bool more) {
         if (pair0 > 0) ctx.barrier();                    // every wave is done reading buf0/buf1
@@ -821,27 +784,19 @@ AW_HD void tiles_fused_ols(Ctx &ctx, const TileParams &p, long long first, long 
             }
         }
         cf2 tab[16];
-        constexpr int kTabG = (kTabEarly0 || kTabEarly1) ? 16 : NP == 7 ? AW_TAB_G7 : 16;
-        auto load_tab_ = [&](int pr) { load_tab_h(p, pr, wave, lane, tab); };
-        auto subfft_cmac_ = [&](auto early, int pr, cf *bf) { pair_subfft_cmac_h<kTabG, decltype(early)::value>(ctx, p, pr, bf, twa, tab, lane, wave, wacc); };
-        if (kTabEarly0) load_tab_(pair0);
+        constexpr int kTabG = NP == 7 ? kTabG7 : 16;
+        auto subfft_cmac_ = [&](int pr, cf *bf) { pair_subfft_cmac_h<kTabG, false>(ctx, p, pr, bf, twa, tab, lane, wave, wacc); };
         ctx.stamp(pair0 > 0 ? 7 : 2);
         ctx.barrier();
-        ctx.stagger(wave, p.stagger);
         ctx.stamp(pair0 > 0 ? 8 : 3);
-        subfft_cmac_(std::bool_constant<kTabEarly0>{}, pair0, buf0);
+        subfft_cmac_(pair0, buf0);
         ctx.stamp(pair0 > 0 ? 9 : 4);
         const int pair1 = pair0 + 1;     // a phantom second pair (odd pair count, runtime loop) lands on the zero pair after the last one
-        if (two && kTabEarly1) load_tab_(pair1);
         if constexpr (kWide) {
-            if (pair0 == 2) load_batch2<CS, (NP == 8 && !AW_WIDE_LATE_B ? 4 : NP == 7 && !AW_WIDE_LATE_B ? 2 : 0)>(in_s + 8, f0, t, raw, raw_b);      // channels 8-15 (a 9-12 channel layout: 8-11 only)
+            if (pair0 == 2) load_batch2<CS, (NP == 8 ? 4 : NP == 7 ? 2 : 0)>(in_s + 8, f0, t, raw, raw_b);      // channels 8-15 (a 9-12 channel layout: 8-11 only)
         }
-        if (!kWhole && kPrefetchRawEarly && more) load_batch<CS, INTERIOR>(p, in_s, hist_s, f0, t, 2 * (pair0 + 2), raw);
-        if (two) subfft_cmac_(std::bool_constant<kTabEarly1>{}, pair1, buf1);
-        if constexpr (kWide && AW_WIDE_LATE_B != 0 && NP >= 7) {      // the group's second batch one pair later (an L2 hit): fewer values live through the CMAC
-            if (pair0 == 2) load_batch2<CS, (NP == 8 ? 4 : 2), false>(in_s + 8, f0, t, raw, raw_b);
-        }
-        if (!kWhole && !kPrefetchRawEarly && more) load_batch<CS, INTERIOR>(p, in_s, hist_s, f0, t, 2 * (pair0 + 2), raw);
+        if (!kWhole && more) load_batch<CS, INTERIOR>(p, in_s, hist_s, f0, t, 2 * (pair0 + 2), raw);
+        if (two) subfft_cmac_(pair1, buf1);
         ctx.stamp(pair0 > 0 ? 10 : 5);
     };
     if constexpr (NP > 0) {
@@ -852,7 +807,7 @@ AW_HD void tiles_fused_ols(Ctx &ctx, const TileParams &p, long long first, long 
         // layouts known at compile time to have an even pair count keep the branch-free body
         constexpr bool kEvenPairs = CS > 0 && ((CS + 1) / 2) % 2 == 0;
         for (int pair0 = 0; pair0 < n_pairs; pair0 += 2)
-            batch(pair0, (kSkipPhantom && !kEvenPairs) ? pair0 + 1 < n_pairs : true, pair0 + 2 < n_pairs);
+            batch(pair0, kEvenPairs ? true : pair0 + 1 < n_pairs, pair0 + 2 < n_pairs);
     }
 
     tile_inverse_rows_h(ctx, wacc, buf0, twa);
@@ -874,30 +829,13 @@ AW_HD void tiles_fused_ols(Ctx &ctx, const TileParams &p, long long first, long 
 // MODE 1 (interior): the window lies inside the call's input (whole-frame vector loads off a uniform base);
 // MODE 2 (head): history + input, nothing past the end (vector loads behind a per-frame pointer select);
 // MODE 0: anything (scalar loads; history, input or the zero page per frame).
-// One 512-bin row of a spectrum from registers (lane holds bins lane + 64 kc) to memory as 16-byte stores: neighbouring
-// lanes trade one value per pair of chunks, so that even lanes store bins (lane, lane + 1) of chunk 2m and odd lanes bins
-// (lane - 1, lane) of chunk 2m + 1 — half the store instructions of 8-byte stores, every instruction still two whole
-// 512-byte runs (the spectrum stores are the forward kernel's issue-bound tail: 10.9 ms with them, 7.9 ms without).
-#ifndef AW_FWD_STORE16
-#define AW_FWD_STORE16 0     // measured cfg 3: 10.95 ms with 16-byte stores against 10.66 ms with 8-byte ones — the stores are not issue-bound
-#endif
+// One 512-bin row of a spectrum from registers (lane holds bins lane + 64 kc) to memory: eight 8-byte streaming stores per lane,
+// every instruction one whole 512-byte run.  A function of its own on purpose: with the loop written out at its call site
+// hipcc emits different code for the forward kernels (see the note at the top).
 template <class Ctx>
-AW_HD void store_row16(Ctx &ctx, cf *row, const cf (&z)[8], int lane) {
-#if AW_FWD_STORE16
-    const bool odd = (lane & 1) != 0;
-    cf *base = row + (lane & ~1);
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const cf na = ctx.xchg1(z[2 * m]), nb = ctx.xchg1(z[2 * m + 1]);
-        cf2 v;
-        v.a = odd ? nb : z[2 * m];
-        v.b = odd ? z[2 * m + 1] : na;
-        *reinterpret_cast<cf2 *>(base + 64 * (2 * m + (odd ? 1 : 0))) = v;
-    }
-#else
+AW_HD void store_row(Ctx &ctx, cf *row, const cf (&z)[8], int lane) {
 #pragma unroll
     for (int kc = 0; kc < 8; ++kc) ctx.st_stream(row + lane + 64 * kc, z[kc]);
-#endif
 }
 
 // Persistent form: the workgroup walks window ids first, first + step, ... < end of its launch; id -> (stream, window)
@@ -949,7 +887,7 @@ AW_HD void tiles_part_forward(Ctx &ctx, const TileParams &p, long long first, lo
 
     // whole-frame mode (interior and head windows of 5-8 channel layouts): both four-channel batches of a window are loaded
     // together (load_frames2 behind either address rule: every line crosses the L2 -> L1 path once), the second batch waits in raw_b
-    constexpr bool kWhole = AW_WHOLE_FRAMES != 0 && (MODE == 1 || MODE == 2) && CS >= 5 && CS <= 8;
+    constexpr bool kWhole = (MODE == 1 || MODE == 2) && CS >= 5 && CS <= 8;
     float raw[16][kBatchCh];
     float raw_b[kWhole ? 16 : 1][kBatchCh];
     auto load_window = [&](const PartWin &w) {
@@ -1026,7 +964,7 @@ AW_HD void tiles_part_forward(Ctx &ctx, const TileParams &p, long long first, lo
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
                     if (s == 1 && skip1) break;
-                    store_row16(ctx, dst + wave_row(wave, s) * kSub, z[s], lane);
+                    store_row(ctx, dst + wave_row(wave, s) * kSub, z[s], lane);
                 }
             }
         }

@@ -737,7 +737,7 @@ struct SpChunkTimer {
 // stream s_base's frames (the caller's whole batch with s_base = 0, or one staged chunk of the host-entry pipeline).
 static aw_status sp_process_fused(aw_spatializer *sp, int s_base, int ns_total, const float *in, float *out, int64_t frames) {
     awk::TileParams p = sp_tile_params(sp, s_base, in, out, frames);
-    p.stagger = sp->ctx->cfg.stamp_thread;
+    p.stamp_thread = sp->ctx->cfg.stamp_thread;
 #if defined(AW_STAMPS) && AW_STAMPS
     {
         const long long nwg = (long long)ns_total * p.tiles_per_stream;

@@ -50,12 +50,10 @@ struct EmuCtx {
     awk::cf opaque(awk::cf v) const { return v; }
     int opaque_i(int v) const { return v; }
     void stamp(int) const {}
-    void sched_fence() const {}
     void sched_fence_hard() const {}
     template <int P> void prio() const {}
     void flush_stamps() const {}
     awk::cf ld(const awk::cf *p) const { return *p; }
-    void stagger(int, int) const {}
     void barrier() const { sh->wg.arrive_and_wait(); }
     // lanes with bit b = 0: hi' = partner.lo ; lanes with bit b = 1: lo' = partner.hi ; partner = lane ^ (1 << b)
     void xswap(awk::cf &lo, awk::cf &hi, int bit) const {
@@ -80,13 +78,6 @@ struct EmuCtx {
             const unsigned long long o = (unsigned long long)off + (unsigned)imm + 4u * i;
             if (o + 4 <= b.bytes) std::memcpy(&dst[i], b.base + o, 4); else dst[i] = 0.0f;
         }
-    }
-    awk::cf xchg1(awk::cf v) const {          // value of lane ^ 1
-        sh->xs[(size_t)tid_ * 2] = v;
-        sh->wave[tid_ >> 6]->arrive_and_wait();
-        const awk::cf r = sh->xs[(size_t)(tid_ ^ 1) * 2];
-        sh->wave[tid_ >> 6]->arrive_and_wait();
-        return r;
     }
     // in-register scan moves of eq_cascade.hpp (DPP on the GPU): value of another lane of the wave, or zero / fill
     double lane_value(double v, int src_lane, double otherwise) const {     // src_lane < 0: no source

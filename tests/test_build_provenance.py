@@ -34,7 +34,7 @@ def test_recorded_manifest_is_the_default_build():
 
 def test_an_environment_knob_changes_the_digest(monkeypatch):
     base = _build_module().flag_manifest()["build_flags_sha16"]
-    for var, val in (("AW_KERNELS_SLP", "1"), ("AW_EXTRA_HIPCC_FLAGS", "-DAW_STAGGER_SLOTS=2"), ("AW_MARCH_SLP", "1")):
+    for var, val in (("AW_KERNELS_SLP", "1"), ("AW_EXTRA_HIPCC_FLAGS", "-DAW_R16_PRIO=2"), ("AW_MARCH_SLP", "1")):
         monkeypatch.setenv(var, val)
         m = _build_module().flag_manifest()
         assert m["build_flags_sha16"] != base and m["env"] == {var: val}

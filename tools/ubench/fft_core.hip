@@ -39,7 +39,6 @@ __global__ void __launch_bounds__(kThreads) k_core(const cf *tw1, const cf *twa_
             else { fft16<false>(y); for (int k1 = 1; k1 < 16; ++k1) y[k1] = cmul(y[k1], pw[k1]); acc = acc + y[5]; }
         }
         if constexpr (!(VARIANT & 8)) ctx.barrier();
-        ctx.stagger(wave, 0);
         if constexpr (VARIANT & 2) { acc = acc + buf0[t]; continue; }      // no sub-FFTs
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
