@@ -12,7 +12,7 @@ _capi.load()
 from .api import (  # noqa: E402
     AirwaveError, Context, ConvolutionEngine, DITHER_MODES, GAIN_MODES, HRIR, HRIRChannelMap, HRIRError, HRIRManager, InputLayout, LEVELS_DTYPE,
     LOUDNESS_DTYPE, loudness_gain, TRUE_PEAK_DTYPE, true_peak_filter, LIMITER_DTYPE,
-    RealtimeAudioProcessor, Resampler, SAMPLE_FORMATS, Spatializer, WAVData, WAVError, WAVLoader, default_context, sample_format_bytes,
+    RealtimeAudioProcessor, Resampler, SAMPLE_FORMATS, Spatializer, EQ_KEEP, WAVData, WAVError, WAVLoader, default_context, sample_format_bytes,
 )
 
 from .rateconv import RateConverter, convert, rateconv_filter, rateconv_plan  # noqa: E402
@@ -34,5 +34,5 @@ __all__ = [
     "AirwaveError", "Context", "ConvolutionEngine", "HRIR", "HRIRChannelMap", "HRIRError", "HRIRManager",
     "InputLayout", "RealtimeAudioProcessor", "Resampler", "Spatializer", "WAVData", "WAVError", "WAVLoader",
     "default_context", "SAMPLE_FORMATS", "sample_format_bytes", "DITHER_MODES", "GAIN_MODES", "LEVELS_DTYPE",
-    "LOUDNESS_DTYPE", "loudness_gain", "TRUE_PEAK_DTYPE", "true_peak_filter", "LIMITER_DTYPE",
+    "LOUDNESS_DTYPE", "loudness_gain", "TRUE_PEAK_DTYPE", "true_peak_filter", "LIMITER_DTYPE", "EQ_KEEP",
 ]

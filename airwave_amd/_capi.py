@@ -69,6 +69,7 @@ SIGNATURES = {
     "aw_spatializer_set_limiter": (_I32, [_V, _I32, ctypes.c_float, _I32, _I32]),
     "aw_spatializer_get_limiter": (_I32, [_V, _I32, _I32, _V]),
     "aw_spatializer_set_equalizer": (_I32, [_V, c_void_pp, _I32, c_int32_p]),
+    "aw_spatializer_set_equalizer_target": (_I32, [_V, c_void_pp, _I32, c_int32_p]),
     "aw_spatializer_reset": (_I32, [_V]),
     "aw_spatializer_stream_count": (_I32, [_V]),
     "aw_spatializer_channel_count": (_I32, [_V]),

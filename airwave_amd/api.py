@@ -16,6 +16,7 @@ from . import _capi
 from ._capi import c_float_p, c_int32_p
 
 AW_OK = 0
+EQ_KEEP = -2          # AW_EQ_KEEP: a stream that is not part of a target change (Spatializer.set_equalizer_target)
 STATUS_NAMES = {
     1: "INVALID_ARGUMENT", 2: "OUT_OF_MEMORY", 3: "HIP", 4: "NO_DEVICE", 5: "INVALID_CHANNEL_MAPPING",
     6: "CONVOLUTION_SETUP_FAILED", 7: "INVALID_CHANNEL_COUNT", 8: "WAV_FILE_READ", 9: "WAV_EMPTY_FILE",
@@ -469,8 +470,10 @@ class Spatializer:
                 "true_peak": g(22),             # the true-peak measurement is on (set_true_peak)
                 "limiter": g(23),               # the limiter is on (set_limiter)
                 "limiter_latency": g(24),       # its latency in frames (0 while it is off)
-                "equalizer": g(25),             # presets of the equalizer stage (set_equalizer; 0: the stage is off)
-                "equalizer_filters": g(26)}     # the largest enabled-filter count among them
+                "equalizer": g(25),             # presets the equalizer stage holds (set_equalizer, set_equalizer_target; 0 and no fade: the stage is off)
+                "equalizer_filters": g(26),     # the largest enabled-filter count among them
+                "equalizer_fade": g(27),        # frames left of the running fade to a new target (set_equalizer_target); 0: none
+                "equalizer_pending": g(28)}     # 1: a target is published and has not begun
 
     def process_device(self, in_ptr: int, out_ptr: int, frames: int) -> None:
         _check(self._lib.aw_spatializer_process(self._h, ctypes.c_void_p(in_ptr), ctypes.c_void_p(out_ptr), frames))
@@ -661,6 +664,17 @@ class Spatializer:
         stream_definition: per stream the index of its preset, -1 = not equalized (None: every stream takes preset 0).  Allocates and
         uploads here, not on the process path, and starts the filter state from zero.  A preset that cannot be prepared raises
         ParametricEqualizerPreparationError, as ParametricEqualizerState does; the previous stage then stays."""
+        self._set_equalizer(self._lib.aw_spatializer_set_equalizer, definitions, stream_definition)
+
+    def set_equalizer_target(self, definitions, stream_definition=None) -> None:
+        """aw_spatializer_set_equalizer_target: publishes a target that the equalizer stage fades to over max(1, round(0.020 * rate))
+        frames, from the first frame of the next batch call on (or from where a running fade ends).  definitions as set_equalizer's;
+        stream_definition: per stream the index of its target, -1 = fade to unity, EQ_KEEP = the stream is not part of the change (None:
+        every stream takes definition 0).  A stage that is off counts as every stream at -1.  Allocates, uploads and synchronises here,
+        not on the process path; info()['equalizer_fade'] / ['equalizer_pending'] follow the fade.  A failing call changes nothing."""
+        self._set_equalizer(self._lib.aw_spatializer_set_equalizer_target, definitions, stream_definition)
+
+    def _set_equalizer(self, entry, definitions, stream_definition) -> None:
         from .eq import _DefHandle, _check_eq            # (eq.py imports this module)
         if definitions is None:
             definitions = []
@@ -678,8 +692,7 @@ class Spatializer:
             if any(h.h is None for h in handles):
                 raise ValueError("a definition is None (map the stream to -1 instead)")
             arr = (ctypes.c_void_p * max(len(handles), 1))(*[h.h for h in handles])
-            _check_eq(self._lib.aw_spatializer_set_equalizer(self._h, ctypes.cast(arr, _capi.c_void_pp) if handles else None, len(handles),
-                                                             None if sd is None else _i32p(sd)))
+            _check_eq(entry(self._h, ctypes.cast(arr, _capi.c_void_pp) if handles else None, len(handles), None if sd is None else _i32p(sd)))
         finally:
             for h in handles:
                 h.__exit__()

@@ -122,6 +122,31 @@ class MixedRateBatch:
             self.buckets[rate] = RateBucket(rate, ids, int(tr.shape[1]), sp, eq_state, folded.responseTaps if folded else 0, folded.tailBound if folded else 0.0,
                                             conv)
 
+    KEEP = "keep"          # retarget_equalizers: the stream is not part of the change
+
+    def retarget_equalizers(self, stream_equalizers) -> None:
+        """A target change of the buckets' equalizer stages (Spatializer.set_equalizer_target): one EqualizerDefinition (fade to it), None
+        (fade to unity) or MixedRateBatch.KEEP per stream, in the caller's order.  Every bucket fades over 20 ms at its own rate, from its
+        next call on; a bucket whose streams all keep is left alone, and a bucket without a stage starts at unity.  Not for a batch made
+        with equalizer=: its equalizer is folded or trails the spatializer as one state."""
+        if len(stream_equalizers) != sum(len(b.stream_ids) for b in self.buckets.values()):
+            raise ValueError("retarget_equalizers needs one entry per stream")
+        if any(b.equalizer is not None or b.eq_response_taps for b in self.buckets.values()):
+            raise ValueError("this batch was made with equalizer=: its equalizer cannot be retargeted per stream")
+        from .api import EQ_KEEP
+        for b in self.buckets.values():
+            presets, which = [], []
+            for i in b.stream_ids:
+                d = stream_equalizers[i]
+                if isinstance(d, str) and d == self.KEEP:
+                    which.append(EQ_KEEP)
+                    continue
+                if d is not None and d not in presets:
+                    presets.append(d)
+                which.append(-1 if d is None else presets.index(d))
+            if any(w != EQ_KEEP for w in which):
+                b.spatializer.set_equalizer_target(presets, which)
+
     def __del__(self):
         if sys.is_finalizing() or not getattr(getattr(self, "ctx", None), "_h", None):
             return

@@ -53,6 +53,44 @@ __global__ void aw_eq_stage_tail_kernel(EqStageParams sp, int n_streams) {
     if (i < n_streams * 2) eq_stage_sequential(sp, i >> 1, i & 1);
 }
 
+// A segment of a target change's fade (eq_stage.hpp): the stage kernel's block -> (stream, ear) map; a fading stream runs both of its
+// cascades on the chunk its threads hold and mixes before the one store, a stream that does not fade does what it does in
+// aw_eq_stage_kernel.  More LDS than the stage kernel (the old rendering's rows, 144 / 74 KB): one workgroup per CU for both ears, two for
+// one, and the launch bounds say so, which leaves each wave the registers of one / two waves per SIMD.
+template <int E>
+__global__ void __launch_bounds__(kEqThreads, E == 2 ? 1 : 2) aw_eq_stage_fade_kernel(EqFadeParams fp, const int *__restrict__ map,
+                                                                                      const int *__restrict__ to_map, const EqStagePreset *__restrict__ presets, const double *__restrict__ tables, int n_streams) {
+    extern __shared__ __align__(16) unsigned char eq_lds[];
+    ScanGpuCtx ctx{reinterpret_cast<cf *>(eq_lds)};
+    if constexpr (E == 2) eq_stage_fade_stream<ScanGpuCtx, 2>(ctx, fp, map, to_map, presets, tables, (long long)blockIdx.x, 0);
+    else {
+        const int b = (int)blockIdx.x, stream = (b >> 4) * 8 + (b & 7);
+        if (stream < n_streams) eq_stage_fade_stream<ScanGpuCtx, 1>(ctx, fp, map, to_map, presets, tables, (long long)stream, (b >> 3) & 1);
+    }
+}
+
+__global__ void aw_eq_stage_fade_tail_kernel(EqFadeParams fp, int n_streams) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < n_streams * 2) eq_stage_fade_sequential(fp, i >> 1, i & 1);
+}
+
+// The two ends of a fade, one workgroup per stream.  begin: the published entry becomes the stream's target and its second state starts
+// from zero.  end: a fading stream's target and second state become its active ones.
+__global__ void aw_eq_stage_turn_kernel(int begin, int *map, int *to_map, int *pending_map, double *z, double *z_to, int row_doubles) {
+    const long long s = blockIdx.x;
+    const int entry = begin ? pending_map[s] : to_map[s];
+    __syncthreads();
+    if (entry == kEqKeep) return;
+    for (int i = (int)threadIdx.x; i < row_doubles; i += (int)blockDim.x) {
+        if (begin) z_to[s * row_doubles + i] = 0.0;
+        else z[s * row_doubles + i] = z_to[s * row_doubles + i];
+    }
+    if (threadIdx.x == 0) {
+        if (begin) { to_map[s] = entry; pending_map[s] = kEqKeep; }
+        else { map[s] = entry; to_map[s] = kEqKeep; }
+    }
+}
+
 __global__ void aw_eq_blend_kernel(const float *__restrict__ old_seg, const float *__restrict__ new_seg, float *__restrict__ out,
                                    long long seg_frames, long long out_stride, long long t_frame, long long length) {
 #pragma clang fp contract(off)
@@ -82,6 +120,8 @@ hipError_t prepare_eq_kernels() {
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_eq_cascade_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, eq_lds_bytes(1));
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_eq_stage_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, eq_lds_bytes(2));
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_eq_stage_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, eq_lds_bytes(1));
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_eq_stage_fade_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, eq_fade_lds_bytes(2));
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&aw_eq_stage_fade_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, eq_fade_lds_bytes(1));
     return e;
 }
 
@@ -122,6 +162,31 @@ hipError_t launch_eq_stage_tail(const EqStageParams &p, int n_streams, hipStream
     if (n_streams <= 0 || p.frames <= 0) return hipSuccess;
     const int n = n_streams * 2;
     hipLaunchKernelGGL(aw_eq_stage_tail_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, p, n_streams);
+    return hipGetLastError();
+}
+
+// launch_eq_stage's policy and grids
+hipError_t launch_eq_stage_fade(const EqFadeParams &p, int n_streams, hipStream_t stream) {
+    if (n_streams <= 0 || p.s.frames <= 0) return hipSuccess;
+    const int cus = p.s.cus > 0 ? p.s.cus : 256, force = p.s.ear_split;
+    const bool split = force >= 0 ? force != 0 : 2 * n_streams <= 3 * cus;
+    if (split)
+        hipLaunchKernelGGL(aw_eq_stage_fade_kernel<1>, dim3((unsigned)((n_streams + 7) / 8) * 16), dim3(kEqThreads), eq_fade_lds_bytes(1), stream, p, p.s.map, p.to_map, p.s.presets, p.s.tables, n_streams);
+    else
+        hipLaunchKernelGGL(aw_eq_stage_fade_kernel<2>, dim3((unsigned)n_streams), dim3(kEqThreads), eq_fade_lds_bytes(2), stream, p, p.s.map, p.to_map, p.s.presets, p.s.tables, n_streams);
+    return hipGetLastError();
+}
+
+hipError_t launch_eq_stage_fade_tail(const EqFadeParams &p, int n_streams, hipStream_t stream) {
+    if (n_streams <= 0 || p.s.frames <= 0) return hipSuccess;
+    const int n = n_streams * 2;
+    hipLaunchKernelGGL(aw_eq_stage_fade_tail_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, p, n_streams);
+    return hipGetLastError();
+}
+
+hipError_t launch_eq_stage_turn(bool begin, int *map, int *to_map, int *pending_map, double *z, double *z_to, int kmax, int n_streams, hipStream_t stream) {
+    if (n_streams <= 0) return hipSuccess;
+    hipLaunchKernelGGL(aw_eq_stage_turn_kernel, dim3((unsigned)n_streams), dim3(64), 0, stream, begin ? 1 : 0, map, to_map, pending_map, z, z_to, kmax * 4);
     return hipGetLastError();
 }
 

@@ -16,6 +16,12 @@ hipError_t launch_eq_sequential(const EqParams &p, int n_streams, hipStream_t st
 // p.y.  launch_eq_stage: p.frames is a multiple of kEqChunk; launch_eq_stage_tail: the rest, and the whole of shorter calls.
 hipError_t launch_eq_stage(const EqStageParams &p, int n_streams, hipStream_t stream);
 hipError_t launch_eq_stage_tail(const EqStageParams &p, int n_streams, hipStream_t stream);
+// A segment of a target change's fade (eq_stage.hpp), in place on p.s.y: the fade's forms of the two launchers above (a stream whose
+// target entry is kEqKeep does what they do).  launch_eq_stage_turn: the fade's ends — begin: pending_map -> to_map with a zeroed second
+// state; end: to_map -> map with the second state copied over the first — for the streams whose entry is not kEqKeep.
+hipError_t launch_eq_stage_fade(const EqFadeParams &p, int n_streams, hipStream_t stream);
+hipError_t launch_eq_stage_fade_tail(const EqFadeParams &p, int n_streams, hipStream_t stream);
+hipError_t launch_eq_stage_turn(bool begin, int *map, int *to_map, int *pending_map, double *z, double *z_to, int kmax, int n_streams, hipStream_t stream);
 // Crossfade of two rendered segments (ParametricEqualizerProcessor.swift:296-304):
 // out[s][f][e] = Float(Double(old) * (1 - g) + Double(new) * g),  g = (t_frame + f + 1) / length.
 // old_seg/new_seg: [stream][seg_frames][2]; out: [stream][out_stride][2].

@@ -18,4 +18,12 @@ struct EqStagePreset {
 };
 static_assert(sizeof(EqStagePreset) == 32, "EqStagePreset");
 
+// A target change (aw_spatializer_set_equalizer_target) fades over T = max(1, round(0.020 * rate)) frames on ONE clock per handle.  While it
+// runs, a stream whose target entry is not kEqKeep is a fading stream: its active preset goes on from its state (-1: the sample itself), its
+// target preset starts from a zeroed state of its own in a second bank (-1: the sample itself), both renderings are rounded to float32 and
+// frame i of the fade (counted from 1) is Float(fma(Double(old), 1 - g, Double(new) * g)), g = i / T: aw_eq_blend_kernel's arithmetic.  When the clock
+// reaches T the target entry and the second bank's rows become the stream's active ones.  The presets of both sides lie in the stage's one
+// table: the setter rebuilds it from the presets still in use and the new ones.
+constexpr int kEqKeep = -2;   // AW_EQ_KEEP: the stream is not part of the change
+
 }  // namespace awk

@@ -48,6 +48,16 @@ struct Equalizer {                            // Equalizer{{n_streams}, n_preset
     size_t total = c.off;
 };
 
+struct EqualizerFade {                        // EqualizerFade{{n_streams}, kmax}; rules: device/eq_stage.hpp (a target change); kmax: Equalizer's
+    Cursor c;
+    size_t kmax;
+    Field<double> state_to = c.take<double>(kmax * 4);                        // the second bank: the state of the presets faded to, rows as Equalizer::state
+    size_t reset_bytes = c.off;                                               // a reset zeroes it with the first bank; the maps stay
+    Field<int32_t> to_map = c.take<int32_t>();                                // the running fade: the preset faded to, -1 = unity, kEqKeep = not fading
+    Field<int32_t> pending_map = c.take<int32_t>();                           // the published target that has not begun, likewise
+    size_t total = c.off;
+};
+
 struct Levels {                               // Levels{{n_streams}}; rules: device/levels.hpp
     Cursor c;
     Field<awl::Record> records = c.take<awl::Record>();

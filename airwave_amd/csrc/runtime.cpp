@@ -598,8 +598,10 @@ int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what) {
         case 22: return sp->tp.on ? 1 : 0;        // the true-peak measurement is on (aw_spatializer_set_true_peak)
         case 23: return sp->lim.on ? 1 : 0;       // the limiter is on (aw_spatializer_set_limiter)
         case 24: return sp->lim.on ? awlim::delay(sp->lim.attack) : 0;      // its latency in frames
-        case 25: return sp->eq.n_presets;         // presets of the equalizer stage (aw_spatializer_set_equalizer); 0: the stage is off
+        case 25: return sp->eq.n_presets;         // presets the equalizer stage holds (aw_spatializer_set_equalizer / _set_equalizer_target); 0 and no fade: the stage is off
         case 26: return sp->eq.kmax;              // the largest enabled-filter count among them
+        case 27: return sp->eq.clock.fading ? sp->eq.clock.length - sp->eq.clock.frame : 0;      // frames left of the running fade (aw_spatializer_set_equalizer_target)
+        case 28: return sp->eq.clock.pending ? 1 : 0;                                            // a target is published and has not begun
         default: return -1;
     }
 }
@@ -1155,34 +1157,83 @@ static awst::Equalizer eq_layout(const aw_spatializer *sp) {
     return awst::Equalizer{{(size_t)sp->n_streams}, (size_t)sp->eq.n_presets, (size_t)sp->eq.kmax, sp->eq.table_doubles};
 }
 
+static awst::EqualizerFade eq_fade_layout(const aw_spatializer *sp) { return awst::EqualizerFade{{(size_t)sp->n_streams}, (size_t)sp->eq.kmax}; }
+
+// every filter state: the active one, which a fade fades from, and the one it fades to (applyPendingReset :341-352); the setting, the
+// clock and a published target stay
 static aw_status eq_reset(aw_spatializer *sp) {
-    const size_t bytes = sp->eq.d ? eq_layout(sp).reset_bytes : 0;
-    return bytes ? stage_zero(sp, sp->eq.d.get(), bytes) : AW_OK;
+    const size_t bytes = sp->eq.d ? eq_layout(sp).reset_bytes : 0, to_bytes = sp->eq.fade ? eq_fade_layout(sp).reset_bytes : 0;
+    aw_status st = bytes ? stage_zero(sp, sp->eq.d.get(), bytes) : AW_OK;
+    if (st == AW_OK && to_bytes) st = stage_zero(sp, sp->eq.fade.get(), to_bytes);
+    return st;
+}
+
+// once per call that runs the stage, before its first launch: where the clock cuts it.  batch_end moves the clock, once per call
+// however many chunks of streams ran the cuts.
+static void eq_begin_call(aw_spatializer *sp, int64_t frames) {
+    sp->eq.plan = awef::plan(sp->eq.clock, frames);
+    sp->eq.planned = true;
+}
+static void eq_end_call(aw_spatializer *sp) {
+    if (!sp->eq.planned) return;
+    sp->eq.planned = false;
+    aw_spatializer::Equalizer &q = sp->eq;
+    for (int i = 0; i < q.plan.n; ++i) {
+        const awef::Segment &g = q.plan.seg[i];
+        for (size_t s = 0; g.begins && s < q.pending_map.size(); ++s)
+            if (q.pending_map[s] != awk::kEqKeep) { q.to_map[s] = q.pending_map[s]; q.pending_map[s] = awk::kEqKeep; }
+        for (size_t s = 0; g.ends && s < q.to_map.size(); ++s)
+            if (q.to_map[s] != awk::kEqKeep) { q.map[s] = q.to_map[s]; q.to_map[s] = awk::kEqKeep; }
+    }
+    q.clock = q.plan.after;
 }
 
 // The float32 output y of the streams [s0, s0 + ns) of a call (dense: `frames` apart), in place, before any meter: the chunk-parallel
 // body over the whole chunks and the sequential tail, the split aw_eq_state_process makes.  A workgroup owns a stream and the state is
-// per stream, so chunks of streams are independent.
+// per stream, so chunks of streams are independent.  Where the call's plan cuts it (a fade begins, runs or ends) each piece runs so, as a
+// call of its own, the fading pieces through the fade kernels; the two ends of a fade are queued between the pieces like everything else.
 static aw_status eq_run(aw_spatializer *sp, float *y, int64_t s0, int ns, int64_t frames) {
     SpStageTimer tm(sp);
     const awst::Equalizer L = eq_layout(sp);
     unsigned char *const d = sp->eq.d.get();
-    awk::EqStageParams p{};
+    awk::EqFadeParams f{};
+    awk::EqStageParams &p = f.s;
     p.z = L.state.at(d, (size_t)s0); p.map = L.map.at(d, (size_t)s0); p.presets = L.presets.at(d); p.tables = L.tables.at(d);
     p.stride_frames = frames; p.kmax = sp->eq.kmax;
     p.cus = sp->ctx->cfg.cus; p.ear_split = sp->ctx->cfg.eq_ear_split;
-    const int64_t body = frames - frames % awk::kEqChunk;
-    if (body > 0) {
-        if (sp->profiling) tm.begin();
-        p.y = y; p.frames = body;
-        AW_HIP_TRY(awk::launch_eq_stage(p, ns, sp->ctx->stream));
-        if (sp->profiling) tm.end("aw_eq_stage_kernel");
+    int *to_map = nullptr, *pending_map = nullptr;
+    if (sp->eq.fade) {
+        const awst::EqualizerFade F = eq_fade_layout(sp);
+        unsigned char *const df = sp->eq.fade.get();
+        f.z_to = F.state_to.at(df, (size_t)s0); f.to_map = to_map = F.to_map.at(df, (size_t)s0); pending_map = F.pending_map.at(df, (size_t)s0);
+        f.length = sp->eq.clock.length;
     }
-    if (frames > body) {
-        if (sp->profiling) tm.begin();
-        p.y = y + body * 2; p.frames = frames - body;
-        AW_HIP_TRY(awk::launch_eq_stage_tail(p, ns, sp->ctx->stream));
-        if (sp->profiling) tm.end("aw_eq_stage_tail_kernel");
+    const awef::Plan &plan = sp->eq.plan;
+    for (int i = 0; i < plan.n; ++i) {
+        const awef::Segment &g = plan.seg[i];
+        const int64_t body = g.frames - g.frames % awk::kEqChunk;
+        if (g.begins) {
+            if (sp->profiling) tm.begin();
+            AW_HIP_TRY(awk::launch_eq_stage_turn(true, const_cast<int *>(p.map), to_map, pending_map, p.z, f.z_to, p.kmax, ns, sp->ctx->stream));
+            if (sp->profiling) tm.end("aw_eq_stage_turn_kernel");
+        }
+        if (body > 0) {
+            if (sp->profiling) tm.begin();
+            p.y = y + g.first * 2; p.frames = body; f.t0 = g.t0;
+            AW_HIP_TRY(g.fade ? awk::launch_eq_stage_fade(f, ns, sp->ctx->stream) : awk::launch_eq_stage(p, ns, sp->ctx->stream));
+            if (sp->profiling) tm.end(g.fade ? "aw_eq_stage_fade_kernel" : "aw_eq_stage_kernel");
+        }
+        if (g.frames > body) {
+            if (sp->profiling) tm.begin();
+            p.y = y + (g.first + body) * 2; p.frames = g.frames - body; f.t0 = g.t0 + body;
+            AW_HIP_TRY(g.fade ? awk::launch_eq_stage_fade_tail(f, ns, sp->ctx->stream) : awk::launch_eq_stage_tail(p, ns, sp->ctx->stream));
+            if (sp->profiling) tm.end(g.fade ? "aw_eq_stage_fade_tail_kernel" : "aw_eq_stage_tail_kernel");
+        }
+        if (g.ends) {
+            if (sp->profiling) tm.begin();
+            AW_HIP_TRY(awk::launch_eq_stage_turn(false, const_cast<int *>(p.map), to_map, pending_map, p.z, f.z_to, p.kmax, ns, sp->ctx->stream));
+            if (sp->profiling) tm.end("aw_eq_stage_turn_kernel");
+        }
     }
     return AW_OK;
 }
@@ -1457,6 +1508,7 @@ static aw_status batch_begin(aw_spatializer *sp, BatchCall *call, unsigned long 
     call->clip = clip;
     call->metered = metered;
     if (metered) {
+        if (sp->eq.d) eq_begin_call(sp, call->frames);
         aw_status st = lv_begin_call(sp, call->frames, true);
         if (st != AW_OK) return st;
         call->loud0 = ld_begin_call(sp, call->frames);
@@ -1470,6 +1522,7 @@ static aw_status batch_begin(aw_spatializer *sp, BatchCall *call, unsigned long 
 // every chunk's kernels are queued: the history they wrote is the next call's
 static void batch_end(aw_spatializer *sp) {
     sp->hist_cur ^= 1;
+    eq_end_call(sp);
     sp->tp.hist.end_call();
     sp->lim.hist.end_call();
 }
@@ -1487,7 +1540,7 @@ static aw_status batch_chunk(aw_spatializer *sp, const BatchCall &call, int64_t 
     if (st == AW_OK && lim) st = grow_buf(sp, &sp->lim.d_y, (size_t)ns * call.out_ps);      // (reserved for: nothing happens)
     float *y = lim ? sp->lim.d_y.get() : dst;
     if (st == AW_OK) st = sp_run_streams(sp, call.lw, (int)s0, ns, x, y, call.frames);
-    if (st == AW_OK && call.metered && sp->eq.n_presets) st = eq_run(sp, y, s0, ns, call.frames);                 // (every later stage sees the equalized y)
+    if (st == AW_OK && call.metered && sp->eq.d) st = eq_run(sp, y, s0, ns, call.frames);                        // (every later stage sees the equalized y)
     if (st == AW_OK && call.metered && sp->ld.on) st = ld_measure(sp, y, s0, ns, call.frames, call.loud0);      // (before the gain)
     if (st == AW_OK && call.metered && tp_runs(sp)) st = tp_measure(sp, y, s0, ns, call.frames);                   // (the gain may read its result)
     if (st == AW_OK && call.metered) st = lv_after_run(sp, y, s0, ns, call.frames, !call.enc && !lim);
@@ -1501,8 +1554,9 @@ static aw_status batch_chunk(aw_spatializer *sp, const BatchCall &call, int64_t 
 static aw_status batch_run_pinned(aw_spatializer *sp, int64_t frames, bool metered, uint64_t *pos0) {
     const LwCallPlan lw = sp_begin_call(sp, frames, pos0);
     aw_status st = metered ? lv_begin_call(sp, frames, false) : AW_OK;
+    if (metered && sp->eq.d) eq_begin_call(sp, frames);
     if (st == AW_OK) st = sp_run_streams(sp, lw, 0, 1, sp->h_pin_in.get(), sp->h_pin_out.get(), frames);
-    if (st == AW_OK && metered && sp->eq.n_presets) st = eq_run(sp, sp->h_pin_out.get(), 0, 1, frames);      // in place over PCIe, like the kernels in front of it
+    if (st == AW_OK && metered && sp->eq.d) st = eq_run(sp, sp->h_pin_out.get(), 0, 1, frames);      // in place over PCIe, like the kernels in front of it
     if (st == AW_OK && metered && sp->ld.on)             // the loudness kernels read the page-locked output as the convolution kernels wrote it
         st = ld_measure(sp, sp->h_pin_out.get(), 0, 1, frames, ld_begin_call(sp, frames));
     const bool tp = metered && tp_runs(sp);
@@ -1885,50 +1939,52 @@ aw_status aw_spatializer_set_loudness(aw_spatializer *sp, int32_t on, double max
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 
-// Checks and the presets' tables first (a refusal leaves the stage as it was), then the one allocation and the upload (here, never on
-// the process path).  Every call that installs presets starts the filter state from zero.
-aw_status aw_spatializer_set_equalizer(aw_spatializer *sp, const aw_eq_definition *const *definitions, int32_t n_definitions,
-                                       const int32_t *stream_definition) try {
+// The checks the two equalizer setters share, answered in this order; lowest: the smallest map entry allowed (-1, or AW_EQ_KEEP)
+static aw_status eq_setter_args(const aw_spatializer *sp, const aw_eq_definition *const *definitions, int32_t n_definitions, const int32_t *stream_definition,
+                                int32_t lowest, bool check_without_definitions) {
     if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
     if (n_definitions < 0) return fail(AW_ERR_INVALID_ARGUMENT, "n_definitions must be >= 0");
     if (n_definitions > 0 && !definitions) return fail(AW_ERR_INVALID_ARGUMENT, "definitions is NULL");
     for (int32_t i = 0; i < n_definitions; ++i)
         if (!definitions[i]) return fail(AW_ERR_INVALID_ARGUMENT, "definition " + std::to_string(i) + " is NULL");
-    for (int s = 0; stream_definition && n_definitions > 0 && s < sp->n_streams; ++s)
-        if (stream_definition[s] < -1 || stream_definition[s] >= n_definitions)
-            return fail(AW_ERR_INVALID_ARGUMENT, "stream_definition[" + std::to_string(s) + "] = " + std::to_string(stream_definition[s]) + " is outside [-1, n_definitions)");
-    std::vector<awh::EqPrepared> prep((size_t)n_definitions);
-    int kmax = 0;
-    size_t table_doubles = 0;
+    for (int s = 0; stream_definition && (n_definitions > 0 || check_without_definitions) && s < sp->n_streams; ++s)
+        if (stream_definition[s] < lowest || stream_definition[s] >= n_definitions)
+            return fail(AW_ERR_INVALID_ARGUMENT, "stream_definition[" + std::to_string(s) + "] = " + std::to_string(stream_definition[s]) + " is outside [" +
+                                                     std::to_string(lowest) + ", n_definitions)");
+    return AW_OK;
+}
+
+static aw_status eq_prepare_all(const aw_spatializer *sp, const aw_eq_definition *const *definitions, int32_t n_definitions, std::vector<awh::EqPrepared> *prep) {
+    prep->resize((size_t)n_definitions);
     for (int32_t i = 0; i < n_definitions; ++i) {
-        const aw_status st = awr::eq_prepare_checked(&definitions[i]->def, sp->sample_rate, prep[(size_t)i]);
+        const aw_status st = awr::eq_prepare_checked(&definitions[i]->def, sp->sample_rate, (*prep)[(size_t)i]);
         if (st != AW_OK) {
             awr::set_error(std::string(aw_last_error_message()) + " (definition " + std::to_string(i) + ")");
             return st;
         }
-        kmax = std::max(kmax, prep[(size_t)i].n_filters);
-        table_doubles += prep[(size_t)i].tab.size() + prep[(size_t)i].plane.size();
     }
-    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
-    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
-    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));                // whatever still reads the old state, tables or image
-    if (n_definitions == 0) {
-        sp->eq.n_presets = sp->eq.kmax = 0; sp->eq.table_doubles = 0;
-        (void)sp->eq.d.reset();
-        sp->eq.image.clear();
-        return AW_OK;
+    return AW_OK;
+}
+
+// The stage's one allocation for these presets and this map, as awst::Equalizer lays it out: the state zeroed, the map, the headers and every
+// preset's tab and plane queued for upload from *image (which stays until the copy has read it).
+struct EqBuilt { awr::Buf<unsigned char> d; std::vector<unsigned char> image; int kmax = 0; size_t table_doubles = 0; };
+static aw_status eq_build(aw_spatializer *sp, const std::vector<awh::EqPrepared> &prep, const std::vector<int32_t> &stream_map, EqBuilt *b) {
+    for (const awh::EqPrepared &q : prep) {
+        b->kmax = std::max(b->kmax, q.n_filters);
+        b->table_doubles += q.tab.size() + q.plane.size();
     }
-    const awst::Equalizer L{{(size_t)sp->n_streams}, (size_t)n_definitions, (size_t)kmax, table_doubles};
+    const awst::Equalizer L{{(size_t)sp->n_streams}, prep.size(), (size_t)b->kmax, b->table_doubles};
     // what lies behind the state, as the layout states it: the map, the headers, then every preset's tab and plane
-    std::vector<unsigned char> image(L.total - L.map.off, 0);
-    auto at = [&](size_t off) { return image.data() + (off - L.map.off); };          // (every field starts on a multiple of 8 bytes but the map's end)
+    b->image.assign(L.total - L.map.off, 0);
+    auto at = [&](size_t off) { return b->image.data() + (off - L.map.off); };       // (every field starts on a multiple of 8 bytes but the map's end)
     int32_t *const map = reinterpret_cast<int32_t *>(at(L.map.off));
     awk::EqStagePreset *const headers = reinterpret_cast<awk::EqStagePreset *>(at(L.presets.off));
     double *const tables = reinterpret_cast<double *>(at(L.tables.off));
-    for (int s = 0; s < sp->n_streams; ++s) map[s] = stream_definition ? stream_definition[s] : 0;
+    for (int s = 0; s < sp->n_streams; ++s) map[s] = stream_map[(size_t)s];
     long long off = 0;
-    for (int32_t i = 0; i < n_definitions; ++i) {
-        const awh::EqPrepared &q = prep[(size_t)i];
+    for (size_t i = 0; i < prep.size(); ++i) {
+        const awh::EqPrepared &q = prep[i];
         awk::EqStagePreset &h = headers[i];
         h.preamp = q.preamp; h.n_filters = q.n_filters; h.reserved = 0;
         h.tab_off = off; h.plane_off = off + (long long)q.tab.size();
@@ -1936,13 +1992,106 @@ aw_status aw_spatializer_set_equalizer(aw_spatializer *sp, const aw_eq_definitio
         if (!q.plane.empty()) std::memcpy(tables + h.plane_off, q.plane.data(), q.plane.size() * sizeof(double));
         off += (long long)(q.tab.size() + q.plane.size());
     }
-    awr::Buf<unsigned char> d;
-    const aw_status st = stage_alloc(sp, &d, L.total, L.reset_bytes);
+    const aw_status st = stage_alloc(sp, &b->d, L.total, L.reset_bytes);
     if (st != AW_OK) return st;
-    AW_HIP_TRY(hipMemcpyAsync(d.get() + L.map.off, image.data(), image.size(), hipMemcpyHostToDevice, sp->ctx->stream));
-    sp->eq.d = std::move(d);
-    sp->eq.image = std::move(image);                                  // (the copy may still read it: it stays until the next setter call has synchronised)
-    sp->eq.n_presets = n_definitions; sp->eq.kmax = kmax; sp->eq.table_doubles = table_doubles;
+    AW_HIP_TRY(hipMemcpyAsync(b->d.get() + L.map.off, b->image.data(), b->image.size(), hipMemcpyHostToDevice, sp->ctx->stream));
+    return AW_OK;
+}
+
+// Checks and the presets' tables first (a refusal leaves the stage as it was), then the one allocation and the upload (here, never on
+// the process path).  Every call that installs presets starts the filter state from zero, and ends a running fade and a published target.
+aw_status aw_spatializer_set_equalizer(aw_spatializer *sp, const aw_eq_definition *const *definitions, int32_t n_definitions,
+                                       const int32_t *stream_definition) try {
+    aw_status st = eq_setter_args(sp, definitions, n_definitions, stream_definition, -1, false);
+    if (st != AW_OK) return st;
+    std::vector<awh::EqPrepared> prep;
+    if ((st = eq_prepare_all(sp, definitions, n_definitions, &prep)) != AW_OK) return st;
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));                // whatever still reads the old state, tables or image
+    aw_spatializer::Equalizer &q = sp->eq;
+    EqBuilt b;
+    std::vector<int32_t> map((size_t)sp->n_streams, 0);
+    if (n_definitions > 0) {
+        for (int s = 0; stream_definition && s < sp->n_streams; ++s) map[(size_t)s] = stream_definition[s];
+        if ((st = eq_build(sp, prep, map, &b)) != AW_OK) return st;
+    }
+    q.d = std::move(b.d);                                             // (no definitions: the stage is off)
+    q.image = std::move(b.image);                                     // (the copy may still read it: it stays until the next setter call has synchronised)
+    q.n_presets = n_definitions; q.kmax = b.kmax; q.table_doubles = b.table_doubles;
+    (void)q.fade.reset();
+    q.clock = awef::Clock{}; q.planned = false;
+    q.prepared = std::move(prep);
+    q.map = std::move(map);
+    q.to_map.clear(); q.pending_map.clear();
+    if (n_definitions == 0) q.map.clear();
+    return AW_OK;
+} AW_NOEXCEPT_TAIL
+
+// Publishes a target; rules: device/eq_stage.hpp, host/eq_fade_plan.hpp.  Like an install it checks and prepares first and allocates, uploads
+// and synchronises here, never on the process path: the stage's allocation is made anew for the presets still in use (active, faded to,
+// published) and the new ones, the states are carried over, and the fade's record is made beside it.  The new entries replace the
+// published target's, stream by stream; AW_EQ_KEEP leaves it.
+aw_status aw_spatializer_set_equalizer_target(aw_spatializer *sp, const aw_eq_definition *const *definitions, int32_t n_definitions,
+                                              const int32_t *stream_definition) try {
+    static_assert(AW_EQ_KEEP == awk::kEqKeep, "AW_EQ_KEEP");
+    aw_status st = eq_setter_args(sp, definitions, n_definitions, stream_definition, AW_EQ_KEEP, true);
+    if (st != AW_OK) return st;
+    if (!stream_definition && n_definitions == 0) return fail(AW_ERR_INVALID_ARGUMENT, "stream_definition is NULL (every stream takes definition 0) and there is no definition");
+    std::vector<awh::EqPrepared> fresh;
+    if ((st = eq_prepare_all(sp, definitions, n_definitions, &fresh)) != AW_OK) return st;
+    AW_HIP_TRY(hipSetDevice(sp->ctx->device));
+    std::lock_guard<std::mutex> lk(sp->ctx->launch_mu);
+    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));                // whatever still reads the old records
+    aw_spatializer::Equalizer &q = sp->eq;
+    const size_t n = (size_t)sp->n_streams, n_old = q.prepared.size();
+    // a stage that is off counts as every stream at -1 (the reference's processor starts at unity)
+    std::vector<int32_t> map = q.d ? q.map : std::vector<int32_t>(n, -1);
+    std::vector<int32_t> to_map = q.fade ? q.to_map : std::vector<int32_t>(n, awk::kEqKeep);
+    std::vector<int32_t> pending_map = q.fade ? q.pending_map : std::vector<int32_t>(n, awk::kEqKeep);
+    bool published = q.clock.pending;
+    for (size_t s = 0; s < n; ++s) {                                  // (the new presets follow the old ones)
+        const int32_t e = stream_definition ? stream_definition[s] : 0;
+        if (e == AW_EQ_KEEP) continue;
+        pending_map[s] = e < 0 ? -1 : (int32_t)n_old + e;
+        published = true;
+    }
+    // the presets some map still names, in their old order; the maps name them by their new index
+    std::vector<int32_t> index(n_old + fresh.size(), -1);
+    for (const std::vector<int32_t> *m : {&map, &to_map, &pending_map})
+        for (int32_t e : *m) if (e >= 0) index[(size_t)e] = 0;
+    std::vector<awh::EqPrepared> prepared;
+    for (size_t i = 0; i < index.size(); ++i)
+        if (index[i] == 0) {
+            index[i] = (int32_t)prepared.size();
+            prepared.push_back(i < n_old ? q.prepared[i] : std::move(fresh[i - n_old]));
+        }
+    for (std::vector<int32_t> *m : {&map, &to_map, &pending_map})
+        for (int32_t &e : *m) if (e >= 0) e = index[(size_t)e];
+    EqBuilt b;
+    if ((st = eq_build(sp, prepared, map, &b)) != AW_OK) return st;
+    const awst::Equalizer L{{n}, prepared.size(), (size_t)b.kmax, b.table_doubles};
+    const awst::EqualizerFade F{{n}, (size_t)b.kmax};
+    awr::Buf<unsigned char> fade;
+    if ((st = stage_alloc(sp, &fade, F.total, F.reset_bytes)) != AW_OK) return st;
+    // the states go on: a stream's rows are the first of its kmax, before and after
+    const size_t row = (size_t)std::min(q.kmax, b.kmax) * 4 * sizeof(double);
+    if (q.d && row)
+        AW_HIP_TRY(hipMemcpy2DAsync(L.state.at(b.d.get()), (size_t)b.kmax * 32, eq_layout(sp).state.at(q.d.get()), (size_t)q.kmax * 32, row, n, hipMemcpyDeviceToDevice, sp->ctx->stream));
+    if (q.fade && row)
+        AW_HIP_TRY(hipMemcpy2DAsync(F.state_to.at(fade.get()), (size_t)b.kmax * 32, eq_fade_layout(sp).state_to.at(q.fade.get()), (size_t)q.kmax * 32, row, n, hipMemcpyDeviceToDevice, sp->ctx->stream));
+    AW_HIP_TRY(hipMemcpyAsync(F.to_map.at(fade.get()), to_map.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, sp->ctx->stream));
+    AW_HIP_TRY(hipMemcpyAsync(F.pending_map.at(fade.get()), pending_map.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, sp->ctx->stream));
+    AW_HIP_TRY(hipStreamSynchronize(sp->ctx->stream));                // (the copies read the old records and the vectors here)
+    q.d = std::move(b.d);
+    q.image = std::move(b.image);
+    q.fade = std::move(fade);
+    q.n_presets = (int)prepared.size(); q.kmax = b.kmax; q.table_doubles = b.table_doubles;
+    q.prepared = std::move(prepared);
+    q.map = std::move(map); q.to_map = std::move(to_map); q.pending_map = std::move(pending_map);
+    q.clock.length = awef::fade_length(sp->sample_rate);
+    q.clock.pending = published;
+    q.planned = false;
     return AW_OK;
 } AW_NOEXCEPT_TAIL
 

@@ -13,6 +13,7 @@
 #include "device/kernels.hpp"
 #include "host/device_buf.hpp"
 #include "host/eq.hpp"
+#include "host/eq_fade_plan.hpp"
 #include "host/stage_records.hpp"
 
 namespace awr {
@@ -134,10 +135,18 @@ struct aw_spatializer {
         int cur = 0; bool ran = false;                // ran: this call queued the stage's kernel, so its history slot is the next call's
         void end_call(bool queued = true) { if (ran && queued) cur ^= 1; ran = false; }
     };
-    // aw_spatializer_set_equalizer: the one stage in front of the meters; rules: device/eq_stage.hpp.  n_presets > 0: the stage is on
+    // aw_spatializer_set_equalizer / _set_equalizer_target: the one stage in front of the meters; rules: device/eq_stage.hpp.  d: the stage is on
     struct Equalizer : Stage {
         int n_presets = 0, kmax = 0; size_t table_doubles = 0;
         std::vector<unsigned char> image;             // what the setter uploads behind the state (map, headers, tables): kept while the copy may read it
+        // target changes (aw_spatializer_set_equalizer_target).  The presets the stage holds, as prepared: the target setter rebuilds the
+        // stage's one table from those still in use and the new ones.  The three maps are the host's copies of the device's, moved as the
+        // clock moves: once per call, by batch_end.
+        std::vector<awh::EqPrepared> prepared;
+        std::vector<int32_t> map, to_map, pending_map;
+        awr::Buf<unsigned char> fade;                 // awst::EqualizerFade, made by the first target; an install drops it
+        awef::Clock clock;
+        awef::Plan plan; bool planned = false;        // the running call's cuts (batch_begin); planned: batch_end moves the clock by them
     } eq;
     struct Levels : Stage {                           // aw_spatializer_set_metering / _set_gain (either makes d); rules: device/levels.hpp
         bool metering = false;

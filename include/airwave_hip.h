@@ -428,7 +428,9 @@ AW_API int32_t aw_spatializer_channel_count(const aw_spatializer *sp);
  * 19 the level meter is on (aw_spatializer_set_metering), 20 the aw_gain_mode of the batch entries (aw_spatializer_set_gain),
  * 21 the loudness measurement is on (aw_spatializer_set_loudness), 22 the true-peak measurement is on (aw_spatializer_set_true_peak),
  * 23 the limiter is on (aw_spatializer_set_limiter), 24 its latency D in frames (0 while it is off),
- * 25 presets of the equalizer stage (aw_spatializer_set_equalizer; 0: the stage is off), 26 the largest enabled-filter count among them. */
+ * 25 presets the equalizer stage holds (aw_spatializer_set_equalizer, aw_spatializer_set_equalizer_target; 0 and no fade: the stage is off),
+ * 26 the largest enabled-filter count among them, 27 frames left of the running fade to a new target (0: none), 28 a target is published
+ * and has not begun (1 / 0). */
 AW_API int64_t aw_spatializer_info(const aw_spatializer *sp, int32_t what);
 /* Average device time of the dominant kernel over the launches since the last call (HIP events
  * on the context stream); used for bench.py's roofline object.  Returns launches counted. */
@@ -618,8 +620,9 @@ AW_API aw_status aw_eq_fold_hrir(const aw_eq_definition *definition_or_null, dou
  *  - with the stage off a call queues what it queued before this entry existed, and every output bit is the same.
  *  - chunking a batch by streams (AW_HOST_CHUNK_MB), sample formats, pinned or pageable buffers and sharding over handles change no bit;
  *    splitting calls in time moves the kernel's chunk boundaries and changes the last bit of some samples (reassociation in Float64).
- *  - state: aw_spatializer_reset zeroes the filter state; every call that installs presets does too.  There is no crossfade between two
- *    settings: a target that changes while audio plays is aw_eq's business (aw_eq_set_target, below).
+ *  - state: aw_spatializer_reset zeroes the filter state; every call that installs presets does too.  An install never crossfades: a
+ *    setting that changes while audio plays is published with aw_spatializer_set_equalizer_target (next entry), which fades to it over
+ *    20 ms as the reference does; the plug-in path keeps aw_eq for that (aw_eq_set_target, below).
  *  - the definitions are read during the call and not kept.  The call makes the stage's one device allocation (state, map, tables); no
  *    batch entry allocates for it afterwards, and it needs no staging.  Do not call it while a process call on the same handle is running.
  * Errors: a preset that cannot be prepared returns what aw_eq_state_create returns for it (AW_ERR_EQ_*; aw_last_eq_filter_error for a bad
@@ -628,6 +631,38 @@ AW_API aw_status aw_eq_fold_hrir(const aw_eq_definition *definition_or_null, dou
  * the previous stage as it was. */
 AW_API aw_status aw_spatializer_set_equalizer(aw_spatializer *sp, const aw_eq_definition *const *definitions, int32_t n_definitions,
                                               const int32_t *stream_definition);
+
+/* A target change of the batch entries' equalizer (ParametricEqualizerProcessor.setTarget, :226-228, :253-374): publishes a target that
+ * the stage fades to over T = max(1, round(0.020 * sample rate)) frames, half away from zero, at the spatializer's rate.  Not an install:
+ * aw_spatializer_set_equalizer keeps its meaning (install, zero the state, no fade) and also ends a running fade and a published target.
+ * stream_definition[s]: p in [0, n_definitions) — stream s fades to a freshly zeroed state of definitions[p], also when that definition is
+ * the one it already runs (the reference fades between two state objects); -1 — it fades to unity and then keeps its samples; AW_EQ_KEEP —
+ * it is not part of the change: its preset and its Float64 state go on untouched.  NULL: every stream takes definition 0.  n_definitions
+ * == 0 is allowed when every entry is -1 or AW_EQ_KEEP.  A handle whose stage is off counts as every stream at -1 and the call switches
+ * the stage on (the reference's processor starts at unity).
+ *  - one fade clock per handle.  A published target begins at the first frame of the next batch call or, while a fade runs, at the frame
+ *    where that fade ends, also in the middle of a call.  Until it begins a newer publication is merged into it stream by stream: an entry
+ *    that is not AW_EQ_KEEP replaces the older one.  When a fade ends the fading streams' new preset and state become their active ones.
+ *    There is no retirement box: the stage behaves as aw_eq does when its host drains after every call.
+ *  - arithmetic, per ear of a fading stream, frame i of the fade counted from 1: old = the active preset's ParametricEqualizerState.process
+ *    going on from its state (the sample itself at -1), new = the target's from a zero state (the sample itself for -1), both rounded to
+ *    float32; out = Float(Double(old) * (1 - g) + Double(new) * g), g = Double(i) / Double(T) (:296-304), computed as aw_eq's blend is:
+ *    the new side's product rounded to Float64, the old side's fused into the sum, fma(Double(old), 1 - g, Double(new) * g).
+ *  - a call is cut at every frame where the clock begins or ends a fade, and every stream, fading or not, is processed as those pieces in
+ *    order, each as aw_eq_state_process splits a call.  A group of streams with one target history therefore equals aw_eq over the
+ *    stage-off output bit for bit, and a stream at AW_EQ_KEEP a handle given the pieces as calls.  Chunking by streams, sample formats,
+ *    pinned or pageable buffers and sharding over handles that receive the same publications change no bit; the clock moves once per call.
+ *  - with no fade running and none published a call queues what it queued before this entry existed.
+ *  - aw_spatializer_reset zeroes every filter state (active, faded from, faded to) and leaves the setting, the clock and a published
+ *    target where they are (applyPendingReset, :341-352).
+ *  - the call may allocate, upload and synchronise; no batch entry allocates, frees or synchronises for the stage: the fade, its begin and
+ *    its end are queued on the context's stream.  Do not call it while a process call on the same handle is running.
+ * Errors: as aw_spatializer_set_equalizer, with AW_EQ_KEEP allowed in the map; NULL stream_definition with n_definitions == 0 is
+ * AW_ERR_INVALID_ARGUMENT too.  A call that fails leaves the stage, the clock and a published target as they were.
+ * aw_spatializer_info: 27 the frames left of the running fade, 28 whether a target is published and has not begun. */
+#define AW_EQ_KEEP (-2)
+AW_API aw_status aw_spatializer_set_equalizer_target(aw_spatializer *sp, const aw_eq_definition *const *definitions, int32_t n_definitions,
+                                                     const int32_t *stream_definition);
 
 /* ParametricEqualizerProcessor  :116-408: starts at unity; aw_eq_set_target prepares and publishes a
  * target that the next process call crossfades to over max(1, round(0.020 * sample_rate)) frames

@@ -156,6 +156,11 @@ class Spatializer {
         if (!streamDefinition.empty() && streamDefinition.size() != (size_t)aw_spatializer_stream_count(h_)) throw Error(AW_ERR_INVALID_ARGUMENT, "streamDefinition needs one entry per stream");
         check(aw_spatializer_set_equalizer(h_, definitions.data(), (int32_t)definitions.size(), streamDefinition.empty() ? nullptr : streamDefinition.data()));
     }
+    // a target the stage fades to over 20 ms from the next batch call on; entries as setEqualizer's, AW_EQ_KEEP: the stream is not part of the change
+    void setEqualizerTarget(const std::vector<const aw_eq_definition *> &definitions, const std::vector<int32_t> &streamDefinition = {}) {
+        if (!streamDefinition.empty() && streamDefinition.size() != (size_t)aw_spatializer_stream_count(h_)) throw Error(AW_ERR_INVALID_ARGUMENT, "streamDefinition needs one entry per stream");
+        check(aw_spatializer_set_equalizer_target(h_, definitions.data(), (int32_t)definitions.size(), streamDefinition.empty() ? nullptr : streamDefinition.data()));
+    }
     int64_t info(int32_t what) const { return aw_spatializer_info(h_, what); }
     void reset() { check(aw_spatializer_reset(h_)); }
     aw_spatializer *get() const { return h_; }

@@ -175,6 +175,31 @@ public final class BatchSpatializer {
         return out
     }
 
+    /// A target the equalizer stage of the batch entries fades to over 20 ms, from the next batch call on
+    /// (`aw_spatializer_set_equalizer_target`).  `streamDefinition`: per stream an index into `definitions`, -1 (fade to unity) or
+    /// `BatchSpatializer.equalizerKeep` (the stream is not part of the change); empty: every stream takes definition 0.  A stage that is
+    /// off counts as every stream at unity.  Allocates and uploads here, not on the process path.
+    public static let equalizerKeep: Int32 = -2        // AW_EQ_KEEP
+    public func setEqualizerTarget(definitions: [HIPEqualizerDefinition], streamDefinition: [Int32] = []) throws {
+        precondition(streamDefinition.isEmpty || streamDefinition.count == Int(aw_spatializer_stream_count(handle)))
+        var handles: [OpaquePointer?] = []
+        defer { for h in handles { aw_eq_definition_destroy(h) } }
+        for d in definitions {
+            guard let h = HIPEqualizerEffect.makeDefinitionHandle(d) else { throw BatchSpatializer.error(AW_ERR_OUT_OF_MEMORY) }
+            handles.append(h)
+        }
+        let st = handles.withUnsafeBufferPointer { defs in
+            streamDefinition.withUnsafeBufferPointer { map in
+                aw_spatializer_set_equalizer_target(handle, defs.baseAddress, Int32(defs.count), streamDefinition.isEmpty ? nil : map.baseAddress)
+            }
+        }
+        guard st == AW_OK else { throw BatchSpatializer.error(st) }
+    }
+
+    /// Frames left of the running fade (`aw_spatializer_info` 27) and whether a target is published and has not begun (28).
+    public var equalizerFadeFramesLeft: Int64 { aw_spatializer_info(handle, 27) }
+    public var equalizerTargetPending: Bool { aw_spatializer_info(handle, 28) == 1 }
+
     /// `reserve` plus the host entry's device-side staging: `process(hostInput:…)` never allocates afterwards either.
     public func reserveHost(maxFrames: Int64) throws {
         let st = aw_spatializer_reserve_host(handle, maxFrames)

@@ -1,5 +1,6 @@
 """What the equalizer stage of the batch entries costs (equalizer stage): device time of aw_eq_stage_kernel against
-aw_eq_cascade_kernel over the same buffer, cfg 4's equalizer shape (512 streams x 10 s at 96 kHz, CCA CRA ParametricEq.txt).
+aw_eq_cascade_kernel over the same buffer, cfg 4's equalizer shape (512 streams x 10 s at 96 kHz, CCA CRA ParametricEq.txt) unless
+--streams / --rate / --five-filters say otherwise.
 
   python tools/eq_stage_cost.py [--streams 512] [--seconds 10] [--reps 10] [--out eq_stage_cost.json]
   python tools/eq_stage_cost.py --cascade-only --package-root <checkout of another commit, built>     the yardstick on that commit
@@ -27,6 +28,8 @@ def main():
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out", default="")
+    ap.add_argument("--rate", type=float, default=96000.0, help="sample rate (cfg 2's shape: --streams 128 --rate 48000 --five-filters)")
+    ap.add_argument("--five-filters", action="store_true", help="the five-filter preset of tests/test_gpu_eq.py instead of the fixture's ten")
     ap.add_argument("--cascade-only", action="store_true", help="time the cascade leg alone (works on commits without the stage)")
     ap.add_argument("--package-root", default=ROOT, help="the checkout whose airwave_amd is measured (its presets are read from this one)")
     a = ap.parse_args()
@@ -36,12 +39,15 @@ def main():
     assert os.path.dirname(os.path.dirname(os.path.abspath(aw.__file__))) == os.path.abspath(a.package_root), aw.__file__
     if not torch.cuda.is_available():
         sys.exit("no GPU: this tool measures device time and has no other mode")
-    fs = 96000.0
+    fs = a.rate
     S, F = a.streams, int(a.seconds * fs)
     F -= F % 32                                                      # whole chunks: one launch per call on either side
     eq_dir = os.path.join(ROOT, "tests", "golden", "eq")
     parse = lambda name: aw.EqualizerAPOParser.parse(open(os.path.join(eq_dir, name), "rb").read(), name)
     fixture, other = parse("CCA CRA ParametricEq.txt"), parse("Bass Booster.txt")
+    if a.five_filters:
+        five = [(1, 105.0, -2.8, 0.7), (0, 65.3, 1.0, 1.68), (0, 1000.0, 6.0, 0.707), (2, 10000.0, -5.2, 0.7), (0, 20.0, 3.0, 4.0)]
+        fixture = aw.EqualizerDefinition(-2.56, [aw.EqualizerFilter(1, None, True, t, f, g, q) for t, f, g, q in five])
     ctx = aw.Context(0, stream=torch.cuda.current_stream().cuda_stream)
     h = np.zeros((2, 256), np.float32)
     h[0, 0] = 1.0
