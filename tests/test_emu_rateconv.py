@@ -9,6 +9,7 @@ import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
 import emu_rateconv as emu  # noqa: E402
+import rateconv_cases as geo  # noqa: E402
 
 PAIRS = [(48000, 96000), (96000, 48000), (44100, 48000), (48000, 44100), (192000, 44100)]
 CHANNELS = [1, 2, 7, 16]
@@ -55,31 +56,60 @@ def test_the_first_output_needs_d_plus_one_frames():
         assert emu.input_frames_for(1, L, M, D) == D + 1
 
 
+def check_calls(pair, channels, n, i, rng, name):
+    """n frames, then 7, then the flush, kernel against the sequential rule: outputs, both history slots and the counts."""
+    k = emu.Converter(pair[0], pair[1], STREAMS, channels, kernel=True)
+    q = emu.Converter(pair[0], pair[1], STREAMS, channels, kernel=False)
+    x = rng.standard_normal((STREAMS, n, channels)).astype(np.float32)
+    x7 = rng.standard_normal((STREAMS, 7, channels)).astype(np.float32)
+    consumed = produced = 0
+    for step, call in enumerate((x, x7)):
+        before = k.history().copy()
+        yk, yq = k.process(call, shift=(i + step) % 4, out_shift=(i + 2 * step + 1) % 4), q.process(call)
+        consumed += call.shape[1]
+        assert yk.shape[1] == available(k, consumed) - produced, (name, step)
+        produced += yk.shape[1]
+        assert same(yk, yq), (name, step)
+        assert same(k.history(), q.history()), (name, step)                     # the slot the call wrote
+        assert same(k.hist[k.cur ^ 1], before), (name, step)                    # the slot it read is as it was
+        assert np.array_equal(k.counts, q.counts) and np.array_equal(k.counts, [consumed, produced]), (name, step)
+        assert np.array_equal(k.dev_counts, np.tile(k.counts, (STREAMS, 1))), (name, step)
+    yk, yq = k.flush(), q.flush()
+    assert same(yk, yq), (name, "flush")
+    assert produced + yk.shape[1] == -(-(consumed * k.L) // k.M), (name, "flush")
+    assert not k.counts.any() and not k.history().any() and not k.dev_counts.any()
+    return produced
+
+
 @pytest.mark.parametrize("channels", CHANNELS)
 @pytest.mark.parametrize("pair", PAIRS, ids=lambda p: f"{p[0]}-{p[1]}")
 def test_kernel_equals_the_sequential_rule(pair, channels):
     rng = np.random.default_rng(pair[0] + 31 * channels)
     for i, (name, n) in enumerate(lengths(pair, channels).items()):
-        k = emu.Converter(pair[0], pair[1], STREAMS, channels, kernel=True)
-        q = emu.Converter(pair[0], pair[1], STREAMS, channels, kernel=False)
-        x = rng.standard_normal((STREAMS, n, channels)).astype(np.float32)
-        x7 = rng.standard_normal((STREAMS, 7, channels)).astype(np.float32)
-        consumed = produced = 0
-        for step, call in enumerate((x, x7)):
-            before = k.history().copy()
-            yk, yq = k.process(call, shift=(i + step) % 4, out_shift=(i + 2 * step + 1) % 4), q.process(call)
-            consumed += call.shape[1]
-            assert yk.shape[1] == available(k, consumed) - produced, (name, step)
-            produced += yk.shape[1]
-            assert same(yk, yq), (name, step)
-            assert same(k.history(), q.history()), (name, step)                     # the slot the call wrote
-            assert same(k.hist[k.cur ^ 1], before), (name, step)                    # the slot it read is as it was
-            assert np.array_equal(k.counts, q.counts) and np.array_equal(k.counts, [consumed, produced]), (name, step)
-            assert np.array_equal(k.dev_counts, np.tile(k.counts, (STREAMS, 1))), (name, step)
-        yk, yq = k.flush(), q.flush()
-        assert same(yk, yq), (name, "flush")
-        assert produced + yk.shape[1] == -(-(consumed * k.L) // k.M), (name, "flush")
-        assert not k.counts.any() and not k.history().any() and not k.dev_counts.any()
+        check_calls(pair, channels, n, i, rng, name)
+
+
+@pytest.mark.parametrize("pair,channels,why", geo.CASES, ids=geo.IDS)
+def test_kernel_equals_the_sequential_rule_over_the_tile_geometries(pair, channels, why):
+    """The shared table of tests/rateconv_cases.py, which tests/test_gpu_rateconv_geometry.py runs on the device: a case that fails here too
+    is the tile's indexing, one that fails only there is the device."""
+    tile = emu.tile(pair[0], pair[1], channels)
+    rng = np.random.default_rng(pair[0] + 31 * channels + 1)
+    for i, n in enumerate((geo.first_call_frames(pair, channels), lengths(pair, channels)["tile+1"])):
+        produced = check_calls(pair, channels, n, i + channels, rng, why)
+        assert produced > (2 - i) * tile
+
+
+@pytest.mark.parametrize("handle", [geo.TINY_TILE, geo.SMALLEST_MEASURING], ids=str)
+def test_a_tile_of_a_handful_of_outputs(handle):
+    """The handles at the refusal boundary (tests/rateconv_cases.py): tiles of 7 and 12 outputs, so a call of 40 outputs is 6 or 4
+    workgroups per stream, each with an input image of nearly the whole LDS."""
+    pair, channels = handle
+    L, M, T, D = emu.plan(*pair)
+    tile = emu.tile(pair[0], pair[1], channels)
+    assert tile == geo.BOUNDARY_TILES[handle] == geo.tile_by_the_formula(L, M, T, channels)
+    produced = check_calls(pair, channels, emu.input_frames_for(40, L, M, D), 1, np.random.default_rng(tile), handle)
+    assert 40 <= produced <= 42 and produced > 3 * tile
 
 
 def available(rc, consumed):

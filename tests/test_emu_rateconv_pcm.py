@@ -12,6 +12,7 @@ import pytest
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
 import emu_rateconv as emu  # noqa: E402
 import emu_rateconv_pcm as pcm  # noqa: E402
+import rateconv_cases as geo  # noqa: E402
 from emu_rateconv_pcm import F32, S16, S24, S32, NONE, TPDF, TPDF_HP  # noqa: E402
 
 STREAMS = 3
@@ -79,6 +80,27 @@ def test_all_format_pairs_on_the_smallest_tile(fi, fo):
 def test_kernel_equals_the_composition(pair, C, form):
     fi, fo, dither, gains = FORMS[form]
     run_three_calls(pair, C, fi, fo, dither, gains, lengths(pair, C)["two tiles + 3"], seed=sorted(FORMS).index(form) + C)
+
+
+@pytest.mark.parametrize("form", ["s24-s24 tpdf_hp", "f32-s16 gain"])
+@pytest.mark.parametrize("pair,C,why", geo.CASES, ids=geo.IDS)
+def test_kernel_equals_the_composition_over_the_tile_geometries(pair, C, why, form):
+    """The shared table of tests/rateconv_cases.py in the two forms tests/test_gpu_rateconv_geometry.py runs on the device (s24 with
+    per-stream gains): a case that fails here too is the tile's indexing, one that fails only there is the device."""
+    fi, fo, dither, _ = FORMS[form]
+    k = run_three_calls(pair, C, fi, fo, dither, GAINS, geo.first_call_frames(pair, C), seed=sorted(FORMS).index(form) + C)
+    assert int(k.levels["frames"][0]) > 2 * emu.tile(pair[0], pair[1], C)
+
+
+def test_a_tile_of_seven_outputs():
+    """The handle next to the refusal boundary (tests/rateconv_cases.py): six workgroups per stream for 40 outputs, each of which encodes
+    7 * 16 elements and leaves them through the ragged-end byte stores."""
+    pair, C = geo.TINY_TILE
+    L, M, T, D = emu.plan(*pair)
+    assert emu.tile(pair[0], pair[1], C) == 7
+    fi, fo, dither, _ = FORMS["s24-s24 tpdf_hp"]
+    k = run_three_calls(pair, C, fi, fo, dither, GAINS, emu.input_frames_for(40, L, M, D), seed=5)
+    assert int(k.levels["frames"][0]) >= 40
 
 
 def test_the_dither_is_in_the_output():

@@ -17,6 +17,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu
 import emu_rateconv as emu  # noqa: E402
 import emu_rateconv_pcm as pcm  # noqa: E402
 import emu_rateconv_tp as tp  # noqa: E402
+import rateconv_cases as geo  # noqa: E402
 from emu_rateconv_pcm import F32, S16, S24, NONE, TPDF  # noqa: E402
 
 STREAMS = 2
@@ -51,8 +52,13 @@ def call_lengths(pair, C):
         made = available(N + n2, L, M, D) - available(N, L, M, D)
         if 7 <= made <= 10 and (L > M or available(N + n2 + 1, L, M, D) == available(N + n2, L, M, D)):
             break
-    else:
-        raise AssertionError("no call of 7 .. 10 outputs")
+    else:                                                 # the ratio makes no such count (8 -> 48 kHz: six a frame): the most below 7 it can
+        assert L > M, "no call of 7 .. 10 outputs"
+        n2 = max(n for n in range(1, 64) if available(N + n, L, M, D) - available(N, L, M, D) < 7)
+        made = available(N + n2, L, M, D) - available(N, L, M, D)
+        assert 1 <= made < 7
+        calls.append((n2, made, made))
+        return calls
     calls.append((n2, 7, 10))
     if L < M:
         calls.append((1, 0, 0))
@@ -80,14 +86,52 @@ def trio(pair, C, dither, gains, S=STREAMS, first=FIRST):
 @pytest.mark.parametrize("form", sorted(FORMS))
 @pytest.mark.parametrize("pair,C", SHAPES + [SHORT], ids=str)
 def test_kernel_equals_the_composition_and_leaves_the_bytes_alone(pair, C, form):
+    tile = tp.tp_tile(pair[0], pair[1], C)
+    assert tile == 5 if (pair, C) == SHORT else tile >= 39
+    check_calls(pair, C, form, call_lengths(pair, C))
+
+
+@pytest.mark.parametrize("pair,C,why", geo.CASES, ids=geo.IDS)
+def test_kernel_equals_the_composition_over_the_tile_geometries(pair, C, why):
+    """The shared table of tests/rateconv_cases.py, which tests/test_gpu_rateconv_geometry.py runs on the device, through process and
+    through measure: a case that fails here too is the tile's indexing, one that fails only there is the device."""
+    assert tp.tp_tile(pair[0], pair[1], C) == emu.tile(pair[0], pair[1], C) - tp.HISTORY >= 1
+    xs, q = check_calls(pair, C, "s16-s24 tpdf gain", call_lengths(pair, C))
+    measure_equals_the_composition(pair, C, xs, q)
+
+
+def test_a_measuring_tile_of_one_output():
+    """The smallest tile that leaves a measuring tile (tests/rateconv_cases.py: 12 outputs, so 1): every workgroup computes its 11
+    predecessors again for one output of its own, and the first 11 take theirs from the carried history."""
+    pair, C = geo.SMALLEST_MEASURING
+    L, M, T, D = emu.plan(*pair)
+    assert tp.tiles(L, M, T, C) == (12, 1) and tp.tiles(L, M, T, geo.TINY_TILE[1]) == (7, -4)
+    lengths = [(emu.input_frames_for(14, L, M, D), 14, 14), (emu.input_frames_for(23, L, M, D) - emu.input_frames_for(14, L, M, D), 9, 9), (1, 0, 0)]
+    xs, q = check_calls(pair, C, "s16-s24 tpdf gain", lengths)
+    measure_equals_the_composition(pair, C, xs, q)
+
+
+def measure_equals_the_composition(pair, C, xs, q):
+    """measure and measure_flush over the calls xs of check_calls leave the records q.records that process and flush left."""
+    fi, _, dither, gains = FORMS["s16-s24 tpdf gain"]
+    k = tp.Kernel(pair[0], pair[1], STREAMS, C, dither, SEED, FIRST, gains)
+    total = sum(k.measure(x, fi, shift=(i + 1) % 4) for i, x in enumerate(xs))
+    total += k.measure_flush()
+    assert k.records.tobytes() == q.records.tobytes() and np.all(k.records["frames"] == total), (pair, C, k.records, q.records)
+    assert not k.levels.view(np.uint8).any() and k.clipped[0] == 0 and not k.counts.any() and not k.tp_history().any()
+
+
+def check_calls(pair, C, form, lengths):
+    """The calls `lengths` (call_lengths) and the flush through the measuring kernel, the composition and the PCM kernel with measuring
+    off; returns the calls' inputs and the composition."""
     fi, fo, dither, gains = FORMS[form]
     rng = np.random.default_rng(pair[0] + C + len(form))
     k, q, plain = trio(pair, C, dither, gains)
     tile = tp.tp_tile(pair[0], pair[1], C)
-    assert tile == 5 if (pair, C) == SHORT else tile >= 39
-    total = 0
-    for step, (n, lo, hi) in enumerate(call_lengths(pair, C)):
+    total, xs = 0, []
+    for step, (n, lo, hi) in enumerate(lengths):
         x = pcm.random_input(rng, (STREAMS, n, C), fi)
+        xs.append(x)
         before, slot = k.tp_history().copy(), k.tp_cur
         yk, yq, yp = k.process(x, fi, fo, shift=step % 4, out_shift=(2 * step + 1) % 4), q.process(x, fi, fo), plain.process(x, fi, fo)
         assert lo <= yk.shape[1] <= hi, (step, yk.shape[1], lo, hi)
@@ -107,6 +151,7 @@ def test_kernel_equals_the_composition_and_leaves_the_bytes_alone(pair, C, form)
     agree(k, q, (pair, C, form, "flush"), plain)
     assert not k.counts.any() and not k.history().any() and not k.tp_history().any()   # n restarts at 0 and v = 0 before it ...
     assert np.all(k.records["frames"] == total + yk.shape[1])                          # ... and the records stay
+    return xs, q
 
 
 def exact_cuts(pair, C, chunks):

@@ -144,8 +144,15 @@ def same_levels(got, want):
 
 @pytest.mark.parametrize("pair,C,form", CASES, ids=lambda v: str(v).replace(" ", "_"))
 def test_device_equals_the_composition_byte_for_byte(G, pair, C, form):
-    fi, fo, dither, gains = FORMS[form]
-    x, x7, want, levels, clipped = case(pair, C, form)
+    check_three_calls(G, pair, C, form)
+
+
+def check_three_calls(G, pair, C, form, gains="form"):
+    """process (input 1 byte, output 3 bytes off a word), process and flush of case(pair, C, form, gains=gains) against the composition:
+    every byte, every record field after every call, and the clipped word."""
+    fi, fo, dither, g = FORMS[form]
+    x, x7, want, levels, clipped = case(pair, C, form, gains=gains)
+    gains = g if isinstance(gains, str) else gains
     rc = converter(G, pair, STREAMS, C, dither, gains)
     assert (rc.info()["dither"], rc.info()["gain_mode"], rc.info()["metering"]) == (dither, 1 if gains else 0, 1)
     word = G.torch.zeros(1, dtype=G.torch.int64, device="cuda")

@@ -91,6 +91,12 @@ def case(pair, C):
 
 @pytest.mark.parametrize("pair,C", SHAPES + [SHORT], ids=str)
 def test_device_equals_the_composition_through_process_and_through_measure(G, pair, C):
+    check_process_and_measure(G, pair, C)
+
+
+def check_process_and_measure(G, pair, C):
+    """The calls of case(pair, C) and the flush through process, then through measure and measure_flush: bytes, true-peak records and
+    levels after every call against the composition."""
     xs, want, records, levels = case(pair, C)
     rc = converter(G, pair, STREAMS, C, TPDF, GAINS)
     info = rc.info()

@@ -142,6 +142,44 @@ def test_the_float32_rule_stays_within_its_bound_of_the_float64_evaluation():
         assert y.shape == y64[:, 0].shape and np.all(np.abs(y - y64[:, 0]) <= bound[:, 0])
 
 
+def test_the_refusal_boundary_of_the_tile():
+    """Every accepted plan (coprime L, M <= 640, T = 2 ceil(48 max(1, M / L))) at 1 .. 16 channels: where the header's rc_tile is 0
+    (aw_rateconv_create refuses), 1 .. 11 (created, aw_tp_rateconv_set refuses) or 12 (the smallest with a measuring tile), and the three
+    handles tests/rateconv_cases.py pins there by name.  The header's tile is asked wherever a tile of 13 outputs does not fit by a margin
+    of one segment (no smaller tile can come from anywhere else), and must equal the formula restated in Python on all of those."""
+    from math import gcd
+    import emu_rateconv_tp as tp
+    import rateconv_cases as geo
+    by_tile = {}
+    for L in range(1, 641):
+        for M in range(1, 641):
+            if L == M or gcd(L, M) != 1:
+                continue
+            D = -(-ref.Z * M // L) if M > L else ref.Z
+            T = 2 * D
+            for C in range(1, 17):
+                span = -(-13 * M // L) + T
+                if ((span - 1) // 32 + 2) * 35 * C + 3 * C + 3 + 13 * C <= 12288:          # 13 outputs fit with a segment to spare
+                    continue
+                tile, tp_tile = tp.tiles(L, M, T, C)
+                assert tile == geo.tile_by_the_formula(L, M, T, C) and tp_tile == tile - 11, (L, M, T, C)
+                by_tile.setdefault(tile, []).append((L, M, T, C))
+    assert set(range(0, 13)) <= set(by_tile)                                         # every tile length from 0 to 12 exists
+    # L = 1, M = 640 has no tile at any channel count: 61 440 taps alone are five times the LDS
+    assert all((1, 640, 61440, C) in by_tile[0] for C in range(1, 17))
+    n_refused_by_set = sum(len(by_tile[t]) for t in range(1, 12))
+    print(f"no tile: {len(by_tile[0])} handles; a tile of 1 .. 11: {n_refused_by_set}; a tile of 12: {len(by_tile[12])}")
+    assert (len(by_tile[0]), n_refused_by_set) == (150012, 18718)                    # (DESIGN.md §4.7 quotes them) of 3 985 184
+    assert all(M > 6 * L for t in range(12) for L, M, T, C in by_tile[t])             # all of them lower the rate more than sixfold
+    for handle, want in geo.BOUNDARY_TILES.items():
+        (in_rate, out_rate), C = handle
+        L, M, T, D = emu.plan(in_rate, out_rate)
+        assert (L, M, T, C) in by_tile[want] and emu.tile(in_rate, out_rate, C) == want, handle
+    assert geo.BOUNDARY_TILES == {geo.NO_TILE: 0, geo.TINY_TILE: 7, geo.SMALLEST_MEASURING: 12}
+    L, M, T, _ = emu.plan(*geo.SMALLEST_MEASURING[0])
+    assert tp.tiles(L, M, T, geo.SMALLEST_MEASURING[1]) == (12, 1) and tp.tiles(L, M, T, geo.TINY_TILE[1]) == (7, -4)
+
+
 def test_the_entries_are_declared_exported_and_typed():
     text = open(HEADER).read()
     declared = set(re.findall(r"AW_API\s+[\w\s\*]+?\b(aw_\w+)\s*\(", text))
