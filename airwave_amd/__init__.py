@@ -13,6 +13,7 @@ from .api import (  # noqa: E402
     AirwaveError, Context, ConvolutionEngine, DITHER_MODES, GAIN_MODES, HRIR, HRIRChannelMap, HRIRError, HRIRManager, InputLayout, LEVELS_DTYPE,
     LOUDNESS_DTYPE, loudness_gain, TRUE_PEAK_DTYPE, true_peak_filter, LIMITER_DTYPE,
     RealtimeAudioProcessor, Resampler, SAMPLE_FORMATS, Spatializer, EQ_KEEP, WAVData, WAVError, WAVLoader, default_context, sample_format_bytes,
+    MultiSpatializer, device_count, device_info,
 )
 
 from .rateconv import RateConverter, convert, rateconv_filter, rateconv_plan  # noqa: E402
@@ -35,4 +36,5 @@ __all__ = [
     "InputLayout", "RealtimeAudioProcessor", "Resampler", "Spatializer", "WAVData", "WAVError", "WAVLoader",
     "default_context", "SAMPLE_FORMATS", "sample_format_bytes", "DITHER_MODES", "GAIN_MODES", "LEVELS_DTYPE",
     "LOUDNESS_DTYPE", "loudness_gain", "TRUE_PEAK_DTYPE", "true_peak_filter", "LIMITER_DTYPE", "EQ_KEEP",
+    "MultiSpatializer", "device_count", "device_info",
 ]

@@ -167,7 +167,43 @@ SIGNATURES = {
     "aw_tp_rateconv_reset_records": (_I32, [_V]),
     "aw_tp_rateconv_measure": (_I32, [_V, _V, _I32, _I64, ctypes.POINTER(ctypes.c_int64)]),
     "aw_tp_rateconv_measure_flush": (_I32, [_V, ctypes.POINTER(ctypes.c_int64)]),
+    # device enumeration and the multi-device batch spatializer
+    "aw_device_count": (_I32, []),
+    "aw_device_info": (_I32, [_I32, _V]),
+    "aw_multi_create": (_I32, [c_int32_p, _I32, c_float_p, _I32, _I32, _D, _I32, c_int32_p, c_int32_p, _I32, _I32, c_void_pp]),
+    "aw_multi_destroy": (None, [_V]),
+    "aw_multi_shard_count": (_I32, [_V]),
+    "aw_multi_stream_count": (_I32, [_V]),
+    "aw_multi_channel_count": (_I32, [_V]),
+    "aw_multi_shard": (_I32, [_V, _I32, c_int32_p, c_int32_p, c_int32_p]),
+    "aw_multi_spatializer": (_V, [_V, _I32]),
+    "aw_multi_context": (_V, [_V, _I32]),
+    "aw_multi_reserve_pcm": (_I32, [_V, _I64, _I32, _I32]),
+    "aw_multi_process_host_pcm": (_I32, [_V, _V, _I32, _V, _I32, _I64, ctypes.POINTER(ctypes.c_uint64)]),
+    "aw_multi_reset": (_I32, [_V]),
+    "aw_multi_alloc_pinned": (_I32, [_V, _SZ, c_void_pp]),
+    "aw_multi_free_pinned": (_I32, [_V, _V]),
+    "aw_multi_set_dither": (_I32, [_V, _I32, _U64, _U64]),
+    "aw_multi_set_metering": (_I32, [_V, _I32]),
+    "aw_multi_reset_levels": (_I32, [_V]),
+    "aw_multi_set_gain": (_I32, [_V, _I32, c_float_p, _I32, ctypes.c_float]),
+    "aw_multi_set_loudness": (_I32, [_V, _I32, _D]),
+    "aw_multi_set_true_peak": (_I32, [_V, _I32]),
+    "aw_multi_set_limiter": (_I32, [_V, _I32, ctypes.c_float, _I32, _I32]),
+    "aw_multi_set_equalizer": (_I32, [_V, c_void_pp, _I32, c_int32_p]),
+    "aw_multi_set_equalizer_target": (_I32, [_V, c_void_pp, _I32, c_int32_p]),
+    "aw_multi_get_levels": (_I32, [_V, _I32, _I32, _V]),
+    "aw_multi_get_loudness": (_I32, [_V, _I32, _I32, _V]),
+    "aw_multi_get_loudness_hops": (_I32, [_V, _I32, _I64, _I64, _V]),
+    "aw_multi_get_true_peak": (_I32, [_V, _I32, _I32, _V]),
+    "aw_multi_get_limiter": (_I32, [_V, _I32, _I32, _V]),
 }
+
+
+class DeviceInfo(ctypes.Structure):
+    """struct aw_device_info (344 bytes)."""
+    _fields_ = [("name", ctypes.c_char * 256), ("arch", ctypes.c_char * 64), ("compute_units", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("total_bytes", ctypes.c_uint64), ("free_bytes", ctypes.c_uint64)]
 
 
 

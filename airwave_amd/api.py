@@ -450,6 +450,12 @@ class Spatializer:
             self._lib.aw_spatializer_destroy(self._h)
             self._h = None
 
+    _ENTRY_PREFIX = "aw_spatializer_"
+
+    def _entry(self, name: str):
+        """The C entry behind a setting or a record getter: MultiSpatializer has the same ones under its own prefix."""
+        return getattr(self._lib, self._ENTRY_PREFIX + name)
+
     def info(self) -> Dict[str, int]:
         g = lambda i: int(self._lib.aw_spatializer_info(self._h, i))
         return {"fft": g(0), "hop": g(1), "partitions": g(2), "path": g(3), "history": g(4), "dominant_frames": g(5), "scratch_bytes": g(6),
@@ -551,12 +557,12 @@ class Spatializer:
             if mode not in DITHER_MODES:
                 raise ValueError(f"unknown dither mode {mode!r} (one of {', '.join(DITHER_MODES)})")
             mode = DITHER_MODES[mode]
-        _check(self._lib.aw_spatializer_set_dither(self._h, int(mode), int(seed), int(first_stream)))
+        _check(self._entry("set_dither")(self._h, int(mode), int(seed), int(first_stream)))
 
     def set_metering(self, on: bool = True) -> None:
         """aw_spatializer_set_metering: per-stream levels of every later batch call (process, process_host_into, the PCM entries).
         Switching it on allocates the records here, not on the process path."""
-        _check(self._lib.aw_spatializer_set_metering(self._h, int(bool(on))))
+        _check(self._entry("set_metering")(self._h, int(bool(on))))
 
     def levels(self, first_stream: int = 0, n: Optional[int] = None) -> np.ndarray:
         """aw_spatializer_get_levels: the records of n streams from first_stream on (default: all) as a structured array of
@@ -566,11 +572,11 @@ class Spatializer:
         if first_stream < 0 or n < 0 or first_stream + n > self.n_streams:
             raise ValueError(f"streams [{first_stream}, {first_stream + n}) outside [0, {self.n_streams})")
         out = np.zeros(n, LEVELS_DTYPE)
-        _check(self._lib.aw_spatializer_get_levels(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
+        _check(self._entry("get_levels")(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
         return out
 
     def reset_levels(self) -> None:
-        _check(self._lib.aw_spatializer_reset_levels(self._h))
+        _check(self._entry("reset_levels")(self._h))
 
     def set_gain(self, mode, gains=None, ceiling: Optional[float] = None) -> None:
         """aw_spatializer_set_gain: 'none'; 'fixed' with one gain (every stream) or one per stream; 'peak_ceiling' with 0 < ceiling <= 1,
@@ -596,14 +602,14 @@ class Spatializer:
             if ceiling is None or not (0.0 < float(np.float32(ceiling)) <= 1.0):
                 raise ValueError(f"a ceiling gain needs 0 < ceiling <= 1, got {ceiling!r}")
             c = float(ceiling)
-        _check(self._lib.aw_spatializer_set_gain(self._h, mode, None if g is None else _fp(g), 0 if g is None else int(g.size), ctypes.c_float(c)))
+        _check(self._entry("set_gain")(self._h, mode, None if g is None else _fp(g), 0 if g is None else int(g.size), ctypes.c_float(c)))
 
     def set_loudness(self, on: bool = True, max_seconds: float = 0.0) -> None:
         """aw_spatializer_set_loudness: BS.1770 integrated loudness of every later batch call, per stream, measured before the gain.
         Switching it on allocates the hop energies of max_seconds per stream here, not on the process path."""
         if on and not (np.isfinite(max_seconds) and max_seconds > 0):
             raise ValueError(f"max_seconds must be finite and positive, got {max_seconds!r}")
-        _check(self._lib.aw_spatializer_set_loudness(self._h, int(bool(on)), float(max_seconds)))
+        _check(self._entry("set_loudness")(self._h, int(bool(on)), float(max_seconds)))
 
     def loudness(self, first_stream: int = 0, n: Optional[int] = None) -> np.ndarray:
         """aw_spatializer_get_loudness: the gated loudness of n streams from first_stream on (default: all) as a structured array of
@@ -613,7 +619,7 @@ class Spatializer:
         if first_stream < 0 or n < 0 or first_stream + n > self.n_streams:
             raise ValueError(f"streams [{first_stream}, {first_stream + n}) outside [0, {self.n_streams})")
         out = np.zeros(n, LOUDNESS_DTYPE)
-        _check(self._lib.aw_spatializer_get_loudness(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
+        _check(self._entry("get_loudness")(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
         return out
 
     def loudness_hops(self, stream: int, first_hop: int, n: int) -> np.ndarray:
@@ -622,13 +628,13 @@ class Spatializer:
         if not 0 <= stream < self.n_streams or first_hop < 0 or n < 0:
             raise ValueError(f"stream {stream}, hops [{first_hop}, {first_hop + n}) out of range")
         out = np.zeros(n, np.float64)
-        _check(self._lib.aw_spatializer_get_loudness_hops(self._h, stream, first_hop, n, ctypes.c_void_p(out.ctypes.data)))
+        _check(self._entry("get_loudness_hops")(self._h, stream, first_hop, n, ctypes.c_void_p(out.ctypes.data)))
         return out
 
     def set_true_peak(self, on: bool = True) -> None:
         """aw_spatializer_set_true_peak: the true peak (4x oversampled) of every later batch call, per stream, measured before the gain.
         Switching it on allocates the records here, not on the process path."""
-        _check(self._lib.aw_spatializer_set_true_peak(self._h, int(bool(on))))
+        _check(self._entry("set_true_peak")(self._h, int(bool(on))))
 
     def true_peak(self, first_stream: int = 0, n: Optional[int] = None) -> np.ndarray:
         """aw_spatializer_get_true_peak: the records of n streams from first_stream on (default: all) as a structured array of
@@ -638,14 +644,14 @@ class Spatializer:
         if first_stream < 0 or n < 0 or first_stream + n > self.n_streams:
             raise ValueError(f"streams [{first_stream}, {first_stream + n}) outside [0, {self.n_streams})")
         out = np.zeros(n, TRUE_PEAK_DTYPE)
-        _check(self._lib.aw_spatializer_get_true_peak(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
+        _check(self._entry("get_true_peak")(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
         return out
 
     def set_limiter(self, on: bool = True, ceiling: float = 1.0, attack_frames: int = 64, hold_frames: int = 128) -> None:
         """aw_spatializer_set_limiter: a look-ahead true-peak limiter on the output of every later batch call, behind the fixed gain;
         0 < ceiling <= 1, 16 <= attack_frames <= 512, 0 <= hold_frames <= 1024.  The output is attack_frames + 11 frames late
         (info()['limiter_latency']).  Switching it on allocates here, not on the process path."""
-        _check(self._lib.aw_spatializer_set_limiter(self._h, int(bool(on)), ctypes.c_float(ceiling), int(attack_frames), int(hold_frames)))
+        _check(self._entry("set_limiter")(self._h, int(bool(on)), ctypes.c_float(ceiling), int(attack_frames), int(hold_frames)))
 
     def limiter(self, first_stream: int = 0, n: Optional[int] = None) -> np.ndarray:
         """aw_spatializer_get_limiter: the records of n streams from first_stream on (default: all) as a structured array of
@@ -655,7 +661,7 @@ class Spatializer:
         if first_stream < 0 or n < 0 or first_stream + n > self.n_streams:
             raise ValueError(f"streams [{first_stream}, {first_stream + n}) outside [0, {self.n_streams})")
         out = np.zeros(n, LIMITER_DTYPE)
-        _check(self._lib.aw_spatializer_get_limiter(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
+        _check(self._entry("get_limiter")(self._h, first_stream, n, ctypes.c_void_p(out.ctypes.data)))
         return out
 
     def set_equalizer(self, definitions, stream_definition=None) -> None:
@@ -664,7 +670,7 @@ class Spatializer:
         stream_definition: per stream the index of its preset, -1 = not equalized (None: every stream takes preset 0).  Allocates and
         uploads here, not on the process path, and starts the filter state from zero.  A preset that cannot be prepared raises
         ParametricEqualizerPreparationError, as ParametricEqualizerState does; the previous stage then stays."""
-        self._set_equalizer(self._lib.aw_spatializer_set_equalizer, definitions, stream_definition)
+        self._set_equalizer(self._entry("set_equalizer"), definitions, stream_definition)
 
     def set_equalizer_target(self, definitions, stream_definition=None) -> None:
         """aw_spatializer_set_equalizer_target: publishes a target that the equalizer stage fades to over max(1, round(0.020 * rate))
@@ -672,7 +678,7 @@ class Spatializer:
         stream_definition: per stream the index of its target, -1 = fade to unity, EQ_KEEP = the stream is not part of the change (None:
         every stream takes definition 0).  A stage that is off counts as every stream at -1.  Allocates, uploads and synchronises here,
         not on the process path; info()['equalizer_fade'] / ['equalizer_pending'] follow the fade.  A failing call changes nothing."""
-        self._set_equalizer(self._lib.aw_spatializer_set_equalizer_target, definitions, stream_definition)
+        self._set_equalizer(self._entry("set_equalizer_target"), definitions, stream_definition)
 
     def _set_equalizer(self, entry, definitions, stream_definition) -> None:
         from .eq import _DefHandle, _check_eq            # (eq.py imports this module)
@@ -719,6 +725,133 @@ class Spatializer:
                 return out
             out.append(((name.value or b"").decode(), float(ms.value), int(n.value)))
             i += 1
+
+
+def device_count() -> int:
+    """aw_device_count: visible HIP devices; 0 when there is none or no driver."""
+    return int(_capi.load().aw_device_count())
+
+
+def device_info(ordinal: int) -> Dict[str, object]:
+    """aw_device_info: name, arch, compute_units, total_bytes and free_bytes of one device (AW_ERR_NO_DEVICE for an ordinal out of range)."""
+    d = _capi.DeviceInfo()
+    _check(_capi.load().aw_device_info(int(ordinal), ctypes.byref(d)))
+    return {"name": d.name.decode("utf-8", "replace"), "arch": d.arch.decode("utf-8", "replace"), "compute_units": int(d.compute_units),
+            "total_bytes": int(d.total_bytes), "free_bytes": int(d.free_bytes)}
+
+
+class _MultiPinnedOwner:
+    """_PinnedOwner for aw_multi_alloc_pinned: page-locked memory every device of the handle can DMA."""
+
+    def __init__(self, multi: "MultiSpatializer", ptr: int, nbytes: int):
+        self._multi, self._ptr = multi, ptr
+        self.__array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 3}
+
+    def __del__(self):
+        try:
+            if self._ptr and getattr(self._multi, "_h", None) and not _finalizing():
+                self._multi._lib.aw_multi_free_pinned(self._multi._h, ctypes.c_void_p(self._ptr))
+        finally:
+            self._ptr = 0
+
+
+class MultiSpatializer(Spatializer):
+    """aw_multi: the batch spatializer over several devices behind one handle.  devices: one ordinal per shard (an ordinal may repeat:
+    several contexts on one device); shard i owns sharding.shard_streams(n_streams, len(devices), i).  The Spatializer methods of the same
+    name, over host arrays laid out as one handle of n_streams streams takes them; per-stream settings and records are sliced and
+    gathered across the shards.  Bit-exact against separately driven handles of the shards' stream counts, not against one big handle."""
+
+    _ENTRY_PREFIX = "aw_multi_"          # set_dither .. set_equalizer_target, levels .. limiter: Spatializer's methods over the multi entries
+
+    def __init__(self, devices: Sequence[int], hrir_tracks, sample_rate: float, left_track, right_track, n_streams: int):
+        self._lib = _capi.load()
+        dev = np.ascontiguousarray(devices, dtype=np.int32).reshape(-1)
+        t = _f32(hrir_tracks)
+        if t.ndim == 1:
+            t = t[None]
+        lt = np.ascontiguousarray(left_track, dtype=np.int32)
+        rt = np.ascontiguousarray(right_track, dtype=np.int32)
+        assert lt.size == rt.size
+        h = ctypes.c_void_p()
+        _check(self._lib.aw_multi_create(_i32p(dev) if dev.size else None, int(dev.size), _fp(t), t.shape[0], t.shape[1], float(sample_rate), int(lt.size),
+                                         _i32p(lt), _i32p(rt), int(n_streams), 0, ctypes.byref(h)))
+        self._h = h
+        self.ctx = None
+        self.devices = [int(d) for d in dev]
+        self.n_streams = int(self._lib.aw_multi_stream_count(self._h))
+        self.n_channels = int(self._lib.aw_multi_channel_count(self._h))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and not _finalizing():
+            self._lib.aw_multi_destroy(self._h)
+            self._h = None
+
+    def shards(self) -> List[Dict[str, int]]:
+        """One entry per device of the list: ordinal, first_stream, count (0: an empty shard, which owns nothing)."""
+        out = []
+        for i in range(self._lib.aw_multi_shard_count(self._h)):
+            o, f, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+            _check(self._lib.aw_multi_shard(self._h, i, ctypes.byref(o), ctypes.byref(f), ctypes.byref(c)))
+            out.append({"ordinal": int(o.value), "first_stream": int(f.value), "count": int(c.value)})
+        return out
+
+    def shard_info(self, shard: int) -> Optional[Dict[str, int]]:
+        """Spatializer.info() of one shard through its borrowed handle; None for an empty shard."""
+        h = self._lib.aw_multi_spatializer(self._h, int(shard))
+        if not h:
+            return None
+        view = Spatializer.__new__(Spatializer)
+        view._lib, view._h = self._lib, ctypes.c_void_p(h)
+        try:
+            return view.info()
+        finally:
+            view._h = None          # borrowed: never destroyed from here
+
+    def info(self) -> Dict[str, int]:
+        raise NotImplementedError("a MultiSpatializer has one info() per shard: shard_info(i)")
+
+    def pinned_empty(self, shape, dtype=np.float32) -> np.ndarray:
+        """A numpy array over page-locked host memory that every device of the handle can DMA (aw_multi_alloc_pinned)."""
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        p = ctypes.c_void_p()
+        _check(self._lib.aw_multi_alloc_pinned(self._h, n, ctypes.byref(p)))
+        owner = _MultiPinnedOwner(self, p.value, max(n, 1))
+        return np.asarray(owner)[:n].view(dtype).reshape(shape)
+
+    def process(self, x) -> np.ndarray:
+        """x: [streams][frames][channels] float32 host array; returns [streams][frames][2]."""
+        a = _f32(x)
+        S, F, C = a.shape
+        assert S == self.n_streams and C == self.n_channels
+        out = np.full((S, F, 2), np.nan, dtype=np.float32)
+        self.process_host_into(a, out)
+        return out
+
+    def process_host_into(self, x: np.ndarray, out: np.ndarray, in_format=None, out_format=None) -> int:
+        """aw_multi_process_host_pcm on caller-owned arrays (e.g. pinned_empty), formats as Spatializer.process_host_into; returns the
+        clipped-sample count summed over the shards."""
+        if not isinstance(x, np.ndarray) or x.ndim < 3:
+            raise ValueError("x: [streams][frames][channels] array required")
+        F = x.shape[1]
+        x, fi = _pcm_array(x, in_format, (self.n_streams, F, self.n_channels), "x")
+        out, fo = _pcm_array(out, out_format, (self.n_streams, F, 2), "out")
+        clipped = ctypes.c_uint64(0)
+        _check(self._lib.aw_multi_process_host_pcm(self._h, ctypes.c_void_p(x.ctypes.data), fi, ctypes.c_void_p(out.ctypes.data), fo, F, ctypes.byref(clipped)))
+        return int(clipped.value)
+
+    def reserve_pcm(self, max_frames: int, in_format="f32", out_format="f32") -> None:
+        fi = SAMPLE_FORMATS.get(in_format, -1) if isinstance(in_format, str) else int(in_format)
+        fo = SAMPLE_FORMATS.get(out_format, -1) if isinstance(out_format, str) else int(out_format)
+        _check(self._lib.aw_multi_reserve_pcm(self._h, int(max_frames), fi, fo))
+
+    def reset(self) -> None:
+        _check(self._lib.aw_multi_reset(self._h))
+
+    # the entries of one handle that the multi handle does not have
+    def _not_here(self, *a, **k):
+        raise NotImplementedError("not an entry of the multi-device handle (host buffers only)")
+
+    process_device = process_planar = process_pcm_device = reserve = reserve_host = set_profiling = kernel_time = stage_times = _not_here
 
 
 class ConvolutionEngine:

@@ -45,6 +45,7 @@ SOURCES = [
     "runtime.cpp",
     "eq_runtime.cpp",
     "rateconv_runtime.cpp",
+    "multi_runtime.cpp",
     "host/eq.cpp",
     "host/tables.cpp",
     "host/host_api.cpp",

@@ -1,6 +1,7 @@
 // device_buf.hpp — the owners of what the HIP runtime hands out by raw handle: Buf<T, Kind> (device or page-locked host memory) and Event.
 // Every allocation the library keeps for itself lives in one of them: the destructor of whatever holds it frees it, and an early return
-// cannot leak it.  Only aw_device_alloc / aw_host_alloc_pinned, which give the pointer to the caller, name the allocation calls themselves.
+// cannot leak it.  Only aw_device_alloc / aw_host_alloc_pinned, which give the pointer to the caller, name the allocation calls themselves;
+// a further unit that hands page-locked memory to its caller (aw_multi_alloc_pinned) goes through host_alloc_raw / host_free_raw below.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -59,6 +60,10 @@ template <class T, Kind K = Kind::device> class Buf {
         return e;
     }
 };
+
+// Page-locked host memory that leaves the library (the caller owns it and gives it back): the allocation flags are the caller's business.
+inline hipError_t host_alloc_raw(void **p, size_t bytes, unsigned flags) { return hipHostMalloc(p, bytes, flags); }
+inline hipError_t host_free_raw(void *p) { return hipHostFree(p); }
 
 // The single named events.  Pooled and pending events circulate as raw handles and are not these.
 class Event {

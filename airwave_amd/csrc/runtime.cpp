@@ -206,7 +206,7 @@ const char *aw_status_string(aw_status s) {
 }
 
 /* ---- context ------------------------------------------------------------------------------ */
-static aw_status context_create_impl(int32_t device, void *ext_stream, bool use_ext, aw_context **out) {
+static aw_status context_create_impl(int32_t device, void *ext_stream, bool use_ext, aw_context **out, int32_t copy_divisor = 1) {
     if (!out) return fail(AW_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
     int count = 0;
@@ -218,6 +218,7 @@ static aw_status context_create_impl(int32_t device, void *ext_stream, bool use_
     aw_context *c = owner.get();
     if (!c) return fail(AW_ERR_OUT_OF_MEMORY, "context");
     c->device = device;
+    c->copy_divisor = std::max(1, copy_divisor);
     if (use_ext) {
         c->stream = reinterpret_cast<hipStream_t>(ext_stream);
         c->owns_stream = false;
@@ -1361,10 +1362,11 @@ static aw_status host_pipeline_objects(aw_context *c) {
     if (c->s_h2d && c->s_d2h && c->ev_d2h[1]) return AW_OK;           // (ev_d2h[1] is the last object made below)
     if (!c->copy_pool) {
         const unsigned hw = std::thread::hardware_concurrency();
-        c->copy_pool = new (std::nothrow) aw_context::CopyPool((int)std::min(12u, std::max(1u, hw / 4)));
+        const unsigned div = (unsigned)c->copy_divisor;          // (1 unless a multi-device handle made the context)
+        c->copy_pool = new (std::nothrow) aw_context::CopyPool((int)std::max(1u, std::min(12u, std::max(1u, hw / 4)) / div));
         if (!c->copy_pool) return fail(AW_ERR_OUT_OF_MEMORY, "copy threads");
         // the output direction moves a quarter or less of the input's bytes (8 against 4 C per frame): a few threads of its own
-        c->copy_pool_out = new (std::nothrow) aw_context::CopyPool((int)std::min(4u, std::max(1u, hw / 8)));
+        c->copy_pool_out = new (std::nothrow) aw_context::CopyPool((int)std::max(1u, std::min(4u, std::max(1u, hw / 8)) / div));
         if (!c->copy_pool_out) return fail(AW_ERR_OUT_OF_MEMORY, "copy threads");
     }
     // (a failure half-way leaves what exists in place: the next call makes the rest, the context's destructor frees whatever is there)
@@ -1943,15 +1945,7 @@ aw_status aw_spatializer_set_loudness(aw_spatializer *sp, int32_t on, double max
 static aw_status eq_setter_args(const aw_spatializer *sp, const aw_eq_definition *const *definitions, int32_t n_definitions, const int32_t *stream_definition,
                                 int32_t lowest, bool check_without_definitions) {
     if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
-    if (n_definitions < 0) return fail(AW_ERR_INVALID_ARGUMENT, "n_definitions must be >= 0");
-    if (n_definitions > 0 && !definitions) return fail(AW_ERR_INVALID_ARGUMENT, "definitions is NULL");
-    for (int32_t i = 0; i < n_definitions; ++i)
-        if (!definitions[i]) return fail(AW_ERR_INVALID_ARGUMENT, "definition " + std::to_string(i) + " is NULL");
-    for (int s = 0; stream_definition && (n_definitions > 0 || check_without_definitions) && s < sp->n_streams; ++s)
-        if (stream_definition[s] < lowest || stream_definition[s] >= n_definitions)
-            return fail(AW_ERR_INVALID_ARGUMENT, "stream_definition[" + std::to_string(s) + "] = " + std::to_string(stream_definition[s]) + " is outside [" +
-                                                     std::to_string(lowest) + ", n_definitions)");
-    return AW_OK;
+    return awr::eq_map_args(definitions, n_definitions, stream_definition, sp->n_streams, lowest, check_without_definitions);
 }
 
 static aw_status eq_prepare_all(const aw_spatializer *sp, const aw_eq_definition *const *definitions, int32_t n_definitions, std::vector<awh::EqPrepared> *prep) {
@@ -2239,15 +2233,7 @@ aw_status aw_spatializer_get_limiter(aw_spatializer *sp, int32_t first_stream, i
 // Checks first, then the allocation and the upload (here, never on the process path); the setting changes only when all of it worked.
 aw_status aw_spatializer_set_gain(aw_spatializer *sp, aw_gain_mode mode, const float *gains_host, int32_t n, float ceiling) try {
     if (!sp) return fail(AW_ERR_INVALID_ARGUMENT, "sp is NULL");
-    if (mode != AW_GAIN_NONE && mode != AW_GAIN_FIXED && mode != AW_GAIN_PEAK_CEILING && mode != AW_GAIN_TRUE_PEAK_CEILING)
-        return fail(AW_ERR_INVALID_ARGUMENT, "unknown gain mode");
-    if (mode == AW_GAIN_FIXED) {
-        if (!gains_host) return fail(AW_ERR_INVALID_ARGUMENT, "gains_host is NULL");
-        if (n != 1 && n != sp->n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "n must be 1 or the stream count");
-        for (int32_t i = 0; i < n; ++i)
-            if (!std::isfinite(gains_host[i])) return fail(AW_ERR_INVALID_ARGUMENT, "gains must be finite");
-    }
-    if ((mode == AW_GAIN_PEAK_CEILING || mode == AW_GAIN_TRUE_PEAK_CEILING) && !(ceiling > 0.0f && ceiling <= 1.0f)) return fail(AW_ERR_INVALID_ARGUMENT, "ceiling must lie in (0, 1]");
+    if (const aw_status args = awr::gain_args(mode, gains_host, n, sp->n_streams, ceiling)) return args;
     if ((mode == AW_GAIN_PEAK_CEILING || mode == AW_GAIN_TRUE_PEAK_CEILING) && sp->lim.on)
         return fail(AW_ERR_INVALID_ARGUMENT, "a per-call ceiling gain cannot feed the limiter: switch the limiter off first");
     if (mode == AW_GAIN_NONE) { sp->lv.gain_mode = AW_GAIN_NONE; return AW_OK; }
@@ -2472,3 +2458,31 @@ aw_status aw_synth_fill(aw_context *ctx, float *dst, int32_t n_streams, int64_t 
 } AW_NOEXCEPT_TAIL
 
 }  // extern "C"
+
+aw_status awr::context_create_divided(int32_t device, int32_t copy_divisor, aw_context **out) { return context_create_impl(device, nullptr, false, out, copy_divisor); }
+
+aw_status awr::eq_map_args(const aw_eq_definition *const *definitions, int32_t n_definitions, const int32_t *stream_definition, int32_t n_streams,
+                           int32_t lowest, bool check_without_definitions) {
+    if (n_definitions < 0) return fail(AW_ERR_INVALID_ARGUMENT, "n_definitions must be >= 0");
+    if (n_definitions > 0 && !definitions) return fail(AW_ERR_INVALID_ARGUMENT, "definitions is NULL");
+    for (int32_t i = 0; i < n_definitions; ++i)
+        if (!definitions[i]) return fail(AW_ERR_INVALID_ARGUMENT, "definition " + std::to_string(i) + " is NULL");
+    for (int s = 0; stream_definition && (n_definitions > 0 || check_without_definitions) && s < n_streams; ++s)
+        if (stream_definition[s] < lowest || stream_definition[s] >= n_definitions)
+            return fail(AW_ERR_INVALID_ARGUMENT, "stream_definition[" + std::to_string(s) + "] = " + std::to_string(stream_definition[s]) + " is outside [" +
+                                                     std::to_string(lowest) + ", n_definitions)");
+    return AW_OK;
+}
+
+aw_status awr::gain_args(aw_gain_mode mode, const float *gains_host, int32_t n, int32_t n_streams, float ceiling) {
+    if (mode != AW_GAIN_NONE && mode != AW_GAIN_FIXED && mode != AW_GAIN_PEAK_CEILING && mode != AW_GAIN_TRUE_PEAK_CEILING)
+        return fail(AW_ERR_INVALID_ARGUMENT, "unknown gain mode");
+    if (mode == AW_GAIN_FIXED) {
+        if (!gains_host) return fail(AW_ERR_INVALID_ARGUMENT, "gains_host is NULL");
+        if (n != 1 && n != n_streams) return fail(AW_ERR_INVALID_ARGUMENT, "n must be 1 or the stream count");
+        for (int32_t i = 0; i < n; ++i)
+            if (!std::isfinite(gains_host[i])) return fail(AW_ERR_INVALID_ARGUMENT, "gains must be finite");
+    }
+    if ((mode == AW_GAIN_PEAK_CEILING || mode == AW_GAIN_TRUE_PEAK_CEILING) && !(ceiling > 0.0f && ceiling <= 1.0f)) return fail(AW_ERR_INVALID_ARGUMENT, "ceiling must lie in (0, 1]");
+    return AW_OK;
+}

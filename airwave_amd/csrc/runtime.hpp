@@ -25,6 +25,15 @@ aw_status hip_fail(hipError_t e, const char *what);
 // awh::eq_prepare of a definition (NULL: unity) with its refusals as the statuses and messages aw_eq_state_create gives (eq_runtime.cpp)
 aw_status eq_prepare_checked(const awh::EqDefinition *def, double sample_rate, awh::EqPrepared &prep);
 bool context_literal_resampler(const aw_context *ctx);
+// The argument checks of the per-stream setters, by stream count, so that the single handle (runtime.cpp) and the multi-device handle
+// (multi_runtime.cpp, which validates a whole argument before it touches a shard) answer with one order and one wording.
+// eq_map_args: lowest = the smallest map entry allowed (-1, or AW_EQ_KEEP); gain_args: mode, gains and ceiling of aw_spatializer_set_gain.
+aw_status eq_map_args(const aw_eq_definition *const *definitions, int32_t n_definitions, const int32_t *stream_definition, int32_t n_streams,
+                      int32_t lowest, bool check_without_definitions);
+aw_status gain_args(aw_gain_mode mode, const float *gains_host, int32_t n, int32_t n_streams, float ceiling);
+// aw_context_create for a handle that drives several contexts side by side (multi_runtime.cpp): the host entry's copy pools of this context
+// get max(1, default / copy_divisor) threads each, so that D contexts do not start D times the threads.  Not part of the ABI.
+aw_status context_create_divided(int32_t device, int32_t copy_divisor, aw_context **out);
 // The C ABI promises "no exceptions": every entry point that can allocate host memory (containers, strings, threads) is a
 // function-try-block whose handler returns caught() — std::bad_alloc / std::length_error become AW_ERR_OUT_OF_MEMORY, anything else
 // AW_ERR_INVALID_ARGUMENT with the exception's text in aw_last_error_message().  Handles under construction are held by Owner<> until
@@ -64,6 +73,7 @@ struct aw_context {
     struct CopyPool;                                                // a few host threads that copy slices of one buffer at a time (runtime.cpp)
     CopyPool *copy_pool_out = nullptr;                              // a second, smaller pool for the output direction (copy OUT of chunk k-1 beside copy IN of chunk k+1)
     CopyPool *copy_pool = nullptr;                                  // made with the pipeline objects; pageable caller buffers are bounced through page-locked chunks by it
+    int copy_divisor = 1;                                           // both pools get max(1, default / copy_divisor) threads (awr::context_create_divided; 1 through the ABI's entries)
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     awr::Event ev_h2d[2], ev_run[2], ev_d2h[2];
 };

@@ -833,6 +833,109 @@ AW_API aw_status aw_tp_rateconv_measure(aw_rateconv *rc, const void *in_device, 
                                         int64_t *out_frames);
 AW_API aw_status aw_tp_rateconv_measure_flush(aw_rateconv *rc, int64_t *out_frames);
 
+/* ---- multi-device batch spatializer ------------------------------------------------------------
+ * One handle, N devices: a single-process host in C or Swift spreads a batch over the GPUs of a box without RCCL, a second process or
+ * threads of its own.  No counterpart in the reference, which renders one stream on one CPU.  There is no new arithmetic here: a shard is
+ * an aw_context + aw_hrir + aw_spatializer of the library, driven through the single-handle entries above.
+ *
+ * Devices.  aw_device_count returns the number of visible HIP devices, 0 when there is none or no driver; it never fails.
+ * aw_device_info fills the struct below (the struct tag and the function share a name, so C code writes `struct aw_device_info`); an
+ * ordinal out of range returns AW_ERR_NO_DEVICE, as aw_context_create does.  The calling thread's current device is left as it was.
+ * Asking for the free memory initialises the HIP runtime on that device, as creating a context there would: on a shared box ask only
+ * about the devices you mean to use. */
+struct aw_device_info {
+    char     name[256];        /* marketing name, NUL-terminated */
+    char     arch[64];         /* architecture name as the runtime reports it, e.g. "gfx950:sramecc+:xnack-" */
+    int32_t  compute_units;
+    int32_t  reserved;         /* 0 */
+    uint64_t total_bytes;      /* device memory */
+    uint64_t free_bytes;       /* ... of which free at the time of the call */
+};                             /* 344 bytes */
+AW_API int32_t aw_device_count(void);
+AW_API aw_status aw_device_info(int32_t ordinal, struct aw_device_info *out);
+/* The shard rule (airwave_amd/csrc/host/shard_plan.hpp; airwave_amd/sharding.py's shard_streams): with D = n_devices, q = n_streams / D and
+ * r = n_streams % D, shard i owns the contiguous streams [i q + min(i, r), + q + (i < r ? 1 : 0)): stream order is kept and the first r
+ * shards are one stream longer.  Shard i lives on device_ordinals[i]; an ordinal may repeat, which puts several contexts on one device
+ * (how a one-GPU box runs this code).  D > n_streams leaves the last shards empty: an empty shard owns nothing and starts no thread.
+ *
+ * What equals what.  Output bytes, the clipped total and every record of the multi handle equal, bit for bit, those of separately created
+ * single handles, one per non-empty shard — aw_spatializer_create with the shard's stream count on a context of its own on that ordinal —
+ * given the same slices of the buffers, the same sequence of calls and the same settings, aw_spatializer_set_dither with first_stream +
+ * the shard's first stream.  The one exception is aw_stream_levels.energy, which no two runs of any handle reproduce bit for bit: its float64
+ * additions come in an unspecified order ("per-stream output levels" above), so it agrees within that section's bound, N * 2^-53 relative
+ * over N samples.  Against ONE handle of n_streams streams only the library's tolerance holds (1e-5 of peak against the float64
+ * oracle): the kernels of a call are chosen from the handle's stream count and the call's length (aw_spatializer_info 0-3 and 7), so a
+ * shard of 512 streams may run other kernels than a handle of 1024.  Where those figures agree between the big handle and every shard,
+ * the "sharding over handles changes no bit" statements of the sections above apply.
+ *
+ * Threads.  aw_multi_create starts one persistent thread per non-empty shard; they sleep between calls.  aw_multi_reserve_pcm and
+ * aw_multi_process_host_pcm run on them, one shard each, side by side, and return when every shard has finished: no work of a call
+ * outlives it.  Every other entry runs on the caller's thread, shard after shard.  The handle is single-owner like every handle: one call
+ * at a time.  The contexts' copy threads (pageable buffers) are divided among the shards: each context gets max(1, default / non-empty
+ * shards) of them.  After aw_multi_reserve_pcm a process call of up to max_frames frames in those formats allocates nothing, on the host
+ * or on any device, and starts no thread.
+ *
+ * Failures.  A failing shard's status is returned — of several, the lowest shard index — and aw_last_error_message() of the CALLING
+ * thread carries that shard's message prefixed with "shard i (device o): ".  A failed aw_multi_create has destroyed what it built.  After
+ * a failed process call the output contents and the streams' state are unspecified, as for one handle: aw_multi_reset before reuse.  A
+ * setter validates its whole argument before it touches a shard, so a call refused for its arguments (AW_ERR_INVALID_ARGUMENT) has
+ * changed none; a HIP failure half-way through a setter leaves the shards before it changed: set again or destroy.
+ *
+ * aw_multi_create: n_devices 1 .. 64; tracks [n_tracks][taps] on the host as for aw_hrir_create; the channel map, n_streams (>= 1) and
+ * block_hint as for aw_spatializer_create, whose statuses an unusable HRIR or map gets.  Every argument error is answered before any HIP
+ * call. */
+typedef struct aw_multi aw_multi;
+AW_API aw_status aw_multi_create(const int32_t *device_ordinals, int32_t n_devices, const float *tracks, int32_t n_tracks, int32_t taps,
+                                 double sample_rate, int32_t n_in_channels, const int32_t *left_track, const int32_t *right_track,
+                                 int32_t n_streams, int32_t block_hint, aw_multi **out);
+AW_API void aw_multi_destroy(aw_multi *m);
+AW_API int32_t aw_multi_shard_count(const aw_multi *m);     /* n_devices, empty shards included */
+AW_API int32_t aw_multi_stream_count(const aw_multi *m);
+AW_API int32_t aw_multi_channel_count(const aw_multi *m);
+/* Shard `shard`: its device ordinal, first stream and stream count (0: empty).  Any output may be NULL. */
+AW_API aw_status aw_multi_shard(const aw_multi *m, int32_t shard, int32_t *device_ordinal, int32_t *first_stream, int32_t *count);
+/* BORROWED handles of a shard, NULL for an empty shard or an index out of range: for aw_spatializer_info, profiling and the probes.  Do
+ * not process, configure, reset or destroy through them: the multi handle owns them and keeps its shards in step. */
+AW_API aw_spatializer *aw_multi_spatializer(const aw_multi *m, int32_t shard);
+AW_API aw_context *aw_multi_context(const aw_multi *m, int32_t shard);
+/* aw_spatializer_reserve_pcm of every shard, on the workers. */
+AW_API aw_status aw_multi_reserve_pcm(aw_multi *m, int64_t max_frames, aw_sample_format in_format, aw_sample_format out_format);
+/* HOST buffers laid out as ONE handle of n_streams streams takes them: in [stream][frames][n_in_channels], out [stream][frames][2],
+ * elements of the given formats.  Shard i runs aw_spatializer_process_host_pcm on its slice (F32 / F32: aw_spatializer_process_host) on
+ * its own worker.  clipped: NULL, or receives the sum over the shards.  Synchronous. */
+AW_API aw_status aw_multi_process_host_pcm(aw_multi *m, const void *in_host, aw_sample_format in_format, void *out_host,
+                                           aw_sample_format out_format, int64_t frames, uint64_t *clipped);
+AW_API aw_status aw_multi_reset(aw_multi *m);               /* aw_spatializer_reset of every shard */
+/* Page-locked host memory that EVERY device of the handle can DMA (hipHostMalloc, portable): with buffers from here each shard's slice
+ * takes the DMA path of the host entry, not the bounce path.  Free it before the handle is destroyed. */
+AW_API aw_status aw_multi_alloc_pinned(aw_multi *m, size_t bytes, void **ptr);
+AW_API aw_status aw_multi_free_pinned(aw_multi *m, void *ptr);
+/* The settings of the single handle, each shard given its slice.  Arguments, defaults and errors are those of the aw_spatializer_* entry
+ * of the same name; per-stream arrays (gains_host with n == n_streams, stream_definition) hold one entry per stream of the multi handle.
+ *  - set_dither: shard i gets first_stream + its first stream, so the handle's noise is that of one handle holding every stream, and the
+ *    multi handle can itself be a shard of a larger job.
+ *  - set_equalizer / set_equalizer_target: the definitions go to every shard, stream_definition is sliced (AW_EQ_KEEP where the single
+ *    entry allows it), NULL stays NULL. */
+AW_API aw_status aw_multi_set_dither(aw_multi *m, aw_dither mode, uint64_t seed, uint64_t first_stream);
+AW_API aw_status aw_multi_set_metering(aw_multi *m, int32_t on);
+AW_API aw_status aw_multi_reset_levels(aw_multi *m);
+AW_API aw_status aw_multi_set_gain(aw_multi *m, aw_gain_mode mode, const float *gains_host, int32_t n, float ceiling);
+AW_API aw_status aw_multi_set_loudness(aw_multi *m, int32_t on, double max_seconds);
+AW_API aw_status aw_multi_set_true_peak(aw_multi *m, int32_t on);
+AW_API aw_status aw_multi_set_limiter(aw_multi *m, int32_t on, float ceiling, int32_t attack_frames, int32_t hold_frames);
+AW_API aw_status aw_multi_set_equalizer(aw_multi *m, const aw_eq_definition *const *definitions, int32_t n_definitions,
+                                        const int32_t *stream_definition);
+AW_API aw_status aw_multi_set_equalizer_target(aw_multi *m, const aw_eq_definition *const *definitions, int32_t n_definitions,
+                                               const int32_t *stream_definition);
+/* The records of the GLOBAL streams [first_stream, first_stream + n), gathered across shard boundaries; each shard's part is what the
+ * aw_spatializer_get_* entry of the same name returns (and synchronises that shard's stream).  get_loudness_hops goes to the shard that
+ * owns the stream. */
+AW_API aw_status aw_multi_get_levels(aw_multi *m, int32_t first_stream, int32_t n, aw_stream_levels *out_host);
+AW_API aw_status aw_multi_get_loudness(aw_multi *m, int32_t first_stream, int32_t n, aw_stream_loudness *out_host);
+AW_API aw_status aw_multi_get_loudness_hops(aw_multi *m, int32_t stream, int64_t first_hop, int64_t n, double *out_host);
+AW_API aw_status aw_multi_get_true_peak(aw_multi *m, int32_t first_stream, int32_t n, aw_stream_true_peak *out_host);
+AW_API aw_status aw_multi_get_limiter(aw_multi *m, int32_t first_stream, int32_t n, aw_stream_limiter *out_host);
+
 AW_API const char *aw_version(void);
 
 #ifdef __cplusplus

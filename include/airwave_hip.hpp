@@ -168,6 +168,87 @@ class Spatializer {
     aw_spatializer *h_ = nullptr;
 };
 
+// aw_device_count / aw_device_info
+inline int deviceCount() { return aw_device_count(); }
+inline struct aw_device_info deviceInfo(int ordinal) {          // (the C function of the same name hides the plain struct name)
+    struct aw_device_info d;
+    check(::aw_device_info(ordinal, &d));
+    return d;
+}
+
+// aw_multi: the batch spatializer over several devices behind one handle (one ordinal per shard; an ordinal may repeat).  Host buffers laid
+// out as one Spatializer of nStreams streams takes them; bit-exact against separately driven Spatializers of the shards' stream counts.
+class MultiSpatializer {
+  public:
+    struct Shard { int32_t ordinal, firstStream, count; };
+    MultiSpatializer(const std::vector<int32_t> &devices, const float *tracks, int nTracks, int taps, double sampleRate,
+                     const std::vector<int32_t> &leftTrack, const std::vector<int32_t> &rightTrack, int nStreams) {
+        check(aw_multi_create(devices.data(), (int32_t)devices.size(), tracks, nTracks, taps, sampleRate, (int32_t)leftTrack.size(), leftTrack.data(),
+                              rightTrack.data(), nStreams, 0, &h_));
+    }
+    ~MultiSpatializer() { aw_multi_destroy(h_); }
+    MultiSpatializer(const MultiSpatializer &) = delete;
+    MultiSpatializer &operator=(const MultiSpatializer &) = delete;
+    int streamCount() const { return aw_multi_stream_count(h_); }
+    int channelCount() const { return aw_multi_channel_count(h_); }
+    std::vector<Shard> shards() const {
+        std::vector<Shard> out((size_t)aw_multi_shard_count(h_));
+        for (size_t i = 0; i < out.size(); ++i) check(aw_multi_shard(h_, (int32_t)i, &out[i].ordinal, &out[i].firstStream, &out[i].count));
+        return out;
+    }
+    int64_t shardInfo(int32_t shard, int32_t what) const { return aw_spatializer_info(aw_multi_spatializer(h_, shard), what); }   // (borrowed handle)
+    void reservePcm(int64_t maxFrames, aw_sample_format inFormat, aw_sample_format outFormat) { check(aw_multi_reserve_pcm(h_, maxFrames, inFormat, outFormat)); }
+    uint64_t processPcmHost(const void *in, aw_sample_format inFormat, void *out, aw_sample_format outFormat, int64_t frames) {
+        uint64_t clipped = 0;
+        check(aw_multi_process_host_pcm(h_, in, inFormat, out, outFormat, frames, &clipped));
+        return clipped;
+    }
+    void processHost(const float *in, float *out, int64_t frames) { check(aw_multi_process_host_pcm(h_, in, AW_SAMPLE_F32, out, AW_SAMPLE_F32, frames, nullptr)); }
+    void reset() { check(aw_multi_reset(h_)); }
+    // page-locked host memory every device of the handle can DMA; free it before the handle goes
+    void *allocPinned(size_t bytes) { void *p = nullptr; check(aw_multi_alloc_pinned(h_, bytes, &p)); return p; }
+    void freePinned(void *p) { check(aw_multi_free_pinned(h_, p)); }
+    void setDither(aw_dither mode, uint64_t seed = 0, uint64_t firstStream = 0) { check(aw_multi_set_dither(h_, mode, seed, firstStream)); }
+    void setMetering(bool on) { check(aw_multi_set_metering(h_, on ? 1 : 0)); }
+    void resetLevels() { check(aw_multi_reset_levels(h_)); }
+    void setGainNone() { check(aw_multi_set_gain(h_, AW_GAIN_NONE, nullptr, 0, 0.0f)); }
+    void setGainFixed(const std::vector<float> &gains) { check(aw_multi_set_gain(h_, AW_GAIN_FIXED, gains.data(), (int32_t)gains.size(), 0.0f)); }
+    void setGainPeakCeiling(float ceiling) { check(aw_multi_set_gain(h_, AW_GAIN_PEAK_CEILING, nullptr, 0, ceiling)); }
+    void setGainTruePeakCeiling(float ceiling) { check(aw_multi_set_gain(h_, AW_GAIN_TRUE_PEAK_CEILING, nullptr, 0, ceiling)); }
+    void setLoudness(bool on, double maxSeconds = 0.0) { check(aw_multi_set_loudness(h_, on ? 1 : 0, maxSeconds)); }
+    void setTruePeak(bool on) { check(aw_multi_set_true_peak(h_, on ? 1 : 0)); }
+    void setLimiter(bool on, float ceiling = 1.0f, int32_t attackFrames = 64, int32_t holdFrames = 128) {
+        check(aw_multi_set_limiter(h_, on ? 1 : 0, ceiling, attackFrames, holdFrames));
+    }
+    // streamDefinition: empty (every stream takes preset 0) or one entry per stream of the multi handle
+    void setEqualizer(const std::vector<const aw_eq_definition *> &definitions, const std::vector<int32_t> &streamDefinition = {}) {
+        if (!streamDefinition.empty() && streamDefinition.size() != (size_t)streamCount()) throw Error(AW_ERR_INVALID_ARGUMENT, "streamDefinition needs one entry per stream");
+        check(aw_multi_set_equalizer(h_, definitions.data(), (int32_t)definitions.size(), streamDefinition.empty() ? nullptr : streamDefinition.data()));
+    }
+    void setEqualizerTarget(const std::vector<const aw_eq_definition *> &definitions, const std::vector<int32_t> &streamDefinition = {}) {
+        if (!streamDefinition.empty() && streamDefinition.size() != (size_t)streamCount()) throw Error(AW_ERR_INVALID_ARGUMENT, "streamDefinition needs one entry per stream");
+        check(aw_multi_set_equalizer_target(h_, definitions.data(), (int32_t)definitions.size(), streamDefinition.empty() ? nullptr : streamDefinition.data()));
+    }
+    // records of the global streams [firstStream, firstStream + n), gathered across the shards
+    std::vector<aw_stream_levels> levels(int32_t firstStream, int32_t n) { return records<aw_stream_levels>(firstStream, n, aw_multi_get_levels); }
+    std::vector<aw_stream_loudness> loudness(int32_t firstStream, int32_t n) { return records<aw_stream_loudness>(firstStream, n, aw_multi_get_loudness); }
+    std::vector<aw_stream_true_peak> truePeak(int32_t firstStream, int32_t n) { return records<aw_stream_true_peak>(firstStream, n, aw_multi_get_true_peak); }
+    std::vector<aw_stream_limiter> limiter(int32_t firstStream, int32_t n) { return records<aw_stream_limiter>(firstStream, n, aw_multi_get_limiter); }
+    std::vector<double> loudnessHops(int32_t stream, int64_t firstHop, int64_t count) {
+        std::vector<double> out((size_t)count);
+        check(aw_multi_get_loudness_hops(h_, stream, firstHop, count, out.data()));
+        return out;
+    }
+    aw_multi *get() const { return h_; }
+  private:
+    template <class R> std::vector<R> records(int32_t firstStream, int32_t n, aw_status (*get)(aw_multi *, int32_t, int32_t, R *)) {
+        std::vector<R> out((size_t)(n > 0 ? n : 0));
+        check(get(h_, firstStream, n, out.data()));
+        return out;
+    }
+    aw_multi *h_ = nullptr;
+};
+
 // RealtimeAudioProcessor.swift:11-191
 class RealtimeAudioProcessor {
   public:
